@@ -18,7 +18,13 @@ order and parameters, bit counts -- and put both into stream order (ParSink's or
 src/par.rs:67-95).  `--gather payload` moves the packed FLAC frame bytes as well, `--gather lengths`
 only what ordering needs.  The exchange of step k runs on its own HIP stream under step k + 1.
 
+A plain run sets up, warms up, times --steps steps and prints one JSON line; `ms_per_step` is the wall time of one timed
+step.  `--full` adds what the headline does not need: the `secondary` measurements (other configurations, sizes, summation
+orders, the host path), the CPU baseline and the reference-identity check.  `--dump-outputs DIR` writes what the last timed
+step computed as .npy files (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
+
     python bench.py                         # 1 GPU
+    python bench.py --full                  # + secondary, cpu_baseline, reference identity
     python bench.py --gpus 8                # starts 8 ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N   # or let a launcher start the ranks
@@ -89,9 +95,16 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU check of the launch and exchange plumbing (no GPU, no analysis, no "
                          "measurement): stand-in records, real sharding + collectives over gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run what it does not need: the `secondary` measurements, "
+                         "the CPU baseline and the reference-identity check (each still off with --no-secondary / "
+                         "--no-cpu-baseline).  A plain run times the steps and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's decision records and a "
+                         "seeded sample of its residual rows) as DIR/<name>.npy in float32 / float64, at most 64 MB")
     return ap.parse_args(argv)
 
 
@@ -126,6 +139,8 @@ def main():
         raise SystemExit("--shared-gpu-test needs --backend gloo (RCCL wants one device per rank)")
     if args.comm == "capi" and (args.dry_run or args.shared_gpu_test or args.backend == "gloo"):
         raise SystemExit("--comm capi is the library's RCCL communicator: one GPU per rank, no gloo / dry-run form")
+    if args.dump_outputs is not None and (args.dry_run or args.steps < 1):
+        raise SystemExit("--dump-outputs writes the last timed step's outputs: it needs --steps >= 1 and no --dry-run")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args, argv))
@@ -370,8 +385,10 @@ def run(args, world):
     p = np.frombuffer(results2[last_b].cpu().numpy().tobytes(), dtype=_capi.FRAME_RESULT_DTYPE)
     lpc_kind = p["kind"] >= 2
     assert (p["lpc"]["status"][lpc_kind] == 0).all(), "subframe status != 0"
-    chosen_bits = int(sum(int(p["bits"][f, r]) for f in range(F) for r in p["role"][f]))
+    chosen_bits = int(p["bits"][np.arange(F)[:, None], p["role"]].sum())
     assign_hist = np.bincount(p["channel_assignment"], minlength=4).tolist()
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, p, residual, F, n)
     exchange_check = None
     if exchanging:
         exchange_check = check_exchange(torch, dist, last_exchange, results2[last_b], frame_len2[last_b], rank,
@@ -473,9 +490,9 @@ def run(args, world):
         },
     }
 
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         out["secondary"] = secondary(torch, _capi, handle, args, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(host, bps, args, n)
         # the order certificate at work (outside the timed region): the device's counters over one more launch of the
         # whole batch, and a sample of the frames against the oracle in the REFERENCE's summation order
@@ -516,6 +533,44 @@ def check_exchange(torch, dist, ex, my_records, my_lengths, rank, world, F, my_p
         ok &= int(lo.item()) == int(hi.item())
     assert ok, "multi-GPU exchange delivered wrong data"
     return {"ok": ok, "stream_frames": int(lengths_all.numel()), "stream_bytes": int(total.item())}
+
+
+DUMP_SEED = 0xF1AC0D0F
+DUMP_MAX_BYTES = 64 << 20
+DUMP_RECORD_FRAMES = 1 << 17   # the records' scalar fields: every frame up to this many (22 MB), a seeded sample beyond
+DUMP_SAMPLE_FRAMES = 512       # residual rows + the records' wide fields: a seeded sample of frames ...
+DUMP_SAMPLE_BYTES = 40 << 20   # ... within this many bytes
+
+
+def dump_outputs(path, records, residual, F, n):
+    """--dump-outputs: what a caller of flacenc_hip_encode_stereo_frames receives from the last timed step, in a form two
+    builds can be compared by: the scalar fields of the decision records (8- / 16-bit integers as float32, wider ones as
+    float64: exact), and for a fixed sample of frames the wide fields (coefficients, Rice parameters) and the two chosen
+    residual rows.  `frame_index` / `sample_frame_index` are the frames the rows belong to."""
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.arange(F) if F <= DUMP_RECORD_FRAMES else np.sort(rng.choice(F, DUMP_RECORD_FRAMES, replace=False))
+    per_frame = 2 * n * 8 + 2 * (32 + 256) * 4
+    sample = np.sort(rng.choice(F, max(1, min(F, DUMP_SAMPLE_FRAMES, DUMP_SAMPLE_BYTES // per_frame)), replace=False))
+
+    def as_float(a):
+        return a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+
+    out = {"frame_index": rows.astype(np.float64), "sample_frame_index": sample.astype(np.float64)}
+    fields = [(name, records[name]) for name in records.dtype.names if name not in ("pad", "lpc")]
+    fields += [("lpc_" + name, records["lpc"][name]) for name in records.dtype["lpc"].base.names]
+    for name, a in fields:
+        # (per frame: [2] or [4] for the scalar fields; [2, 32] coefficients and [2, 256] Rice parameters are wide)
+        out[name] = as_float(a[sample] if a.ndim > 2 else a[rows])
+    picked = torch.from_numpy(sample).to(residual.device)
+    out["residual"] = residual.view(F, 2, n).index_select(0, picked).cpu().numpy().astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def secondary(torch, _capi, handle, args, dev):

@@ -5,7 +5,7 @@ TAG=$1
 export GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-$PWD}
 O=$GRAFT_REPO_ROOT/gpurun_out/collect_$TAG; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1
 bash tools/profile_stages.sh $TAG > $O/profile_stages.log 2>&1
 python3 tools/bench_configs.py > $O/configs.json 2> $O/configs.txt
