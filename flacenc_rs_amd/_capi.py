@@ -41,6 +41,10 @@ FLAG_ALLOW_ORDER_32 = 1
 MEM_HOST = 0
 MEM_DEVICE = 1
 COMM_ID_BYTES = 128  # FLACENC_HIP_COMM_ID_BYTES
+# FLACENC_HIP_DECODE_* status bits of the frame decoder, FLACENC_HIP_INDEX_ERROR
+DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 8
+DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
+INDEX_ERROR = 1 << 63
 
 # every symbol include/flacenc_hip.h declares
 ABI_VERSION = 6  # FLACENC_HIP_ABI_VERSION of include/flacenc_hip.h
@@ -90,6 +94,10 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_comm_info",
     "flacenc_hip_allgather_async",
     "flacenc_hip_allgather_records_async",
+    "flacenc_hip_decode_frames_async",
+    "flacenc_hip_decode_frames",
+    "flacenc_hip_verify_frames_async",
+    "flacenc_hip_index_frames_async",
     "flacenc_hip_synchronize",
     "flacenc_sigen_fill_frames",
     "flacenc_sigen_fill_frames_strided",
@@ -336,6 +344,18 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_encode_stereo_frames.restype = C.c_int
     L.flacenc_hip_encode_stereo_frames_async.argtypes = frame_args + [vp]
     L.flacenc_hip_encode_stereo_frames_async.restype = C.c_int
+    L.flacenc_hip_decode_frames_async.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                                  C.c_size_t, vp, vp, vp, vp]
+    L.flacenc_hip_decode_frames_async.restype = C.c_int
+    L.flacenc_hip_decode_frames.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            vp, C.c_size_t, vp, vp, vp, C.c_int]
+    L.flacenc_hip_decode_frames.restype = C.c_int
+    L.flacenc_hip_verify_frames_async.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                                  C.c_size_t, vp, vp]
+    L.flacenc_hip_verify_frames_async.restype = C.c_int
+    L.flacenc_hip_index_frames_async.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp,
+                                                 vp]
+    L.flacenc_hip_index_frames_async.restype = C.c_int
     L.flacenc_hip_comm_unique_id.argtypes = [vp]
     L.flacenc_hip_comm_unique_id.restype = C.c_int
     L.flacenc_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -705,6 +725,88 @@ class Handle:
 
     def frame_bytes_bound(self, block_size: int, bits_per_sample: int) -> int:
         return int(self._lib.flacenc_hip_stereo_frame_bytes_bound(block_size, bits_per_sample))
+
+    # -- the way back: decode, verify and index frames --------------------------------------------------------
+    def decode_frames(self, data, offsets, lengths, channels: int, bits_per_sample: int, max_block_size: int):
+        """flacenc_hip_decode_frames on host arrays: frame f = lengths[f] bytes at data[offsets[f]:] ->
+        (samples int32 [n, channels, max_block_size], block_sizes uint32, numbers uint64, status uint32)."""
+        buf = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data,
+                                   np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lengths, np.uint32)
+        n = len(off)
+        out = np.empty((n, channels, max_block_size), np.int32)
+        bs = np.zeros(n, np.uint32)
+        num = np.zeros(n, np.uint64)
+        st = np.zeros(n, np.uint32)
+        rc = self._lib.flacenc_hip_decode_frames(self._h, buf.ctypes.data, buf.size, off.ctypes.data, ln.ctypes.data,
+                                                 n, channels, bits_per_sample, max_block_size, out.ctypes.data,
+                                                 max_block_size, bs.ctypes.data, num.ctypes.data, st.ctypes.data,
+                                                 MEM_HOST)
+        self._check(rc)
+        return out, bs, num, st
+
+    @staticmethod
+    def _device_copy(arr):
+        import torch
+        return torch.from_numpy(np.array(arr, copy=True)).to("cuda")
+
+    def verify_frames(self, data, offsets, lengths, channels: int, bits_per_sample: int, max_block_size: int,
+                      expected):
+        """flacenc_hip_verify_frames_async on host arrays (staged through device tensors): -> status uint32 [n]."""
+        import torch
+        buf = self._device_copy(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data)
+        off = self._device_copy(np.asarray(offsets, np.uint64).view(np.int64))
+        ln = self._device_copy(np.asarray(lengths, np.uint32).view(np.int32))
+        exp = self._device_copy(np.asarray(expected, np.int32))
+        n = len(offsets)
+        st = torch.zeros(n, dtype=torch.int32, device="cuda")
+        self.verify_frames_device(buf.data_ptr(), off.data_ptr(), ln.data_ptr(), n, channels, bits_per_sample,
+                                  max_block_size, exp.data_ptr(), exp.shape[-1], st.data_ptr(),
+                                  torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return st.cpu().numpy().view(np.uint32)
+
+    def index_frames(self, data, channels: int, bits_per_sample: int, max_frames: int):
+        """flacenc_hip_index_frames_async on a host buffer of frames -> (offsets uint64, lengths uint32, ok)."""
+        import torch
+        buf = self._device_copy(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data)
+        off = torch.zeros(max(1, max_frames), dtype=torch.int64, device="cuda")
+        ln = torch.zeros(max(1, max_frames), dtype=torch.int32, device="cuda")
+        nf = torch.zeros(1, dtype=torch.int64, device="cuda")
+        self.index_frames_device(buf.data_ptr() if buf.numel() else 0, buf.numel(), channels, bits_per_sample,
+                                 max_frames, off.data_ptr(), ln.data_ptr(), nf.data_ptr(),
+                                 torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        raw = int(nf.cpu().numpy().view(np.uint64)[0])
+        n = raw & (INDEX_ERROR - 1)
+        return (off.cpu().numpy().view(np.uint64)[:n], ln.cpu().numpy().view(np.uint32)[:n],
+                not (raw & INDEX_ERROR))
+
+    def decode_frames_device(self, bytes_ptr: int, offsets_ptr: int, lengths_ptr: int, n_frames: int, channels: int,
+                             bits_per_sample: int, max_block_size: int, out_ptr: int, stride: int,
+                             block_sizes_ptr: int, numbers_ptr: int | None, status_ptr: int,
+                             stream: int | None = None):
+        rc = self._lib.flacenc_hip_decode_frames_async(self._h, bytes_ptr, offsets_ptr, lengths_ptr, n_frames, channels,
+                                                       bits_per_sample, max_block_size, out_ptr, stride,
+                                                       block_sizes_ptr, numbers_ptr or None, status_ptr,
+                                                       stream or None)
+        self._check(rc)
+
+    def verify_frames_device(self, bytes_ptr: int, offsets_ptr: int, lengths_ptr: int, n_frames: int, channels: int,
+                             bits_per_sample: int, max_block_size: int, expected_ptr: int, stride: int,
+                             status_ptr: int, stream: int | None = None):
+        rc = self._lib.flacenc_hip_verify_frames_async(self._h, bytes_ptr, offsets_ptr, lengths_ptr, n_frames, channels,
+                                                       bits_per_sample, max_block_size, expected_ptr, stride,
+                                                       status_ptr, stream or None)
+        self._check(rc)
+
+    def index_frames_device(self, bytes_ptr: int, n_bytes: int, channels: int, bits_per_sample: int, max_frames: int,
+                            offsets_ptr: int, lengths_ptr: int, n_frames_ptr: int, stream: int | None = None):
+        rc = self._lib.flacenc_hip_index_frames_async(self._h, bytes_ptr or None, n_bytes, channels, bits_per_sample,
+                                                      max_frames, offsets_ptr, lengths_ptr, n_frames_ptr,
+                                                      stream or None)
+        self._check(rc)
 
     # -- the ordered gather's collective (RCCL communicator owned by the handle) ----------
     @staticmethod

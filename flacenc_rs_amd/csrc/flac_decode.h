@@ -1,0 +1,32 @@
+// flac_decode.h -- launchers of the frame decoder's kernels (flac_decode.cpp) for flacenc_hip_api.cpp.
+#ifndef FLACENC_FLAC_DECODE_H_
+#define FLACENC_FLAC_DECODE_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace flacenc_hip {
+
+// scratch of one decode / verify launch of n frames
+size_t decode_scratch_bytes(size_t n_frames);
+
+// decode (expected == NULL) or verify (out == NULL) n_frames frames; n_bytes bounds offsets[f] + lengths[f]
+// (UINT64_MAX when the caller did not give it)
+hipError_t launch_decode_frames(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets,
+                                const uint32_t* lengths, uint32_t n_frames, uint32_t channels, uint32_t bps,
+                                uint32_t max_block_size, int32_t* out, const int32_t* expected, size_t stride,
+                                uint32_t* block_sizes, uint64_t* numbers, uint32_t* status, void* scratch,
+                                hipStream_t stream);
+
+// candidate capacity and scratch of one index launch
+size_t index_candidate_capacity(size_t max_frames);
+size_t index_scratch_bytes(uint64_t n_bytes, size_t capacity);
+
+hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t channels, uint32_t bps,
+                               size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
+                               void* scratch, size_t capacity, hipStream_t stream);
+
+}  // namespace flacenc_hip
+
+#endif  // FLACENC_FLAC_DECODE_H_

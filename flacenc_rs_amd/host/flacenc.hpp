@@ -1048,5 +1048,43 @@ component::Stream encode_with_fixed_block_size(const config::Encoder& config, So
   return stream;
 }
 
+// Frame::decode (src/component/decode.rs:55-110) for a run of frames on the GPU: frame f is lengths[f] bytes at
+// bytes + offsets[f] (host memory).  Each result is the frame's samples interleaved as Frame::decode lays them out
+// (decode.rs:101-107), or empty with the frame's FLACENC_HIP_DECODE_* bits in `status`.
+struct DecodedFrame {
+  uint32_t status = 0;
+  uint64_t number = 0;
+  size_t block_size = 0;
+  std::vector<int32_t> samples;  // interleaved, block_size * channels
+};
+
+inline std::vector<DecodedFrame> decode_frames(HipContext& gpu, const uint8_t* bytes, size_t n_bytes,
+                                               const std::vector<uint64_t>& offsets,
+                                               const std::vector<uint32_t>& lengths, size_t channels,
+                                               size_t bits_per_sample, size_t max_block_size) {
+  const size_t n = offsets.size();
+  if (lengths.size() != n) throw std::invalid_argument("decode_frames: offsets and lengths differ in length");
+  std::vector<int32_t> rows(n * channels * max_block_size);
+  std::vector<uint32_t> block_sizes(n), status(n);
+  std::vector<uint64_t> numbers(n);
+  const int rc = flacenc_hip_decode_frames(gpu.get(), bytes, n_bytes, offsets.data(), lengths.data(), n,
+                                           static_cast<uint32_t>(channels), static_cast<uint32_t>(bits_per_sample),
+                                           static_cast<uint32_t>(max_block_size), rows.data(), max_block_size,
+                                           block_sizes.data(), numbers.data(), status.data(), FLACENC_HIP_MEM_HOST);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  std::vector<DecodedFrame> out(n);
+  for (size_t f = 0; f < n; ++f) {
+    out[f].status = status[f];
+    if (status[f]) continue;
+    out[f].number = numbers[f];
+    out[f].block_size = block_sizes[f];
+    out[f].samples.resize(block_sizes[f] * channels);
+    const int32_t* base = rows.data() + f * channels * max_block_size;
+    for (size_t c = 0; c < channels; ++c)
+      for (size_t t = 0; t < block_sizes[f]; ++t) out[f].samples[t * channels + c] = base[c * max_block_size + t];
+  }
+  return out;
+}
+
 }  // namespace flacenc
 #endif  // FLACENC_HOST_FLACENC_HPP_

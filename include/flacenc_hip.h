@@ -626,6 +626,64 @@ void flacenc_hip_host_free(void* p);
  * threads feeding and draining FrameBufs (src/par.rs:288-325), which only move bytes here. */
 int flacenc_hip_set_host_threads(flacenc_hip_handle* h, int threads);
 
+/* ---- the way back: decode, verify and index frames on the GPU ----------------------------------------------- */
+/*
+ * Frame::decode (src/component/decode.rs:55-110) over the frames the parser reads (src/component/parser.rs: frame
+ * :183, residual :633) -- what `flacenc decode` runs (flacenc-bin/src/main.rs:270-370) -- for a whole launch of frames
+ * at once.  Frame f is lengths[f] bytes at bytes + offsets[f]: the strided pack output (offsets = f * out_stride,
+ * lengths = out_len) and the stream flacenc_hip_stream_offsets_async places both fit.  RFC 9639 frames: both sync codes,
+ * every block-size code (6 and 7 included) and sample-rate code, channel codes 0..10, sample-size code 0 (= the
+ * stream's bits_per_sample), the coded number up to 7 bytes, CRC-8; Constant, Verbatim, Fixed 0..4 and LPC 1..32
+ * (precision 1..15) subframes, wasted bits, both Rice methods and escaped partitions (raw width 0..31); left/side,
+ * right/side and mid/side are undone as in decode.rs:71-98, and reconstruction accumulates in 64 bits and truncates to
+ * i32 (decode.rs:159-177).
+ * The decoder is a deliberate superset of the reference's parser in two places, neither of which affects a frame the
+ * reference writes: it accepts wasted bits (the parser asserts there are none, parser.rs:446-448), and it reads an
+ * escape code as an escaped partition (the parser reads it as a Rice parameter, parser.rs:653-690).
+ *   out          channel-major int32, frame f channel c at out + (f*channels + c)*stride (the encoder's input layout,
+ *                flacenc_hip_fill_le_bytes); stride >= max_block_size; samples beyond the block are zero
+ *   block_sizes  the block size of the frame's header; numbers (NULL to skip): its coded frame or sample number
+ *   status       0, or an OR of FLACENC_HIP_DECODE_*; a frame with a status has zero rows, block size 0, number 0
+ * bits_per_sample must be 4..24 (32-bit FLAC needs a 33-bit side channel) and channels 1..8; a frame whose bit depth is
+ * above 24 or whose block size is above max_block_size is UNSUPPORTED.  For any input bytes the decoder reads nothing
+ * outside [offsets[f], offsets[f] + lengths[f]) and writes nothing outside frame f's rows and slots: garbage gives a
+ * status, never a fault.  flacenc_hip_decode_frames also checks every span against n_bytes (LENGTH when it does not
+ * fit) and takes host or device pointers; the *_async forms take device pointers and enqueue on `stream`.
+ * flacenc_hip_verify_frames_async runs the same parse, compares every sample with `expected` (same layout as `out`)
+ * and writes only `status` (MISMATCH on a frame that decodes to other samples): `flac --verify` for a whole launch.
+ * flacenc_hip_index_frames_async finds the frames of a buffer that holds only frames (a .flac file after its metadata
+ * blocks): every byte position whose header is valid for the stream with a matching CRC-8 is a candidate, each is
+ * parsed for its length and CRC-16, and the frames are exactly those reachable from byte 0 by "the next frame starts
+ * where this one ends" (resolved on the device by pointer jumping), so a header planted inside a frame is never one.
+ * offsets / lengths receive at most max_frames frames in stream order; n_frames[0] = the number written, with
+ * FLACENC_HIP_INDEX_ERROR set when that chain does not end exactly at n_bytes or holds more than max_frames frames.
+ * Scratch (the per-frame skim records, the candidates) comes from the handle.
+ */
+#define FLACENC_HIP_DECODE_BAD_HEADER 1u       /* no sync code, a reserved code or a malformed coded number */
+#define FLACENC_HIP_DECODE_HEADER_CRC 2u
+#define FLACENC_HIP_DECODE_FRAME_CRC 4u
+#define FLACENC_HIP_DECODE_PARSE 8u            /* a subframe or residual field out of range, or the frame ends early */
+#define FLACENC_HIP_DECODE_LENGTH 16u          /* the parsed length differs from lengths[f] */
+#define FLACENC_HIP_DECODE_STREAM_MISMATCH 32u /* channels or bit depth differ from the arguments (parser.rs:197-214) */
+#define FLACENC_HIP_DECODE_UNSUPPORTED 64u     /* bit depth above 24 or block size above max_block_size */
+#define FLACENC_HIP_DECODE_MISMATCH 128u       /* verify: a sample differs from `expected` */
+#define FLACENC_HIP_INDEX_ERROR 0x8000000000000000ull
+int flacenc_hip_decode_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, size_t n_frames, uint32_t channels,
+                                    uint32_t bits_per_sample, uint32_t max_block_size, int32_t* out, size_t stride,
+                                    uint32_t* block_sizes, uint64_t* numbers, uint32_t* status, void* stream);
+int flacenc_hip_decode_frames(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets,
+                              const uint32_t* lengths, size_t n_frames, uint32_t channels, uint32_t bits_per_sample,
+                              uint32_t max_block_size, int32_t* out, size_t stride, uint32_t* block_sizes,
+                              uint64_t* numbers, uint32_t* status, int memory_kind);
+int flacenc_hip_verify_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, const uint64_t* offsets,
+                                    const uint32_t* lengths, size_t n_frames, uint32_t channels,
+                                    uint32_t bits_per_sample, uint32_t max_block_size, const int32_t* expected,
+                                    size_t stride, uint32_t* status, void* stream);
+int flacenc_hip_index_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, uint32_t channels,
+                                   uint32_t bits_per_sample, size_t max_frames, uint64_t* offsets, uint32_t* lengths,
+                                   uint64_t* n_frames, void* stream);
+
 int flacenc_hip_synchronize(flacenc_hip_handle* h);
 
 #ifdef __cplusplus

@@ -328,8 +328,41 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, total_samples: u64, channels: u32, bytes_per_sample: u32, n_frames: usize,
         block_size: u32, frames: *mut i32, stride: usize, stream: *mut c_void,
     ) -> c_int;
+    /// `Frame::decode` (`src/component/decode.rs:55-110`) over the parser's frames (`src/component/parser.rs:183`,
+    /// `:633`) for a launch of frames; `FLACENC_HIP_DECODE_*` bits per frame in `status`.
+    pub fn flacenc_hip_decode_frames_async(
+        h: *mut Handle, bytes: *const u8, offsets: *const u64, lengths: *const u32, n_frames: usize, channels: u32,
+        bits_per_sample: u32, max_block_size: u32, out: *mut i32, stride: usize, block_sizes: *mut u32,
+        numbers: *mut u64, status: *mut u32, stream: *mut c_void,
+    ) -> c_int;
+    pub fn flacenc_hip_decode_frames(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, offsets: *const u64, lengths: *const u32, n_frames: usize,
+        channels: u32, bits_per_sample: u32, max_block_size: u32, out: *mut i32, stride: usize, block_sizes: *mut u32,
+        numbers: *mut u64, status: *mut u32, memory_kind: c_int,
+    ) -> c_int;
+    pub fn flacenc_hip_verify_frames_async(
+        h: *mut Handle, bytes: *const u8, offsets: *const u64, lengths: *const u32, n_frames: usize, channels: u32,
+        bits_per_sample: u32, max_block_size: u32, expected: *const i32, stride: usize, status: *mut u32,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn flacenc_hip_index_frames_async(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, channels: u32, bits_per_sample: u32, max_frames: usize,
+        offsets: *mut u64, lengths: *mut u32, n_frames: *mut u64, stream: *mut c_void,
+    ) -> c_int;
     pub fn flacenc_hip_synchronize(h: *mut Handle) -> c_int;
 }
+
+/// `FLACENC_HIP_DECODE_*`: the status bits of `flacenc_hip_decode_frames` / `_verify_frames_async`.
+pub const DECODE_BAD_HEADER: u32 = 1;
+pub const DECODE_HEADER_CRC: u32 = 2;
+pub const DECODE_FRAME_CRC: u32 = 4;
+pub const DECODE_PARSE: u32 = 8;
+pub const DECODE_LENGTH: u32 = 16;
+pub const DECODE_STREAM_MISMATCH: u32 = 32;
+pub const DECODE_UNSUPPORTED: u32 = 64;
+pub const DECODE_MISMATCH: u32 = 128;
+/// Set in `n_frames` by `flacenc_hip_index_frames_async` when the chain of frames does not end at `n_bytes`.
+pub const INDEX_ERROR: u64 = 1 << 63;
 
 /// One handle per host thread, like the crate's `reusable!` thread-locals (`src/lib.rs:92-116`).
 /// The second field is the summation order every configuration built for this handle asks for.
@@ -357,6 +390,51 @@ impl Gpu {
             OK => Ok(Self(h, order)),
             _ => Err(EncodeError::Config(VerifyError::new("gpu", "no usable HIP device"))),
         }
+    }
+}
+
+/// What `Gpu::decode_frames` gives back for one frame: the interleaved samples as `Frame::decode` lays them out
+/// (`src/component/decode.rs:101-107`), or the frame's `DECODE_*` status bits.
+pub type DecodedFrame = Result<Vec<i32>, u32>;
+
+impl Gpu {
+    /// Decodes `lengths[f]` bytes at `bytes[offsets[f]..]` for every f on the device (`flacenc_hip_decode_frames`, host
+    /// memory) and returns each frame's samples interleaved like `Frame::decode`, or its status bits.
+    pub fn decode_frames(
+        &mut self, bytes: &[u8], offsets: &[u64], lengths: &[u32], channels: usize, bits_per_sample: usize,
+        max_block_size: usize,
+    ) -> Result<Vec<DecodedFrame>, EncodeError> {
+        let n = offsets.len();
+        assert_eq!(lengths.len(), n);
+        let mut out = vec![0i32; n * channels * max_block_size];
+        let mut block_sizes = vec![0u32; n];
+        let mut status = vec![0u32; n];
+        let rc = unsafe {
+            flacenc_hip_decode_frames(
+                self.0, bytes.as_ptr(), bytes.len() as u64, offsets.as_ptr(), lengths.as_ptr(), n, channels as u32,
+                bits_per_sample as u32, max_block_size as u32, out.as_mut_ptr(), max_block_size,
+                block_sizes.as_mut_ptr(), std::ptr::null_mut(), status.as_mut_ptr(), MEM_HOST,
+            )
+        };
+        if rc != OK {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_decode_frames failed")));
+        }
+        Ok((0..n)
+            .map(|f| {
+                if status[f] != 0 {
+                    return Err(status[f]);
+                }
+                let bs = block_sizes[f] as usize;
+                let rows = &out[f * channels * max_block_size..(f + 1) * channels * max_block_size];
+                let mut inter = vec![0i32; bs * channels];
+                for ch in 0..channels {
+                    for t in 0..bs {
+                        inter[t * channels + ch] = rows[ch * max_block_size + t];
+                    }
+                }
+                Ok(inter)
+            })
+            .collect())
     }
 }
 
