@@ -45,6 +45,7 @@ COMM_ID_BYTES = 128  # FLACENC_HIP_COMM_ID_BYTES
 DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 8
 DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
 INDEX_ERROR = 1 << 63
+VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flacenc_hip_encode_variable*
 
 # every symbol include/flacenc_hip.h declares
 ABI_VERSION = 6  # FLACENC_HIP_ABI_VERSION of include/flacenc_hip.h
@@ -98,6 +99,10 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_frames",
     "flacenc_hip_verify_frames_async",
     "flacenc_hip_index_frames_async",
+    "flacenc_hip_variable_bytes_bound",
+    "flacenc_hip_variable_max_frames",
+    "flacenc_hip_encode_variable_async",
+    "flacenc_hip_encode_variable",
     "flacenc_hip_synchronize",
     "flacenc_sigen_fill_frames",
     "flacenc_sigen_fill_frames_strided",
@@ -356,6 +361,16 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_index_frames_async.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp,
                                                  vp]
     L.flacenc_hip_index_frames_async.restype = C.c_int
+    L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
+    L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
+    L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
+    L.flacenc_hip_variable_max_frames.restype = C.c_size_t
+    variable_args = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t,
+                     C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp, vp]
+    L.flacenc_hip_encode_variable_async.argtypes = variable_args + [vp]
+    L.flacenc_hip_encode_variable_async.restype = C.c_int
+    L.flacenc_hip_encode_variable.argtypes = variable_args + [C.c_int]
+    L.flacenc_hip_encode_variable.restype = C.c_int
     L.flacenc_hip_comm_unique_id.argtypes = [vp]
     L.flacenc_hip_comm_unique_id.restype = C.c_int
     L.flacenc_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -449,6 +464,16 @@ def pinned_array(nbytes: int) -> np.ndarray:
     arr = np.frombuffer(buf, dtype=np.uint8)
     arr.flags.writeable = True
     return arr
+
+
+def variable_bytes_bound(channels: int, block_size: int, levels: int, bits_per_sample: int, total_samples: int) -> int:
+    """flacenc_hip_variable_bytes_bound: room for the frames of flacenc_hip_encode_variable (0: arguments rejected)."""
+    return int(load().flacenc_hip_variable_bytes_bound(channels, block_size, levels, bits_per_sample, total_samples))
+
+
+def variable_max_frames(block_size: int, levels: int, total_samples: int) -> int:
+    """flacenc_hip_variable_max_frames: the most frames flacenc_hip_encode_variable can choose (0: rejected)."""
+    return int(load().flacenc_hip_variable_max_frames(block_size, levels, total_samples))
 
 
 class Handle:
@@ -806,6 +831,52 @@ class Handle:
         rc = self._lib.flacenc_hip_index_frames_async(self._h, bytes_ptr or None, n_bytes, channels, bits_per_sample,
                                                       max_frames, offsets_ptr, lengths_ptr, n_frames_ptr,
                                                       stream or None)
+        self._check(rc)
+
+    # -- block-size search: variable-blocking streams ---------------------------------------------------------
+    def encode_variable(self, frames, bits_per_sample: int, cfg: FrameConfig, levels: int, total_samples: int | None = None,
+                        block_size: int | None = None, sample_rate: int = 44100, first_sample_number: int = 0,
+                        out_capacity: int | None = None, max_frames: int | None = None):
+        """flacenc_hip_encode_variable on host arrays.  frames: int32 [superblocks, channels, stride] in FrameBuf layout
+        (zero beyond total_samples); block_size (the superblock S) defaults to the stride, total_samples to all rows.
+        -> dict(data=bytes of the frames back to back, offsets, lengths, block_sizes, split_masks, frames=count,
+        bytes=total, overflow=bool); on overflow data and the per-frame arrays are empty."""
+        x = np.ascontiguousarray(frames, np.int32)
+        n_sb, channels, stride = x.shape
+        block_size = block_size or stride
+        total = n_sb * block_size if total_samples is None else total_samples
+        cap = variable_bytes_bound(channels, block_size, levels, bits_per_sample, total) if out_capacity is None \
+            else out_capacity
+        mf = variable_max_frames(block_size, levels, total) if max_frames is None else max_frames
+        out = np.zeros(max(1, cap), np.uint8)
+        off = np.zeros(max(1, mf), np.uint64)
+        ln = np.zeros(max(1, mf), np.uint32)
+        bs = np.zeros(max(1, mf), np.uint32)
+        masks = np.zeros(max(1, n_sb), np.uint32)
+        tot = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_encode_variable(self._h, C.byref(cfg), x.ctypes.data, total, channels, block_size,
+                                                   levels, stride, bits_per_sample, sample_rate, first_sample_number,
+                                                   out.ctypes.data, cap, off.ctypes.data, ln.ctypes.data, bs.ctypes.data,
+                                                   mf, masks.ctypes.data, tot.ctypes.data, MEM_HOST)
+        self._check(rc)
+        raw = int(tot[0])
+        n = raw & (VARIABLE_OVERFLOW - 1)
+        overflow = bool(raw & VARIABLE_OVERFLOW)
+        k = 0 if overflow else n
+        return dict(data=out[:int(tot[1])].tobytes() if not overflow else b"", offsets=off[:k].copy(),
+                    lengths=ln[:k].copy(), block_sizes=bs[:k].copy(), split_masks=masks[:n_sb].copy(), frames=n,
+                    bytes=int(tot[1]), overflow=overflow)
+
+    def encode_variable_device(self, cfg: FrameConfig, frames_ptr: int, total_samples: int, channels: int,
+                               block_size: int, levels: int, stride: int, bits_per_sample: int, sample_rate: int,
+                               first_sample_number: int, out_ptr: int, out_capacity: int, offsets_ptr: int,
+                               lengths_ptr: int, block_sizes_ptr: int, max_frames: int, split_masks_ptr: int | None,
+                               totals_ptr: int, stream: int | None = None):
+        """flacenc_hip_encode_variable_async: device pointers, enqueued on `stream`."""
+        rc = self._lib.flacenc_hip_encode_variable_async(
+            self._h, C.byref(cfg), frames_ptr, total_samples, channels, block_size, levels, stride, bits_per_sample,
+            sample_rate, first_sample_number, out_ptr or None, out_capacity, offsets_ptr or None, lengths_ptr or None,
+            block_sizes_ptr or None, max_frames, split_masks_ptr or None, totals_ptr, stream or None)
         self._check(rc)
 
     # -- the ordered gather's collective (RCCL communicator owned by the handle) ----------

@@ -18,6 +18,7 @@ constexpr int kThreads = 256;
 __global__ void __launch_bounds__(kThreads) frame_decide_kernel(FrameDecideArgs a) {
   __shared__ int smin[4][kThreads / 64], smax[4][kThreads / 64];
   __shared__ FrameDecision sdec;
+  __shared__ bool s_redo;
   const int tid = threadIdx.x;
   // Every frame (grid = n_frames: one trip), or -- only_marked, a small grid -- the frames the marking kernel listed
   // (FrameDecideArgs::marked_list) or, when the list does not hold them all, a grid-stride walk of all frames.  Everything
@@ -33,7 +34,13 @@ __global__ void __launch_bounds__(kThreads) frame_decide_kernel(FrameDecideArgs 
   for (uint32_t trip = blockIdx.x; trip < count; trip += gridDim.x) {
   const uint32_t f = listed ? a.marked_list[trip] : trip;
   if (f >= a.n_frames) continue;
-  if (a.only_marked && a.results[f].channel_assignment != 0xFF) continue;
+  if (a.only_marked) {  // (one lane reads the record, the workgroup branches on that one value)
+    if (tid == 0) s_redo = a.results[f].channel_assignment == 0xFF;
+    __syncthreads();
+    const bool redo = s_redo;
+    __syncthreads();
+    if (!redo) continue;
+  }
   const int n = (int)a.block_size;
   const int32_t* __restrict__ l = a.frames + (size_t)(2u * f) * a.stride;
   const int32_t* __restrict__ r = l + a.stride;
@@ -123,6 +130,7 @@ __global__ void __launch_bounds__(kThreads) frame_decide_kernel(FrameDecideArgs 
 __global__ void __launch_bounds__(kThreads) channel_decide_kernel(ChannelDecideArgs a) {
   __shared__ int smin[kThreads / 64], smax[kThreads / 64];
   __shared__ uint32_t skind;
+  __shared__ bool s_redo;
   const int tid = threadIdx.x;
   // (the loop of frame_decide_kernel: every subframe, the listed ones, or a grid-stride walk)
   uint32_t count = a.n_subframes;
@@ -136,7 +144,13 @@ __global__ void __launch_bounds__(kThreads) channel_decide_kernel(ChannelDecideA
   for (uint32_t trip = blockIdx.x; trip < count; trip += gridDim.x) {
   const size_t sf = listed ? a.marked_list[trip] : trip;
   if (sf >= a.n_subframes) continue;
-  if (a.only_marked && a.results[sf].kind != 0xFF) continue;
+  if (a.only_marked) {  // (one lane reads the record, the workgroup branches on that one value)
+    if (tid == 0) s_redo = a.results[sf].kind == 0xFF;
+    __syncthreads();
+    const bool redo = s_redo;
+    __syncthreads();
+    if (!redo) continue;
+  }
   const int n = (int)a.block_size;
   const int32_t* __restrict__ x = a.samples + sf * a.stride;
   int mn = INT32_MAX, mx = INT32_MIN;

@@ -91,16 +91,16 @@ struct QlpcKernelArgs {
   uint32_t only_marked;       // generic kernel: redo only subframes whose record says status == -1
   // subframes bigblock_residual_kernel marked for that clean-up launch: qlpc_marked_kernel returns at once on 0.  The
   // handle alternates between two counters from pipeline to pipeline; the clean-up launch clears `marked_next`, the one
-  // the following pipeline counts into (a pipeline without a clean-up launch leaves a stale count behind at worst: a
-  // scan that finds nothing).  nullptr: always scan.
+  // the following pipeline counts into, and attaching the scratch clears the pipeline's own (so a pipeline without a
+  // clean-up launch leaves no stale count or list entries to the one after next).  nullptr: always scan.
   uint32_t* marked_count = nullptr;
   uint32_t* marked_next = nullptr;
   // The first `marked_cap` of those marks, in the order they were counted (slot = what the mark's atomicAdd returned): the
   // clean-up launches visit these records directly instead of reading the status of all n_subframes records -- a scan of
   // 262 144 records for one marked subframe took a 256-sample launch 90 us (round 6).  An entry counts in units of
   // `marked_unit` records: 1, or 4 for stereo frames (whose four roles are marked together: entry = the frame).  Consumers
-  // check an entry against n_subframes and the record's own status, so that entries a pipeline without a clean-up launch
-  // left behind cost a look and nothing else.  nullptr, or more marks than the list holds: the scan.
+  // check an entry against n_subframes and the record's own status, read by one lane and shared through LDS so that the
+  // workgroup branches as one.  nullptr, or more marks than the list holds: the scan.
   uint32_t* marked_list = nullptr;
   uint32_t marked_cap = 0;
   uint32_t marked_unit = 1;

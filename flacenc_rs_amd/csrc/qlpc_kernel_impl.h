@@ -604,11 +604,17 @@ __global__ void __launch_bounds__(MAXP <= 12 ? 1024 : (MAXP <= 16 ? 512 : 256)) 
     if (count == 0u) return;
     if (a.marked_list != nullptr && count <= a.marked_cap) {
       // the marks' own list (QlpcKernelArgs::marked_list): no scan.  Everything here is workgroup-uniform.
+      // The record's status is read by one lane and handed to the workgroup through LDS: every wave takes the same
+      // branch in front of the body's barriers, whatever another workgroup writes to that record meanwhile.
+      __shared__ int listed_status;
       const uint32_t unit = a.marked_unit;
       for (uint32_t i = blockIdx.x; i < count * unit; i += gridDim.x) {
         const uint32_t sf = a.marked_list[i / unit] * unit + i % unit;
         if (sf >= a.n_subframes) continue;
-        const int st = a.params[sf].status;
+        if (threadIdx.x == 0) listed_status = a.params[sf].status;
+        __syncthreads();
+        const int st = listed_status;
+        __syncthreads();  // (read by all before lane 0 writes the next entry's)
         if (st != -1 && st != -2) continue;
         qlpc_subframe_call<MAXP, BIG>(a, sf);
         __syncthreads();

@@ -463,6 +463,14 @@ struct Stream {  // datatype.rs:65
 
 // ----------------------------------------------------------------- the GPU side ----
 // RAII owner of a flacenc_hip_handle (the role of the reference's per-thread scratch)
+// What HipContext::encode_variable gives back: the chosen frames back to back, per frame its offset, length and block
+// size, per superblock its split mask (bit n - 1: heap node n split; include/flacenc_hip.h).
+struct VariableFrames {
+  std::vector<uint8_t> bytes;
+  std::vector<uint64_t> offsets;
+  std::vector<uint32_t> lengths, block_sizes, split_masks;
+};
+
 class HipContext {
  public:
   explicit HipContext(int device_id = 0) {
@@ -505,6 +513,35 @@ class HipContext {
     if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY;
     if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER;
     return 0u;
+  }
+
+  // The block-size search (flacenc_hip_encode_variable, host memory): `frames` in FrameBuf layout, channel c of
+  // superblock i at frames + (i * channels + c) * block_size, zero beyond total_samples.
+  VariableFrames encode_variable(const flacenc_hip_frame_config& cfg, const int32_t* frames, uint64_t total_samples,
+                                 uint32_t channels, uint32_t block_size, uint32_t levels, uint32_t bits_per_sample,
+                                 uint32_t sample_rate, uint64_t first_sample_number = 0) {
+    const size_t cap = flacenc_hip_variable_bytes_bound(channels, block_size, levels, bits_per_sample, total_samples);
+    const size_t max_frames = flacenc_hip_variable_max_frames(block_size, levels, total_samples);
+    if (cap == 0 && total_samples != 0)
+      throw error::EncodeError(error::EncodeError::Device, "encode_variable: channels, block size or levels rejected");
+    VariableFrames v;
+    v.bytes.resize(cap);
+    v.offsets.resize(max_frames);
+    v.lengths.resize(max_frames);
+    v.block_sizes.resize(max_frames);
+    v.split_masks.resize((total_samples + block_size - 1) / block_size);
+    uint64_t totals[2] = {0, 0};
+    const int rc = flacenc_hip_encode_variable(h_, &cfg, frames, total_samples, channels, block_size, levels, block_size,
+                                               bits_per_sample, sample_rate, first_sample_number, v.bytes.data(), cap,
+                                               v.offsets.data(), v.lengths.data(), v.block_sizes.data(), max_frames,
+                                               v.split_masks.data(), totals, FLACENC_HIP_MEM_HOST);
+    if (rc != FLACENC_HIP_OK || (totals[0] & FLACENC_HIP_VARIABLE_OVERFLOW))
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+    v.bytes.resize(totals[1]);
+    v.offsets.resize(totals[0]);
+    v.lengths.resize(totals[0]);
+    v.block_sizes.resize(totals[0]);
+    return v;
   }
 
  private:

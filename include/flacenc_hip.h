@@ -684,6 +684,48 @@ int flacenc_hip_index_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, 
                                    uint32_t bits_per_sample, size_t max_frames, uint64_t* offsets, uint32_t* lengths,
                                    uint64_t* n_frames, void* stream);
 
+/* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
+/*
+ * Each region coded at the block size that compresses it best (BASELINE config 5's "beat-search block sizing"; the
+ * reference snapshot has no such mode, so this is an extension like FLACENC_HIP_FLAG_ALLOW_ORDER_32).  The input is cut
+ * into superblocks of block_size = S samples; a full superblock may be coded as any binary tiling into blocks of S, S/2,
+ * .., S/2^(levels-1).  Nodes are numbered in heap order (node 1 the superblock, children of n are 2n and 2n+1); node n
+ * costs the exact byte length of its block coded as a variable-blocking frame, and bottom-up node n is split exactly when
+ * its children's best sum is strictly smaller (ties keep the larger block).  A last partial superblock of
+ * total_samples % S samples is one frame, never split.
+ * Every chosen frame's bytes between header and CRC-16 are exactly what the fixed-blocking encode+pack call
+ * (flacenc_hip_encode_pack_stereo_frames_async for 2 channels, flacenc_hip_encode_pack_frames_async otherwise) writes for
+ * those samples at that block size under the same config and flags; its header uses variable blocking (sync 0xFFF9, the
+ * coded number = first_sample_number + the block's first sample offset, up to 36 bits), with both CRCs recomputed.
+ *   frames        FrameBuf layout at S: channel c of superblock i at frames + (i*channels + c)*stride, zero beyond
+ *                 total_samples (what flacenc_hip_fill_le_bytes writes)
+ *   levels        1..5; S must be divisible by 2^(levels-1) with S / 2^(levels-1) >= 256 (levels 1: S >= 256)
+ *   out           the chosen frames back to back (out_capacity bytes of room); per output frame its byte offset in out,
+ *                 length and block size (max_frames entries of room); split_masks (NULL to skip): per superblock bit
+ *                 n - 1 set for every split node n of its chosen tiling; totals[0] = frames, totals[1] = bytes
+ * When the frames or bytes exceed max_frames / out_capacity, nothing is written to out or the per-frame arrays, totals[0]
+ * carries FLACENC_HIP_VARIABLE_OVERFLOW and totals hold what a call with enough room needs.  first_sample_number +
+ * total_samples must not exceed 2^36.  flacenc_hip_variable_bytes_bound / _max_frames give room that always suffices
+ * (0 for arguments the encoder rejects).  The async form takes device pointers and enqueues everything on `stream` in the
+ * handle's scratch; flacenc_hip_encode_variable takes host or device pointers and returns when the outputs are there.
+ */
+#define FLACENC_HIP_VARIABLE_OVERFLOW 0x8000000000000000ull
+size_t flacenc_hip_variable_bytes_bound(uint32_t channels, uint32_t block_size, uint32_t levels,
+                                        uint32_t bits_per_sample, uint64_t total_samples);
+size_t flacenc_hip_variable_max_frames(uint32_t block_size, uint32_t levels, uint64_t total_samples);
+int flacenc_hip_encode_variable_async(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
+                                      uint64_t total_samples, uint32_t channels, uint32_t block_size, uint32_t levels,
+                                      size_t stride, uint32_t bits_per_sample, uint32_t sample_rate,
+                                      uint64_t first_sample_number, uint8_t* out, size_t out_capacity,
+                                      uint64_t* frame_offsets, uint32_t* frame_lengths, uint32_t* frame_block_sizes,
+                                      size_t max_frames, uint32_t* split_masks, uint64_t* totals, void* stream);
+int flacenc_hip_encode_variable(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
+                                uint64_t total_samples, uint32_t channels, uint32_t block_size, uint32_t levels,
+                                size_t stride, uint32_t bits_per_sample, uint32_t sample_rate,
+                                uint64_t first_sample_number, uint8_t* out, size_t out_capacity, uint64_t* frame_offsets,
+                                uint32_t* frame_lengths, uint32_t* frame_block_sizes, size_t max_frames,
+                                uint32_t* split_masks, uint64_t* totals, int memory_kind);
+
 int flacenc_hip_synchronize(flacenc_hip_handle* h);
 
 #ifdef __cplusplus

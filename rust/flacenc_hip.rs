@@ -349,7 +349,79 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, channels: u32, bits_per_sample: u32, max_frames: usize,
         offsets: *mut u64, lengths: *mut u32, n_frames: *mut u64, stream: *mut c_void,
     ) -> c_int;
+    /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
+    /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
+    /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.
+    pub fn flacenc_hip_variable_bytes_bound(
+        channels: u32, block_size: u32, levels: u32, bits_per_sample: u32, total_samples: u64,
+    ) -> usize;
+    pub fn flacenc_hip_variable_max_frames(block_size: u32, levels: u32, total_samples: u64) -> usize;
+    pub fn flacenc_hip_encode_variable_async(
+        h: *mut Handle, cfg: *const FrameConfig, frames: *const i32, total_samples: u64, channels: u32, block_size: u32,
+        levels: u32, stride: usize, bits_per_sample: u32, sample_rate: u32, first_sample_number: u64, out: *mut u8,
+        out_capacity: usize, frame_offsets: *mut u64, frame_lengths: *mut u32, frame_block_sizes: *mut u32,
+        max_frames: usize, split_masks: *mut u32, totals: *mut u64, stream: *mut c_void,
+    ) -> c_int;
+    pub fn flacenc_hip_encode_variable(
+        h: *mut Handle, cfg: *const FrameConfig, frames: *const i32, total_samples: u64, channels: u32, block_size: u32,
+        levels: u32, stride: usize, bits_per_sample: u32, sample_rate: u32, first_sample_number: u64, out: *mut u8,
+        out_capacity: usize, frame_offsets: *mut u64, frame_lengths: *mut u32, frame_block_sizes: *mut u32,
+        max_frames: usize, split_masks: *mut u32, totals: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     pub fn flacenc_hip_synchronize(h: *mut Handle) -> c_int;
+}
+
+/// `FLACENC_HIP_VARIABLE_OVERFLOW`: set in `totals[0]` of `flacenc_hip_encode_variable*` when the room was too small.
+pub const VARIABLE_OVERFLOW: u64 = 0x8000000000000000;
+
+/// What `Gpu::encode_variable` gives back: the frames back to back, and per frame its offset, length and block size.
+pub struct VariableStream {
+    pub bytes: Vec<u8>,
+    pub offsets: Vec<u64>,
+    pub lengths: Vec<u32>,
+    pub block_sizes: Vec<u32>,
+}
+
+impl Gpu {
+    /// Encodes `channels`-channel PCM in FrameBuf layout (`frames[(i * channels + c) * block_size + t]`, zero beyond
+    /// `total_samples`) with the block-size search (`flacenc_hip_encode_variable`, host memory).
+    pub fn encode_variable(
+        &mut self, config: &config::Encoder, frames: &[i32], total_samples: u64, channels: usize, levels: u32,
+        bits_per_sample: usize, sample_rate: usize, first_sample_number: u64,
+    ) -> Result<VariableStream, EncodeError> {
+        let block_size = config.block_size as u32;
+        let cap = unsafe {
+            flacenc_hip_variable_bytes_bound(channels as u32, block_size, levels, bits_per_sample as u32, total_samples)
+        };
+        let max_frames = unsafe { flacenc_hip_variable_max_frames(block_size, levels, total_samples) };
+        let superblocks = ((total_samples + block_size as u64 - 1) / block_size as u64) as usize;
+        if cap == 0 || frames.len() < superblocks * channels * block_size as usize {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "encode_variable: arguments rejected")));
+        }
+        let cfg = FrameConfig::from_encoder(config, self.1);
+        let mut bytes = vec![0u8; cap];
+        let mut offsets = vec![0u64; max_frames];
+        let mut lengths = vec![0u32; max_frames];
+        let mut block_sizes = vec![0u32; max_frames];
+        let mut totals = [0u64; 2];
+        let rc = unsafe {
+            flacenc_hip_encode_variable(
+                self.0, &cfg, frames.as_ptr(), total_samples, channels as u32, block_size, levels,
+                block_size as usize, bits_per_sample as u32, sample_rate as u32, first_sample_number,
+                bytes.as_mut_ptr(), cap, offsets.as_mut_ptr(), lengths.as_mut_ptr(), block_sizes.as_mut_ptr(),
+                max_frames, std::ptr::null_mut(), totals.as_mut_ptr(), MEM_HOST,
+            )
+        };
+        if rc != OK || totals[0] & VARIABLE_OVERFLOW != 0 {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_encode_variable failed")));
+        }
+        let n = totals[0] as usize;
+        bytes.truncate(totals[1] as usize);
+        offsets.truncate(n);
+        lengths.truncate(n);
+        block_sizes.truncate(n);
+        Ok(VariableStream { bytes, offsets, lengths, block_sizes })
+    }
 }
 
 /// `FLACENC_HIP_DECODE_*`: the status bits of `flacenc_hip_decode_frames` / `_verify_frames_async`.

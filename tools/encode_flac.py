@@ -7,7 +7,11 @@ What stays on the host is what the reference keeps serial too: the container's 4
 MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-frame) batch: the
 frame-level entry points take any block size.
 
-    python tools/encode_flac.py [in.wav] out.flac [--seconds 10]
+    python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L]
+
+With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
+the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
+(the last frame aside) and 4096 as the block-size range.
 """
 import argparse
 import hashlib
@@ -22,9 +26,10 @@ sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dir
 from flacenc_rs_amd import _capi  # noqa: E402
 
 
-def stream_info_block(block_size, min_frame, max_frame, rate, channels, bps, total, md5):
-    """MetadataBlock(StreamInfo)::write, src/component/bitrepr.rs:199-270 (last-block flag set)."""
-    body = struct.pack(">HH", block_size, block_size)
+def stream_info_block(block_size, min_frame, max_frame, rate, channels, bps, total, md5, min_block=None):
+    """MetadataBlock(StreamInfo)::write, src/component/bitrepr.rs:199-270 (last-block flag set); min_block for a
+    variable-blocking stream (default: block_size, a fixed-blocking one)."""
+    body = struct.pack(">HH", block_size if min_block is None else min_block, block_size)
     body += min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
     packed = (rate << 44) | ((channels - 1) << 41) | ((bps - 1) << 36) | total
     body += packed.to_bytes(8, "big") + md5
@@ -67,6 +72,27 @@ def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_orde
     return head + b"".join(packed), np.concatenate(records)
 
 
+def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8):
+    """pcm int32 [n_samples, channels] -> (.flac bytes, dict of encode_variable's outputs): the block-size search over
+    superblocks of block_size samples, written as a variable-blocking stream."""
+    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order), use_fixed=use_fixed)
+    total, channels = pcm.shape
+    n_sb = (total + block_size - 1) // block_size
+    rows = np.zeros((n_sb * block_size, channels), np.int32)
+    rows[:total] = pcm
+    frames = np.ascontiguousarray(rows.reshape(n_sb, block_size, channels).transpose(0, 2, 1))
+    v = handle.encode_variable(frames, bps, cfg, levels, total_samples=total, sample_rate=rate)
+    inter = np.ascontiguousarray(pcm).reshape(-1)
+    nbytes = (bps + 7) // 8
+    md5 = hashlib.md5(inter.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :nbytes].tobytes()).digest()
+    sizes, blocks = v["lengths"], v["block_sizes"]
+    # RFC 9639 section 8.2: the minimum block size excludes the last block
+    min_block = int(blocks[:-1].min()) if len(blocks) > 1 else int(blocks[0])
+    head = b"fLaC" + stream_info_block(block_size, int(sizes.min()), int(sizes.max()), rate, channels, bps, total, md5,
+                                       min_block=min_block)
+    return head + v["data"], v
+
+
 def encode(frames, bps, rate, handle, use_fixed=True, lpc_order=8):
     """frames int32 [n_frames, 2, n] (whole blocks only) -> (.flac bytes, records)."""
     pcm = np.ascontiguousarray(frames.transpose(0, 2, 1)).reshape(-1, 2)
@@ -77,6 +103,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("paths", nargs="+")
     ap.add_argument("--seconds", type=float, default=10.0)
+    ap.add_argument("--levels", type=int, default=0, help="block-size search over 1..5 levels (variable blocking)")
     args = ap.parse_args()
     n = 4096
     if len(args.paths) == 2:
@@ -92,6 +119,14 @@ def main():
         nf = (nsamp + n - 1) // n
         pcm = np.ascontiguousarray(_capi.sigen_frames(nf, 2, n, bps, rate / 440.0, 0.8, 0.2, seed=1)
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
+    if args.levels:
+        data, v = encode_pcm_variable(pcm, bps, rate, _capi.Handle(0), block_size=n, levels=args.levels)
+        with open(args.paths[-1], "wb") as f:
+            f.write(data)
+        sizes = np.bincount(v["block_sizes"]).nonzero()[0]
+        print(f"{v['frames']} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM "
+              f"size; block sizes {dict((int(b), int((v['block_sizes'] == b).sum())) for b in sizes)}")
+        return
     data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n)
     nf = len(res)
     with open(args.paths[-1], "wb") as f:
