@@ -403,6 +403,14 @@ FLAG_REFERENCE_SUM_ORDER = 32
 FLAG_NIGHTLY_SUM_ORDER = 64
 FLAG_CANONICAL_SUM_ORDER = 128  # the kernels' own order without the order certificate
 FLAG_INTEGER_PARITY_ONLY = 256  # with FLAG_REFERENCE_SUM_ORDER: certified shapes keep their own order (integers only)
+FLAG_WASTED_BITS = 512  # frame-level calls code subframes whose low bits are all zero as x >> k at w - k bits
+
+
+def wasted_bits(results) -> np.ndarray:
+    """Wasted bits k per output channel (FLAG_WASTED_BITS): the `pad` field of the result records, [n, 2] for
+    FRAME_RESULT_DTYPE (output channel c) and [n] for CHANNEL_RESULT_DTYPE (pad[0]); 0 wherever the flag found none."""
+    pad = np.asarray(results)["pad"]
+    return pad.copy() if results.dtype == FRAME_RESULT_DTYPE else pad[..., 0].copy()
 
 
 def make_config(lpc_order=10, quant_precision=15, window=("tukey", 0.4), max_rice_parameter=30,

@@ -29,6 +29,7 @@
 #include "qlpc_kernel.h"
 #include "variable_block.h"
 #include "variable_block_core.h"
+#include "wasted_bits.h"
 
 namespace {
 
@@ -143,6 +144,8 @@ struct flacenc_hip_handle {
   DeviceBuffer d_dec, d_dec_io, d_idx;  // frame decoder: skim records, host-pointer staging, index candidates
   // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
   DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
+  // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
+  DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into
@@ -307,6 +310,20 @@ int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, 
       n_subframes > 0x7FFFFFFFull) {
     h->last_error = "null pointer, stride < block_size, or too many subframes";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  return FLACENC_HIP_OK;
+}
+
+// check_batch_args for the candidate-level batches (flacenc_hip_qlpc_batch, _stereo_qlpc_batch, _fixed_lpc_batch and
+// their async forms): their records have no field for wasted bits, so FLACENC_HIP_FLAG_WASTED_BITS is refused there
+int check_candidate_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
+                               size_t n_subframes, uint32_t block_size, size_t stride,
+                               flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride) {
+  const int rc = check_batch_args(h, cfg, samples, n_subframes, block_size, stride, params, residual, residual_stride);
+  if (rc != FLACENC_HIP_OK) return rc;
+  if (cfg->flags & FLACENC_HIP_FLAG_WASTED_BITS) {
+    h->last_error = "FLACENC_HIP_FLAG_WASTED_BITS is for the frame-level calls only";
+    return FLACENC_HIP_ERR_UNSUPPORTED;
   }
   return FLACENC_HIP_OK;
 }
@@ -816,6 +833,105 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
                                      int32_t* residual, size_t residual_stride, void* stream,
                                      const PackTarget* pack, bool* packed);
 
+// FLACENC_HIP_FLAG_WASTED_BITS for stereo frames (channels == 0) or Independent(channels) frames: scan, one host
+// synchronisation for the count m of frames with wasted bits, the unflagged pipeline unless every frame has some, then
+// the fix-up of the m frames -- their rows x >> k through the candidate batches (per-row width w - k) and a deciding
+// kernel that writes their records and residual rows over the first pass's.  Device pointers, `stream`.
+static int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
+                         size_t n_frames, uint32_t channels, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
+                         flacenc_hip_stereo_frame_result* results, flacenc_hip_channel_result* chan_results,
+                         int32_t* residual, size_t residual_stride, void* stream) {
+  const bool stereo = channels == 0;
+  const size_t rows = stereo ? 4 : channels;
+  int rc = check_batch_args(h, &cfg->qlpc, frames, n_frames * rows, block_size, stride,
+                            stereo ? reinterpret_cast<flacenc_hip_subframe_params*>(results)
+                                   : reinterpret_cast<flacenc_hip_subframe_params*>(chan_results),
+                            residual, residual_stride, 1);
+  if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
+  if (bits_per_sample < 8 || bits_per_sample > 24) {
+    h->last_error = "bits_per_sample must be in 8..=24";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
+  // the unflagged configuration (FUSED_PACK: a kernel choice the fix-up's packer has no part in)
+  flacenc_hip_frame_config plain = *cfg;
+  plain.qlpc.flags &= ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = ensure(h, h->d_wk, n_frames * rows)) != FLACENC_HIP_OK) return rc;
+  if ((rc = ensure(h, h->d_wlist, (n_frames + 1) * 4)) != FLACENC_HIP_OK) return rc;
+  flacenc_hip::WastedArgs w{};
+  w.frames = frames;
+  w.stride = stride;
+  w.block_size = block_size;
+  w.n_frames = static_cast<uint32_t>(n_frames);
+  w.channels = stereo ? 2u : channels;
+  w.stereo = stereo ? 1u : 0u;
+  w.bits_per_sample = bits_per_sample;
+  w.k = static_cast<uint8_t*>(h->d_wk.ptr);
+  w.count = static_cast<uint32_t*>(h->d_wlist.ptr);
+  w.list = w.count + 1;
+  w.use_constant = cfg->use_constant;
+  HIP_TRY(h, hipMemsetAsync(w.count, 0, 4, s));
+  HIP_TRY(h, flacenc_hip::launch_wasted_scan(w, s));
+  uint32_t m = 0;
+  HIP_TRY(h, hipMemcpyAsync(&m, w.count, 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  if (m < n_frames) {  // (m = 0: exactly the unflagged launches)
+    rc = stereo ? encode_stereo_frames_impl(h, &plain, frames, n_frames, block_size, stride, bits_per_sample, results,
+                                            residual, residual_stride, stream, nullptr, nullptr)
+                : flacenc_hip_encode_frames_async(h, &plain, frames, n_frames, channels, block_size, stride,
+                                                  bits_per_sample, chan_results, residual, residual_stride, stream);
+    if (rc != FLACENC_HIP_OK || m == 0) return rc;
+  }
+  // ---- the fix-up of the m marked frames ----
+  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) plain.use_fixed = plain.use_lpc = 0;  // too_short, coding.rs:396
+  const size_t n_rows = static_cast<size_t>(m) * rows;
+  const size_t cstride = (static_cast<size_t>(block_size) + 3) & ~static_cast<size_t>(3);
+  if ((rc = ensure(h, h->d_wrows, n_rows * cstride * 4)) != FLACENC_HIP_OK) return rc;
+  if ((rc = ensure(h, h->d_wbps, n_rows)) != FLACENC_HIP_OK) return rc;
+  w.m = m;
+  w.shifted = static_cast<int32_t*>(h->d_wrows.ptr);
+  w.shifted_stride = cstride;
+  w.shifted_bps = static_cast<uint8_t*>(h->d_wbps.ptr);
+  w.use_fixed = plain.use_fixed;
+  w.use_lpc = plain.use_lpc;
+  w.use_leftside = plain.use_leftside;
+  w.use_rightside = plain.use_rightside;
+  w.use_midside = plain.use_midside;
+  w.cand_stride = cstride;
+  w.results = results;
+  w.chan_results = chan_results;
+  w.residual = residual;
+  w.residual_stride = residual_stride;
+  HIP_TRY(h, flacenc_hip::launch_wasted_shift(w, s));
+  if (plain.use_lpc) {  // estimated_qlpc of the shifted rows: what flacenc_hip_qlpc_batch runs
+    if ((rc = ensure(h, h->d_cparams, n_rows * sizeof(flacenc_hip_subframe_params))) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_cresid, n_rows * cstride * 4)) != FLACENC_HIP_OK) return rc;
+    rc = enqueue(h, &plain.qlpc, w.shifted, n_rows, block_size, cstride, w.shifted_bps,
+                 static_cast<flacenc_hip_subframe_params*>(h->d_cparams.ptr), static_cast<int32_t*>(h->d_cresid.ptr),
+                 cstride, nullptr, nullptr, s);
+    if (rc != FLACENC_HIP_OK) return rc;
+    w.lpc_params = static_cast<const flacenc_hip_subframe_params*>(h->d_cparams.ptr);
+    w.lpc_residual = static_cast<const int32_t*>(h->d_cresid.ptr);
+  }
+  if (plain.use_fixed) {  // fixed_lpc of the shifted rows: what flacenc_hip_fixed_lpc_batch runs
+    if ((rc = ensure(h, h->d_fparams, n_rows * sizeof(flacenc_hip_subframe_params))) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_fresid, n_rows * cstride * 4)) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_fkeys, n_rows * 8)) != FLACENC_HIP_OK) return rc;
+    rc = enqueue_fixed(h, &plain, w.shifted, n_rows, block_size, cstride, w.shifted_bps, bits_per_sample, false,
+                       static_cast<flacenc_hip_subframe_params*>(h->d_fparams.ptr),
+                       static_cast<int32_t*>(h->d_fresid.ptr), cstride,
+                       static_cast<unsigned long long*>(h->d_fkeys.ptr), s);
+    if (rc != FLACENC_HIP_OK) return rc;
+    w.fixed_params = static_cast<const flacenc_hip_subframe_params*>(h->d_fparams.ptr);
+    w.fixed_residual = static_cast<const int32_t*>(h->d_fresid.ptr);
+    w.fixed_keys = static_cast<const unsigned long long*>(h->d_fkeys.ptr);
+  }
+  HIP_TRY(h, flacenc_hip::launch_wasted_decide(w, s));
+  return FLACENC_HIP_OK;
+}
+
 extern "C" {
 
 int flacenc_hip_abi_version(void) { return FLACENC_HIP_ABI_VERSION; }
@@ -858,8 +974,10 @@ void flacenc_hip_destroy(flacenc_hip_handle* h) {
                           &h->d_lpc, &h->d_tables, &h->d_keys, &h->d_sel, &h->d_results, &h->d_out, &h->d_outlen, &h->d_cparams, &h->d_cresid,
                           &h->d_fparams, &h->d_fresid, &h->d_fkeys, &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram,
                           &h->d_dec, &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack,
-                          &h->d_vbs_meta, &h->d_vbs_io})
+                          &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk, &h->d_wlist, &h->d_wrows, &h->d_wbps})
     if (b->ptr) (void)hipFree(b->ptr);
+  if (h->d_cert_fb) (void)hipFree(h->d_cert_fb);  // (the order mode's counters and their pinned mirror)
+  if (h->h_cert_fb) (void)hipHostFree(h->h_cert_fb);
   for (int i = 0; i < 2; ++i) {
     for (DeviceBuffer* b : {&h->d_pcm[i], &h->d_pack[i], &h->d_plen[i], &h->d_poff[i], &h->d_cont[i]})
       if (b->ptr) (void)hipFree(b->ptr);
@@ -958,7 +1076,7 @@ int flacenc_hip_fixed_lpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_f
   const bool stereo = layout == FLACENC_HIP_LAYOUT_STEREO_FRAMES;
   if (!stereo && layout != FLACENC_HIP_LAYOUT_SUBFRAMES) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   const size_t n_sub = stereo ? n_units * 4 : n_units;
-  int rc = check_batch_args(h, &cfg->qlpc, samples, n_sub, block_size, stride, params, residual, residual_stride);
+  int rc = check_candidate_batch_args(h, &cfg->qlpc, samples, n_sub, block_size, stride, params, residual, residual_stride);
   if (rc != FLACENC_HIP_OK || n_units == 0) return rc;
   if (!bps && (bits_per_sample < 8 || bits_per_sample > 25)) {
     h->last_error = "bits_per_sample must be in 8..=25 when no per-subframe bps array is given";
@@ -988,7 +1106,7 @@ int flacenc_hip_fixed_lpc_batch(flacenc_hip_handle* h, const flacenc_hip_frame_c
   if (!stereo && layout != FLACENC_HIP_LAYOUT_SUBFRAMES) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   const size_t n_sub = stereo ? n_units * 4 : n_units;
   const size_t n_rows = stereo ? n_units * 2 : n_units;
-  int rc = check_batch_args(h, &cfg->qlpc, samples, n_sub, block_size, stride, params, residual, residual_stride);
+  int rc = check_candidate_batch_args(h, &cfg->qlpc, samples, n_sub, block_size, stride, params, residual, residual_stride);
   if (rc != FLACENC_HIP_OK || n_units == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t dstride = (static_cast<size_t>(block_size) + 3) & ~static_cast<size_t>(3);
@@ -1252,6 +1370,9 @@ int flacenc_hip_encode_frames_async(flacenc_hip_handle* h, const flacenc_hip_fra
                                     flacenc_hip_channel_result* results, int32_t* residual,
                                     size_t residual_stride, void* stream) {
   if (!h || !cfg || (!results && n_frames) || channels < 1 || channels > 8) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_WASTED_BITS)
+    return encode_wasted(h, cfg, frames, n_frames, channels, block_size, stride, bits_per_sample, nullptr, results,
+                         residual, residual_stride, stream);
   const size_t n_sub = n_frames * channels;
   int rc = check_batch_args(h, &cfg->qlpc, frames, n_sub, block_size, stride,
                             reinterpret_cast<flacenc_hip_subframe_params*>(results), residual, residual_stride, 1);
@@ -2268,8 +2389,8 @@ int flacenc_hip_qlpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_qlpc_c
                                  flacenc_hip_subframe_params* params, int32_t* residual,
                                  size_t residual_stride, double* autocorr, double* lpc_coefs,
                                  void* stream) {
-  int rc = check_batch_args(h, cfg, samples, n_subframes, block_size, stride, params, residual,
-                            residual_stride);
+  int rc = check_candidate_batch_args(h, cfg, samples, n_subframes, block_size, stride, params, residual,
+                                      residual_stride);
   if (rc != FLACENC_HIP_OK || n_subframes == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default (null) stream
@@ -2283,8 +2404,8 @@ int flacenc_hip_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_config*
                            flacenc_hip_subframe_params* params, int32_t* residual,
                            size_t residual_stride, double* autocorr, double* lpc_coefs,
                            int memory_kind) {
-  int rc = check_batch_args(h, cfg, samples, n_subframes, block_size, stride, params, residual,
-                            residual_stride);
+  int rc = check_candidate_batch_args(h, cfg, samples, n_subframes, block_size, stride, params, residual,
+                                      residual_stride);
   if (rc != FLACENC_HIP_OK || n_subframes == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   if (memory_kind == FLACENC_HIP_MEM_DEVICE) {
@@ -2335,8 +2456,8 @@ int flacenc_hip_stereo_qlpc_batch_async(flacenc_hip_handle* h, const flacenc_hip
                                         size_t stride, uint32_t bits_per_sample,
                                         flacenc_hip_subframe_params* params, int32_t* residual,
                                         size_t residual_stride, void* stream) {
-  int rc = check_batch_args(h, cfg, frames, n_frames * 4, block_size, stride, params, residual,
-                            residual_stride);
+  int rc = check_candidate_batch_args(h, cfg, frames, n_frames * 4, block_size, stride, params, residual,
+                                      residual_stride);
   if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
   if (bits_per_sample < 8 || bits_per_sample > 24) {
     h->last_error = "bits_per_sample must be in 8..=24";
@@ -2363,8 +2484,8 @@ int flacenc_hip_stereo_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_
     return FLACENC_HIP_OK;
   }
   if (memory_kind != FLACENC_HIP_MEM_HOST) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  int rc = check_batch_args(h, cfg, frames, n_frames * 4, block_size, stride, params, residual,
-                            residual_stride);
+  int rc = check_candidate_batch_args(h, cfg, frames, n_frames * 4, block_size, stride, params, residual,
+                                      residual_stride);
   if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t dstride = (static_cast<size_t>(block_size) + 3) & ~static_cast<size_t>(3);
@@ -2409,6 +2530,9 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
                                      const PackTarget* pack, bool* packed) {
   if (packed) *packed = false;
   if (!h || !cfg || (!results && n_frames)) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_WASTED_BITS)  // (never the fused bit writer: the caller packs)
+    return encode_wasted(h, cfg, frames, n_frames, 0, block_size, stride, bits_per_sample, results, nullptr, residual,
+                         residual_stride, stream);
   int rc = check_batch_args(h, &cfg->qlpc, frames, n_frames * 4, block_size, stride,
                             reinterpret_cast<flacenc_hip_subframe_params*>(results), residual, residual_stride, 1);
   if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;

@@ -126,7 +126,8 @@ __global__ void __launch_bounds__(kThreads) frame_decide_kernel(FrameDecideArgs 
   }
 }
 
-// encode_subframe (coding.rs:384-418) for one channel of an Independent(n) frame
+// encode_subframe (coding.rs:384-418) for one channel of an Independent(n) frame (restated with a per-channel width and
+// + k bits by wasted_bits.cpp's choose_row / wasted_channel_decide_kernel: a change of the rule here belongs there too)
 __global__ void __launch_bounds__(kThreads) channel_decide_kernel(ChannelDecideArgs a) {
   __shared__ int smin[kThreads / 64], smax[kThreads / 64];
   __shared__ uint32_t skind;

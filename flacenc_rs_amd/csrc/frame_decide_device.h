@@ -28,6 +28,9 @@ struct FrameDecision {
   uint32_t choice[3];  // assignment, role of output channel 0, of channel 1
 };
 
+// (wasted_bits.cpp -- choose_row and wasted_frame_decide_kernel -- restates this choice with a per-role width and + k bits
+// for FLACENC_HIP_FLAG_WASTED_BITS: a change of encode_subframe's or try_stereo_coding's rule here belongs there too;
+// tests/test_gpu_wasted_bits.py holds both against the same oracle model.)
 // Threads 0..3 of the workgroup decide the roles, thread 0 the assignment; `lo` / `hi`: the roles' minima / maxima
 // (thread k < 4 passes those of role k).  Two workgroup barriers inside; writes the result's header fields and copies
 // the two chosen predictor records (all `nthreads` threads take part).

@@ -209,18 +209,23 @@ struct StereoView {  // flacenc_hip_stereo_frame_result: 2 subframes, roles L / 
     return fr->channel_assignment == 0 ? 1u : 7u + fr->channel_assignment;
   }
   __device__ uint32_t kind(int c) const { return fr->kind[c]; }
-  __device__ uint32_t bps(int c) const { return bps0 + (fr->role[c] == 3 ? 1u : 0u); }
+  // wasted bits of output channel c (pad[c]: 0 unless FLACENC_HIP_FLAG_WASTED_BITS found some); the subframe is
+  // coded as x >> k at w - k bits
+  __device__ uint32_t wasted(int c) const { return fr->pad[c]; }
+  __device__ uint32_t bps(int c) const { return bps0 + (fr->role[c] == 3 ? 1u : 0u) - wasted(c); }
   __device__ unsigned long long bits(int c) const { return fr->bits[fr->role[c]]; }
   __device__ int32_t dc(int c) const { return fr->dc_offset[c]; }
   __device__ const flacenc_hip_subframe_params* rec(int c) const { return &fr->lpc[c]; }
   __device__ size_t residual_row(int c) const { return row0 + (size_t)c; }
-  __device__ int32_t sample(int c, int t) const {  // the role's input sample (coding.rs:476-484 for M / S)
+  __device__ int32_t sample(int c, int t) const {  // the role's input sample (coding.rs:476-484 for M / S), >> k
     const uint32_t role = fr->role[c];
     const int32_t lv = l[t];
-    if (role == 0u) return lv;
-    const int32_t rv = r[t];
-    if (role == 1u) return rv;
-    return role == 2u ? ((lv + rv) >> 1) : (lv - rv);
+    int32_t v = lv;
+    if (role != 0u) {
+      const int32_t rv = r[t];
+      v = role == 1u ? rv : (role == 2u ? ((lv + rv) >> 1) : (lv - rv));
+    }
+    return v >> wasted(c);
   }
 };
 struct ChannelView {  // flacenc_hip_channel_result x channels: Independent(n)
@@ -232,12 +237,13 @@ struct ChannelView {  // flacenc_hip_channel_result x channels: Independent(n)
   __device__ uint32_t nsub() const { return nch; }
   __device__ uint32_t channel_tag() const { return nch - 1u; }
   __device__ uint32_t kind(int c) const { return ch[c].kind; }
-  __device__ uint32_t bps(int) const { return bps0; }
+  __device__ uint32_t wasted(int c) const { return ch[c].pad[0]; }  // (see StereoView::wasted)
+  __device__ uint32_t bps(int c) const { return bps0 - wasted(c); }
   __device__ unsigned long long bits(int c) const { return ch[c].bits; }
   __device__ int32_t dc(int c) const { return ch[c].dc_offset; }
   __device__ const flacenc_hip_subframe_params* rec(int c) const { return &ch[c].params; }
   __device__ size_t residual_row(int c) const { return row0 + (size_t)c; }
-  __device__ int32_t sample(int c, int t) const { return x[(size_t)c * stride + t]; }
+  __device__ int32_t sample(int c, int t) const { return x[(size_t)c * stride + t] >> wasted(c); }
 };
 
 // ALIGNED: the block size is a multiple of 4096, so every partition order up to 8 gives partitions that are
@@ -308,12 +314,20 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
     const uint32_t sub_bits = (uint32_t)view.bits(c);
     const uint32_t bps_mask = bps >= 32u ? 0xFFFFFFFFu : ((1u << bps) - 1u);
     auto sample = [&](int t) -> int32_t { return view.sample(c, t); };
+    // Wasted bits (RFC 9639 11.25): the type byte's last bit is the flag, then k - 1 zeros and a one; everything after
+    // the type byte moves k bits on (sub_base: the type byte, sb: where a subframe without wasted bits would start)
+    const uint32_t wasted = view.wasted(c);
+    const uint32_t sb = sub_base + wasted;
+    if (wasted != 0u && tid == 0) {
+      put_bits(words, sub_base + 7u, 1u, 1u);
+      put_bits(words, sb + 7u, 1u, 1u);
+    }
     if (kind == FLACENC_HIP_KIND_CONSTANT) {  // bitrepr.rs:449-454
-      if (tid == 0) put_bits(words, sub_base + 8u, (uint32_t)view.dc(c) & bps_mask, bps);
+      if (tid == 0) put_bits(words, sb + 8u, (uint32_t)view.dc(c) & bps_mask, bps);
     } else if (kind == FLACENC_HIP_KIND_VERBATIM) {  // bitrepr.rs:463-470
       if (tid == 0) put_bits(words, sub_base, 0x02u, 8u);
       for (int t = tid; t < n; t += kPackThreads)
-        put_bits(words, sub_base + 8u + (uint32_t)t * bps, (uint32_t)sample(t) & bps_mask, bps);
+        put_bits(words, sb + 8u + (uint32_t)t * bps, (uint32_t)sample(t) & bps_mask, bps);
     } else {
       const flacenc_hip_subframe_params* rec = view.rec(c);
       const uint32_t order = rec->order;
@@ -321,15 +335,15 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
       // FixedLpc::write bitrepr.rs:479-487 / Lpc::write :501-527 up to the residual
       const uint32_t head_bits = 8u + order * bps + (kind == FLACENC_HIP_KIND_LPC ? 9u + order * precision : 0u);
       if ((uint32_t)tid < order)  // warm-up samples
-        put_bits(words, sub_base + 8u + (uint32_t)tid * bps, (uint32_t)sample(tid) & bps_mask, bps);
+        put_bits(words, sb + 8u + (uint32_t)tid * bps, (uint32_t)sample(tid) & bps_mask, bps);
       if (kind == FLACENC_HIP_KIND_LPC && tid >= 64 && (uint32_t)(tid - 64) < order)  // quantised coefficients
-        put_bits(words, sub_base + 8u + order * bps + 9u + (uint32_t)(tid - 64) * precision,
+        put_bits(words, sb + 8u + order * bps + 9u + (uint32_t)(tid - 64) * precision,
                  (uint32_t)(int32_t)rec->coefs[tid - 64] & ((1u << precision) - 1u), precision);
       if (tid == 128) {
         put_bits(words, sub_base, kind == FLACENC_HIP_KIND_LPC ? (0x40u | ((order - 1u) << 1)) : (0x10u | (order << 1)), 8u);
         if (kind == FLACENC_HIP_KIND_LPC) {
-          put_bits(words, sub_base + 8u + order * bps, precision - 1u, 4u);
-          put_bits(words, sub_base + 8u + order * bps + 4u, (uint32_t)rec->shift & 31u, 5u);
+          put_bits(words, sb + 8u + order * bps, precision - 1u, 4u);
+          put_bits(words, sb + 8u + order * bps + 4u, (uint32_t)rec->shift & 31u, 5u);
         }
       }
       // Residual::write, bitrepr.rs:550-597
@@ -342,7 +356,7 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
         // partition (its length is a multiple of 16) -- one Rice parameter per thread, no per-sample
         // partition walk.  A code of p + 1 <= 31 bits at bit offset <= 31 fits a 64-bit window over two
         // buffer words: one shift and two ORs per sample, no branch.
-        rice_runs16(words, e, n, order, porder, rec->rice_params, sub_base + head_bits, &scan_pairs, &scan_id, tid);
+        rice_runs16(words, e, n, order, porder, rec->rice_params, sb + head_bits, &scan_pairs, &scan_id, tid);
       } else if (!ALIGNED) {
         __syncthreads();  // the previous subframe is done with rice_p
         rice_p[tid] = rec->rice_params[tid];
@@ -351,8 +365,8 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
         for (uint32_t q = tid; q < nparts; q += kPackThreads) rice2 |= rice_p[q] > 14 ? 1u : 0u;
         rice2 = __syncthreads_or((int)rice2) ? 1u : 0u;
         const uint32_t pbits = rice2 ? 5u : 4u;
-        if (tid == 192) put_bits(words, sub_base + head_bits, (rice2 << 4) | porder, 6u);
-        const uint32_t res_base = sub_base + head_bits + 6u;
+        if (tid == 192) put_bits(words, sb + head_bits, (rice2 << 4) | porder, 6u);
+        const uint32_t res_base = sb + head_bits + 6u;
         // contiguous slice of samples per thread; pass 1 counts its bits, pass 2 writes them.
         // Up to 16 samples per thread (blocks <= 4096) are held in registers as zig-zag codes.
         const int per = (n + kPackThreads - 1) / kPackThreads;

@@ -506,8 +506,13 @@ class HipContext {
   // parameters on every shape -- certified on blocks of 4096 / 4608, the stable build's own chains elsewhere -- with the
   // fixed-LPC selector's sums exact integers rather than that build's f32 chains, which only matters above 16 bits).
   enum class SumOrder { Canonical, Stable, SimdNightly };
+  // Wasted bits k of output channel c of a record (FLACENC_HIP_FLAG_WASTED_BITS; 0 without it)
+  static uint32_t wasted_bits(const flacenc_hip_stereo_frame_result& r, int c) { return r.pad[c]; }
+  static uint32_t wasted_bits(const flacenc_hip_channel_result& r) { return r.pad[0]; }
   void set_sum_order(SumOrder o) { sum_order_ = o; }
   SumOrder sum_order() const { return sum_order_; }
+  // (never FLACENC_HIP_FLAG_WASTED_BITS: the SubFrame rebuilt from the records has no wasted-bits field; a caller of
+  // encode_variable may pass it in cfg, and the frames' bytes then carry the wasted bits)
   uint32_t sum_order_flags(size_t lpc_order) const {
     // (the mirror consumes integers only: certified shapes keep their own order, INTEGER_PARITY_ONLY)
     if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY;

@@ -145,6 +145,32 @@ extern "C" {
  * What is given up is only the bit-equality of the optional floating-point outputs (autocorr, lpc_coefs). */
 #define FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY 256u
 
+/* Wasted bits (RFC 9639 section 11.25), an extension like FLACENC_HIP_FLAG_FINEST_RICE_ORDER: the reference never writes
+ * them (its parser asserts the flag is 0, src/component/parser.rs:446-448).  Per subframe signal x of width w (a role L,
+ * R, M, S of a stereo frame -- S at bits_per_sample + 1 -- or a channel of an Independent(n) frame):
+ *   - use_constant and x constant: today's Constant, k = 0;
+ *   - otherwise k = the trailing zero bits of the OR of all samples (0 when that OR is 0); for k > 0 the candidate is
+ *     encode_subframe(x >> k, w - k) -- kind, predictor, residual and Rice partition of the shifted signal at the
+ *     reduced width -- and its bit count that subframe's count_bits + k (the unary count is k - 1 zeros and a one);
+ *     try_stereo_coding compares these counts as it does without the flag.
+ * The result records keep their layout: flacenc_hip_stereo_frame_result::pad[c] is output channel c's k and
+ * flacenc_hip_channel_result::pad[0] the channel's k; bits[] include the + k; the record and the residual row are
+ * those of the shifted signal.  Every writer stores 0 there without the flag, and the packers read pad as k: callers
+ * of flacenc_hip_pack_* that build records themselves must pass 0 in pad unless they mean wasted bits.
+ * Honoured by the frame-level calls (flacenc_hip_encode_[stereo_]frames[_async], flacenc_hip_encode_pack_*_async,
+ * flacenc_hip_encode_pcm[_stereo], flacenc_hip_encode_variable[_async]); the candidate-level batches
+ * (flacenc_hip_qlpc_batch, _stereo_qlpc_batch, _fixed_lpc_batch) answer FLACENC_HIP_ERR_UNSUPPORTED.  FUSED_PACK is
+ * ignored under this flag (a kernel choice, never a result).
+ * A flagged call first scans every frame for wasted bits and then SYNCHRONISES the stream once to read how many frames
+ * have some: the *_async forms block the host for that long, and a flagged call cannot be captured into a graph.  Frames
+ * without wasted bits take exactly the unflagged kernels; frames with some are analysed again, as shifted signals, by
+ * the candidate batches, and a deciding kernel writes their records over the first pass's.
+ * Scratch: for m such frames the handle holds m * rows shifted rows, and as many LPC and (with use_fixed) fixed-LPC
+ * candidate rows, each row ceil4(block_size) int32 (rows = 4 for stereo frames, else channels) -- 3 x 6.4 GB (+ 25 %
+ * growth slack) when all 98 304 stereo frames of 4096 samples are marked; memory that stays with the handle until
+ * flacenc_hip_destroy.  Callers that bound memory bound the frames per call. */
+#define FLACENC_HIP_FLAG_WASTED_BITS 512u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1
@@ -330,7 +356,7 @@ typedef struct flacenc_hip_stereo_frame_result {
   uint8_t analysis_status; /* OR of the FLACENC_HIP_SUBFRAME_* bits of the four LPC analyses (L, R, M, S): non-zero
                               where the reference panics (lpc.rs:646, :786-799); the frame is still valid FLAC --
                               the affected candidate was dropped -- but a drop-in should raise */
-  uint8_t pad[2];
+  uint8_t pad[2];          /* pad[c]: wasted bits k of output channel c (FLACENC_HIP_FLAG_WASTED_BITS; 0 without it) */
   int32_t dc_offset[2];
   uint64_t bits[4];
   flacenc_hip_subframe_params lpc[2];
@@ -442,7 +468,7 @@ int flacenc_hip_pack_stereo_frames_async(flacenc_hip_handle* h, const int32_t* f
 typedef struct flacenc_hip_channel_result {
   uint8_t kind; /* FLACENC_HIP_KIND_* */
   uint8_t analysis_status; /* FLACENC_HIP_SUBFRAME_* bits of this channel's LPC analysis (see above) */
-  uint8_t pad[2];
+  uint8_t pad[2];          /* pad[0]: wasted bits k of the channel (FLACENC_HIP_FLAG_WASTED_BITS; 0 without it); pad[1] 0 */
   int32_t dc_offset;
   uint64_t bits;
   flacenc_hip_subframe_params params;

@@ -47,6 +47,11 @@ pub const FLAG_CANONICAL_SUM_ORDER: u32 = 128;
 /// `FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY`: with `FLAG_REFERENCE_SUM_ORDER`, shapes whose own order is certified to give the
 /// stable build's integers keep it (no second pass over the samples); this binding consumes integers only.
 pub const FLAG_INTEGER_PARITY_ONLY: u32 = 256;
+/// `FLACENC_HIP_FLAG_WASTED_BITS`: the frame-level calls code a subframe whose samples all end in k zero bits as
+/// `x >> k` at `width - k` bits, with k in the record's `pad`.  An extension the reference never writes: nothing in this
+/// binding sets it -- `encode_with_fixed_block_size` must not, because the reference's `SubFrame` it rebuilds has no
+/// wasted-bits field.
+pub const FLAG_WASTED_BITS: u32 = 512;
 
 /// `flacenc_hip_qlpc_config` (include/flacenc_hip.h): the path's fields of `config::Qlpc` /
 /// `config::Prc` (`src/config.rs:271-288`, `211-214`).
@@ -543,6 +548,7 @@ fn abi_config_with(c: &config::SubFrameCoding, order: SumOrder) -> QlpcConfig {
         window_type,
         tukey_alpha,
         max_rice_parameter: c.prc.max_parameter as u32,
+        // (never FLAG_WASTED_BITS: the SubFrame this binding rebuilds from the records has no wasted-bits field)
         flags: if order == SumOrder::Canonical {
             0
         } else if cfg!(feature = "simd-nightly") && c.qlpc.lpc_order <= 15 {

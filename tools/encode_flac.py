@@ -7,11 +7,14 @@ What stays on the host is what the reference keeps serial too: the container's 4
 MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-frame) batch: the
 frame-level entry points take any block size.
 
-    python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L]
+    python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
 (the last frame aside) and 4096 as the block-size range.
+With --wasted-bits (FLACENC_HIP_FLAG_WASTED_BITS) a subframe whose samples all end in k zero bits -- 16-bit content in a
+24-bit WAV, say -- is coded as x >> k at bits_per_sample - k bits; the reference never writes them, every decoder reads
+them.
 """
 import argparse
 import hashlib
@@ -44,10 +47,10 @@ def md5_of(frames, bps):
     return hashlib.md5(raw.tobytes()).digest()
 
 
-def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_order=8):
+def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_order=8, flags=0):
     """pcm int32 [n_samples, 2] -> (.flac bytes, per-frame decision records).  Like
     encode_with_fixed_block_size (src/coding.rs:645-700): whole blocks, then the shorter last one."""
-    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order), use_fixed=use_fixed)
+    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=use_fixed)
     n_full = pcm.shape[0] // block_size
     groups = []
     if n_full:
@@ -72,10 +75,10 @@ def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_orde
     return head + b"".join(packed), np.concatenate(records)
 
 
-def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8):
+def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8, flags=0):
     """pcm int32 [n_samples, channels] -> (.flac bytes, dict of encode_variable's outputs): the block-size search over
     superblocks of block_size samples, written as a variable-blocking stream."""
-    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order), use_fixed=use_fixed)
+    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=use_fixed)
     total, channels = pcm.shape
     n_sb = (total + block_size - 1) // block_size
     rows = np.zeros((n_sb * block_size, channels), np.int32)
@@ -104,7 +107,10 @@ def main():
     ap.add_argument("paths", nargs="+")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--levels", type=int, default=0, help="block-size search over 1..5 levels (variable blocking)")
+    ap.add_argument("--wasted-bits", action="store_true",
+                    help="code subframes whose low bits are all zero at reduced width (FLACENC_HIP_FLAG_WASTED_BITS)")
     args = ap.parse_args()
+    flags = _capi.FLAG_WASTED_BITS if args.wasted_bits else 0
     n = 4096
     if len(args.paths) == 2:
         with wave.open(args.paths[0], "rb") as w:
@@ -120,20 +126,22 @@ def main():
         pcm = np.ascontiguousarray(_capi.sigen_frames(nf, 2, n, bps, rate / 440.0, 0.8, 0.2, seed=1)
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
     if args.levels:
-        data, v = encode_pcm_variable(pcm, bps, rate, _capi.Handle(0), block_size=n, levels=args.levels)
+        data, v = encode_pcm_variable(pcm, bps, rate, _capi.Handle(0), block_size=n, levels=args.levels,
+                                      flags=flags)
         with open(args.paths[-1], "wb") as f:
             f.write(data)
         sizes = np.bincount(v["block_sizes"]).nonzero()[0]
         print(f"{v['frames']} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM "
               f"size; block sizes {dict((int(b), int((v['block_sizes'] == b).sum())) for b in sizes)}")
         return
-    data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n)
+    data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n, flags=flags)
     nf = len(res)
     with open(args.paths[-1], "wb") as f:
         f.write(data)
     kinds = np.bincount(res["kind"].ravel(), minlength=4)
+    wasted = int((res["pad"] != 0).sum())
     print(f"{nf} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM size; "
-          f"subframes constant/verbatim/fixed/lpc = {kinds.tolist()}")
+          f"subframes constant/verbatim/fixed/lpc = {kinds.tolist()}, with wasted bits {wasted}")
 
 
 if __name__ == "__main__":
