@@ -404,6 +404,7 @@ FLAG_NIGHTLY_SUM_ORDER = 64
 FLAG_CANONICAL_SUM_ORDER = 128  # the kernels' own order without the order certificate
 FLAG_INTEGER_PARITY_ONLY = 256  # with FLAG_REFERENCE_SUM_ORDER: certified shapes keep their own order (integers only)
 FLAG_WASTED_BITS = 512  # frame-level calls code subframes whose low bits are all zero as x >> k at w - k bits
+FLAG_ORDER_SEARCH = 1024  # every LPC candidate's order chosen by an exhaustive search over 1..lpc_order
 
 
 def wasted_bits(results) -> np.ndarray:

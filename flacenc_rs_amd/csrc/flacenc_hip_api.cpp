@@ -26,6 +26,7 @@
 #include "flacenc_hip_debug.h"
 #include "frame_decide.h"
 #include "frame_pack.h"
+#include "order_search.h"
 #include "qlpc_kernel.h"
 #include "variable_block.h"
 #include "variable_block_core.h"
@@ -146,6 +147,8 @@ struct flacenc_hip_handle {
   DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
   // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
   DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
+  // order search: every candidate order's predictor record and the chosen order (order_search.h)
+  DeviceBuffer d_order;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into
@@ -569,14 +572,26 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
   // (R[] and the predictor records between the launches of the split pipelines: orders from 13, and blocks of
   // 8192 / 16384 at any order -- the big-block kernels)
   // (... and, round 6, every unflagged launch: the reference's chains go in front of whatever kernel takes the shape)
+  const bool order_search = (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) != 0;
   if (cfg->lpc_order >= 13 || a.reference_order || a.direct_mse || block_size == 8192 || block_size == 16384 ||
-      flacenc_hip::subwave_shape(block_size) || a.certify != 0u) {
+      flacenc_hip::subwave_shape(block_size) || a.certify != 0u || order_search) {
     if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
   }
   if (plan.table_scratch_bytes_per_subframe) {
     rc = ensure(h, h->d_tables, plan.table_scratch_bytes_per_subframe * n_subframes);
     if (rc != FLACENC_HIP_OK) return rc;
     a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
+  }
+  if (order_search) {
+    // FLACENC_HIP_FLAG_ORDER_SEARCH: R[] in the stable build's order (nightly's with its flag; the
+    // certificate and INTEGER_PARITY_ONLY do not apply), every order 1..P searched, the records written by stage 3
+    a.certify = 0;
+    a.integer_parity_only = 0;
+    a.cert_stats = nullptr;
+    rc = ensure(h, h->d_order, flacenc_hip::order_search_scratch_bytes(a.n_subframes, cfg->lpc_order));
+    if (rc != FLACENC_HIP_OK) return rc;
+    HIP_TRY(h, flacenc_hip::launch_order_search(a, plan, a.reference_order == 2u ? 1u : 0u, h->d_order.ptr, stream));
+    return FLACENC_HIP_OK;
   }
   // frame-level callers on the big-block shapes: L / R candidates straight into the output rows, role min / max
   // from the residual kernel (only bigblock_residual_kernel knows how; see QlpcKernelArgs::residual_lr)
@@ -974,7 +989,7 @@ void flacenc_hip_destroy(flacenc_hip_handle* h) {
                           &h->d_lpc, &h->d_tables, &h->d_keys, &h->d_sel, &h->d_results, &h->d_out, &h->d_outlen, &h->d_cparams, &h->d_cresid,
                           &h->d_fparams, &h->d_fresid, &h->d_fkeys, &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram,
                           &h->d_dec, &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack,
-                          &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk, &h->d_wlist, &h->d_wrows, &h->d_wbps})
+                          &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk, &h->d_wlist, &h->d_wrows, &h->d_wbps, &h->d_order})
     if (b->ptr) (void)hipFree(b->ptr);
   if (h->d_cert_fb) (void)hipFree(h->d_cert_fb);  // (the order mode's counters and their pinned mirror)
   if (h->h_cert_fb) (void)hipHostFree(h->h_cert_fb);
@@ -1021,6 +1036,8 @@ int flacenc_hip_verify_config(const flacenc_hip_qlpc_config* cfg) {
   if ((cfg->flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER) && (cfg->flags & FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER))
     return FLACENC_HIP_ERR_BAD_CONFIG;
   if ((cfg->flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER) && cfg->lpc_order > 15) return FLACENC_HIP_ERR_UNSUPPORTED;
+  // the order search runs on the autocorrelation's R[]; the covariance-method estimator has none
+  if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
   return FLACENC_HIP_OK;
 }
 
@@ -1391,7 +1408,8 @@ int flacenc_hip_encode_frames_async(flacenc_hip_handle* h, const flacenc_hip_fra
   }
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  {
+  // FLACENC_HIP_FLAG_ORDER_SEARCH: the candidate batches + channel_decide_kernel for every shape
+  if (!((cfg->qlpc.flags & FLACENC_HIP_FLAG_ORDER_SEARCH) && cfg->use_lpc)) {
     // block size 4096, order <= 12: one fused kernel, a wave per channel (analysis, fixed-LPC
     // candidate, encode_subframe's choice, only the chosen residual written)
     uint32_t glog = 0;
@@ -2633,7 +2651,9 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
   bool want_fused = false;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_FUSED_PACK) want_fused = true;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_TWO_STAGE_PACK) want_fused = false;
-  if (pack && want_fused && !fixed_composite && block_size == 4096 && flacenc_hip::wave_kernel_eligible(a)) {
+  // FLACENC_HIP_FLAG_ORDER_SEARCH: the candidate batches + frame_decide_kernel for every shape (FUSED_PACK ignored)
+  const bool order_search = (cfg->qlpc.flags & FLACENC_HIP_FLAG_ORDER_SEARCH) != 0 && cfg->use_lpc;
+  if (pack && want_fused && !fixed_composite && !order_search && block_size == 4096 && flacenc_hip::wave_kernel_eligible(a)) {
     const size_t bound = flacenc_hip_stereo_frame_bytes_bound(block_size, bits_per_sample);
     flacenc_hip::FramePackArgs pa{};
     fill_header_specs(pa, block_size, pack->sample_rate, bits_per_sample);
@@ -2657,7 +2677,7 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
     int rc2 = attach_split_scratch(h, a, stream);
     if (rc2 != FLACENC_HIP_OK) return rc2;
   }
-  if (!flacenc_hip::wave_kernel_eligible(a) || fixed_composite) {
+  if (!flacenc_hip::wave_kernel_eligible(a) || fixed_composite || order_search) {
     // General shapes: the same result from candidate batches (4 QLPC + 4 fixed-LPC candidates per
     // frame in handle scratch) and the stand-alone controller kernel (frame_decide.cpp).
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2691,7 +2711,7 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
     const bool fixed_big = !cfg->use_fixed ||
                            (cfg->fixed_order_sel == FLACENC_HIP_ORDERSEL_APPROXENT && fparts != 0 && (fparts & (fparts - 1)) == 0 &&
                             block_size / fparts >= 64 && block_size / fparts <= 4096 && cfg->fixed_max_order <= 4);
-    if (big_shape && fixed_big) {
+    if (big_shape && fixed_big && !order_search) {
       if ((rc = ensure(h, h->d_cparams, n_sub * sizeof(flacenc_hip_subframe_params))) != FLACENC_HIP_OK) return rc;
       if ((rc = ensure(h, h->d_cresid, n_sub * cstride * 4)) != FLACENC_HIP_OK) return rc;
       if ((rc = ensure(h, h->d_minmax, n_sub * 2 * sizeof(int32_t))) != FLACENC_HIP_OK) return rc;
@@ -2735,7 +2755,7 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
     // whole of encode_frame -- both candidates of the four roles, the decision, the two chosen rows -- several frames
     // per workgroup.  A frame with a candidate beyond its exact sums (residuals of 2^25 and more) comes back marked
     // and takes the general path below, whose three kernels return at once when the count of marked frames is 0.
-    if (block_size >= FLACENC_HIP_MIN_BLOCK_SIZE && flacenc_hip::subwave_shape(block_size)) {
+    if (block_size >= FLACENC_HIP_MIN_BLOCK_SIZE && flacenc_hip::subwave_shape(block_size) && !order_search) {
       flacenc_hip::QlpcKernelArgs m = a;
       m.stamps = nullptr;
       m.fixed_partitions = cfg->fixed_partitions;

@@ -1,0 +1,496 @@
+// order_search.cpp -- FLACENC_HIP_FLAG_ORDER_SEARCH: per QLPC candidate subframe, the LPC order
+// 1..P whose exact Lpc::count_bits is smallest.  Every candidate comes from the one R[0..P] the reference-order pass
+// produces: levinson_quantize at order o reads lags 0..o only, so candidate o is bit for bit the order-o run, and
+// candidate P is the unflagged FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER record.
+#include "order_search.h"
+
+#include "acorr_reference.h"
+#include "lds_opt_in.h"
+#include "qlpc_kernel_impl.h"
+
+namespace flacenc_hip {
+namespace {
+
+constexpr int kOsThreads = 256;
+constexpr int kTabStride = 31;                    // Rice parameters 0..30 per partition row
+constexpr uint32_t kMaxBits = (1u << 27) - 1u;    // MAX_P_TO_BITS, rice.rs:51
+constexpr uint32_t kWideU = 1u << 27;             // zig-zag codes from here on can wrap a 16-sample chunk's u32 sum
+constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, 0 (levinson_batch_kernel's record)
+constexpr size_t kSmallBytes = 1024 + 16 * 8 + 2 * 8 + 16 * 4 + 256 + 256;  // psum, level bits, sums, misc, two ps rows
+
+enum { kMaxAbs = 0, kUMax, kSat, kLo, kHi, kRice2 };
+
+struct OrderSearchArgs {
+  const int32_t* samples;
+  size_t stride;
+  uint32_t block_size;
+  uint32_t n_subframes;
+  uint32_t stereo;
+  const uint8_t* bps;
+  uint32_t bps_uniform;
+  uint32_t lpc_order;
+  uint32_t precision;
+  uint32_t max_rice_parameter;
+  uint32_t rice_finest_only;
+  const int32_t* cand;  // [n][P][36]
+  uint32_t* best;       // [n]: chosen order, 0 = no candidate with status 0
+  int32_t* residual;    // zig-zag rows of the order under test when they do not fit the LDS (the output rows; stage 3
+  size_t residual_stride;  // overwrites them)
+};
+
+__host__ __device__ inline int finest_order(int n) {  // finest_partition_order(n, 64), rice.rs:157-165 (warm-up <= 32)
+  const unsigned max_splits = (unsigned)n / 64u;
+  int lg = 0;
+  while ((2u << lg) <= max_splits) ++lg;
+  int tz = 0;
+  while (((n >> tz) & 1) == 0 && tz < 15) ++tz;
+  const int fo = lg < tz ? lg : tz;
+  return fo < 8 ? fo : 8;
+}
+
+__host__ __device__ inline size_t round16(size_t x) { return (x + 15) & ~static_cast<size_t>(15); }
+
+size_t search_lds_bytes(uint32_t n, bool lds_u) {
+  const size_t parts = static_cast<size_t>(1) << finest_order(static_cast<int>(n));
+  return round16(4 * static_cast<size_t>(n)) * (lds_u ? 2 : 1) + round16(parts * kTabStride * 4) + kSmallBytes;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// candidate o of subframe sf at [(sf * P + o - 1) * 36]: levinson_quantize on R[0..o] (lpc.rs:633-705, 273-302)
+template <int MAXP>
+__global__ void __launch_bounds__(64) order_levinson_kernel(const double* __restrict__ racc, uint32_t n_subframes,
+                                                             uint32_t P, uint32_t precision, int32_t* __restrict__ cand) {
+  const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
+  if (i >= (size_t)n_subframes * P) return;
+  const size_t sf = i / P;
+  const int o = (int)(i % P) + 1;
+  double coef[MAXP];
+  int32_t qc[MAXP];
+  int order, shift;
+  const int status = levinson_quantize<MAXP>(racc + sf * 33, o, (int)precision, coef, qc, &order, &shift);
+  int32_t* pr = cand + i * kCandWords;
+#pragma unroll
+  for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
+  for (int k = MAXP; k < 32; ++k) pr[k] = 0;
+  pr[32] = order;
+  pr[33] = shift;
+  pr[34] = status;
+  pr[35] = 0;
+}
+
+// the chosen order's predictor record for the stage-3 kernels, and its unquantised coefficients (zeros from o on)
+template <int MAXP>
+__global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict__ racc, uint32_t n_subframes, uint32_t P,
+                                                         uint32_t precision, const uint32_t* __restrict__ best,
+                                                         int32_t* __restrict__ pred, double* __restrict__ lpc_coefs) {
+  const size_t sf = (size_t)blockIdx.x * 64u + threadIdx.x;
+  if (sf >= n_subframes) return;
+  int o = (int)best[sf];
+  if (o < 1 || o > (int)P) o = (int)P;  // no candidate with status 0: the order-P record, status included
+  double coef[MAXP];
+  int32_t qc[MAXP];
+  int order, shift;
+  const int status = levinson_quantize<MAXP>(racc + sf * 33, o, (int)precision, coef, qc, &order, &shift);
+  int32_t* pr = pred + sf * kCandWords;
+#pragma unroll
+  for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
+  for (int k = MAXP; k < 32; ++k) pr[k] = 0;
+  pr[32] = order;
+  pr[33] = shift;
+  pr[34] = status;
+  pr[35] = 0;
+  if (lpc_coefs) {
+#pragma unroll
+    for (int k = 0; k < MAXP; ++k) lpc_coefs[sf * 32 + k] = (k < o && status == 0) ? coef[k] : 0.0;
+    for (int k = MAXP; k < 32; ++k) lpc_coefs[sf * 32 + k] = 0.0;
+  }
+}
+
+// One workgroup per subframe: the samples staged in LDS once, then for every candidate order with status 0 the residual
+// (compute_error, lpc.rs:359-390), the finest partitions' Rice bit tables over a parameter window and the reference's
+// merge / minimiser walk (PrcParameterFinder::find, rice.rs:246-298) -> the exact Lpc::count_bits (bitrepr.rs:492-499,
+// 533-544) as the candidate's key.  LDS_U: the zig-zag residual row of the order under test lives in LDS (blocks up to
+// 8192 samples), otherwise in the subframe's output row.
+//
+// The window: a table entry f(p) = sum(u >> p) + len (p + 1) + 4 has f(p + 1) - f(p) = len - sum(ceil((u >> p) / 2)), which
+// does not decrease with p, and is > 0 once len 2^p > sum(u), < 0 while 3 len 2^p <= sum(u).  So every partition's minimisers
+// lie in [lo_i, hi_i] (the smallest p with 3 len 2^p > S_i, resp. len 2^p > S_i, both capped at max_p), a merged table is
+// a sum of such functions, and its minimisers lie inside [min lo_i, max hi_i]: outside it every table is strictly
+// monotone.  Entries that saturate at MAX_P_TO_BITS are far above any minimum (a partition's at hi_i stays below
+// 32 len).  The argument needs every entry to be min(MAX, exact sum): zig-zag codes below 2^27 (no 16-sample chunk can
+// wrap the u32 accumulator) and every S_i below 2^32 here; otherwise the window is all of 0..max_p.  The entries
+// themselves are always computed as the reference does -- u32 adds, the clamp after each 16-sample chunk.
+template <bool LDS_U>
+__global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const uint32_t sf = blockIdx.x;
+  const int n = (int)a.block_size;
+  const int P = (int)a.lpc_order;
+  const int fo = finest_order(n);
+  const int nparts = 1 << fo;
+  const int psize = n >> fo;
+  const uint32_t maxp = a.max_rice_parameter;
+
+  unsigned char* p = smem;
+  int32_t* sbuf = reinterpret_cast<int32_t*>(p);
+  p += round16(4 * (size_t)n);
+  uint32_t* ubuf;
+  if (LDS_U) {
+    ubuf = reinterpret_cast<uint32_t*>(p);
+    p += round16(4 * (size_t)n);
+  } else {
+    ubuf = reinterpret_cast<uint32_t*>(a.residual + (size_t)sf * a.residual_stride);
+  }
+  uint32_t* tab = reinterpret_cast<uint32_t*>(p);
+  p += round16((size_t)nparts * kTabStride * 4);
+  uint32_t* psum = reinterpret_cast<uint32_t*>(p);
+  p += 1024;
+  unsigned long long* lvl_bits = reinterpret_cast<unsigned long long*>(p);
+  p += 16 * 8;
+  unsigned long long* acc64 = reinterpret_cast<unsigned long long*>(p);
+  p += 2 * 8;
+  uint32_t* misc = reinterpret_cast<uint32_t*>(p);
+  p += 16 * 4;
+  uint8_t* pl = p;
+  p += 256;
+  uint8_t* psel = p;
+
+  // ---- load (stereo: roles L, R, M = (l + r) >> 1, S = l - r of frame sf / 4, coding.rs:476-484) ----
+  const int role = a.stereo ? (int)(sf & 3u) : 0;
+  const int32_t* src = a.stereo ? a.samples + (size_t)(2u * (sf >> 2) + (role == 1 ? 1u : 0u)) * a.stride
+                                : a.samples + (size_t)sf * a.stride;
+  const int32_t* src2 = src + a.stride;
+  if (tid < 16) misc[tid] = 0u;
+  __syncthreads();
+  uint32_t my_max = 0;
+  for (int t = tid; t < n; t += kOsThreads) {
+    int32_t v = src[t];
+    if (role == 2) v = (v + src2[t]) >> 1;
+    else if (role == 3) v -= src2[t];
+    sbuf[t] = v;
+    const uint32_t av = (uint32_t)(v < 0 ? -(int64_t)v : (int64_t)v);
+    my_max = my_max > av ? my_max : av;
+  }
+  my_max = wave_max_u32(my_max);
+  if (lane == 0) atomicMax(&misc[kMaxAbs], my_max);
+  __syncthreads();
+  const uint64_t maxabs = misc[kMaxAbs];
+  const unsigned long long bps = a.bps ? (unsigned long long)a.bps[sf]
+                                       : (unsigned long long)(a.bps_uniform + (role == 3 ? 1u : 0u));
+
+  unsigned long long best_key = ~0ull;
+  uint32_t best_o = 0;
+  for (int o = 1; o <= P; ++o) {
+    const int32_t* pr = a.cand + ((size_t)sf * (size_t)P + (size_t)(o - 1)) * kCandWords;
+    if (pr[34] != 0) continue;  // (uniform: every thread reads the same record)
+    const int q = pr[32];
+    const int shift = pr[33];
+    int32_t c[32];
+    int64_t sumabs = 0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      c[j] = pr[j];
+      sumabs += c[j] < 0 ? -(int64_t)c[j] : (int64_t)c[j];
+    }
+    // compute_error's i32 criterion (lpc.rs:361-377), and 24-bit operands for v_mad_i32_i24
+    const bool narrow = maxabs * (uint64_t)sumabs < 0x7FFFFFFFull && maxabs < (1u << 23);
+
+    __syncthreads();  // (the previous candidate's readers are done)
+    if (tid < nparts) psum[tid] = 0u;
+    if (tid < 16) lvl_bits[tid] = 0ull;
+    if (tid < 2) acc64[tid] = 0ull;
+    if (tid == 0) {
+      misc[kUMax] = 0u;
+      misc[kSat] = 0u;
+      misc[kLo] = 31u;
+      misc[kHi] = 0u;
+      misc[kRice2] = 0u;
+    }
+    __syncthreads();
+
+    // ---- residual, zig-zag codes, per-partition sums of u ----
+    uint32_t my_umax = 0;
+    for (int base = 0; base < n; base += kOsThreads) {
+      const int t = base + tid;
+      uint32_t u = 0;
+      if (t < n && t >= q) {
+        const int32_t* h = sbuf + (t - 1);
+        int32_t e;
+        if (narrow) {
+          int32_t acc = 0;
+#pragma unroll
+          for (int j = 0; j < 32; ++j)
+            if (j < q) acc += __mul24(c[j], h[-j]);
+          e = (int32_t)((uint32_t)sbuf[t] - (uint32_t)(acc >> shift));
+        } else {
+          int64_t acc = 0;
+#pragma unroll
+          for (int j = 0; j < 32; ++j)
+            if (j < q) acc += (int64_t)c[j] * (int64_t)h[-j];
+          e = (int32_t)(uint32_t)(uint64_t)((int64_t)sbuf[t] - (acc >> shift));
+        }
+        u = zigzag(e);
+      }
+      if (t < n) ubuf[t] = u;
+      my_umax = my_umax > u ? my_umax : u;
+      // a wave's 64 samples lie in at most two partitions (psize >= 64)
+      const int w0 = base + 64 * wave;
+      if (w0 < n) {
+        const int pa = w0 / psize;
+        const int mine = t < n ? t / psize : pa;
+        const unsigned long long sa = wave_sum_u64(mine == pa ? (unsigned long long)u : 0ull);
+        const int wl = (w0 + 63 < n ? w0 + 63 : n - 1) / psize;
+        unsigned long long sb = 0;
+        if (wl != pa) sb = wave_sum_u64(mine != pa ? (unsigned long long)u : 0ull);
+        if (lane == 0) {
+          if (sa >= (1ull << 32)) {
+            misc[kSat] = 1u;
+          } else if (sa) {
+            const uint32_t old = atomicAdd(&psum[pa], (uint32_t)sa);
+            if ((uint32_t)(old + (uint32_t)sa) < old) misc[kSat] = 1u;
+          }
+          if (wl != pa) {
+            if (sb >= (1ull << 32)) {
+              misc[kSat] = 1u;
+            } else if (sb) {
+              const uint32_t old = atomicAdd(&psum[wl], (uint32_t)sb);
+              if ((uint32_t)(old + (uint32_t)sb) < old) misc[kSat] = 1u;
+            }
+          }
+        }
+      }
+    }
+    my_umax = wave_max_u32(my_umax);
+    if (lane == 0) atomicMax(&misc[kUMax], my_umax);
+    __syncthreads();
+
+    // ---- the parameter window ----
+    if (tid < nparts) {
+      const unsigned long long len = (unsigned long long)(psize - (tid == 0 ? q : 0));
+      const unsigned long long S = psum[tid];
+      uint32_t lo = 0, hi = 0;
+      while (lo < maxp && ((3ull * len) << lo) <= S) ++lo;
+      while (hi < maxp && (len << hi) <= S) ++hi;
+      atomicMin(&misc[kLo], lo);
+      atomicMax(&misc[kHi], hi);
+    }
+    __syncthreads();
+    const bool wide = misc[kUMax] >= kWideU;
+    int lo = (int)misc[kLo], hi = (int)misc[kHi];
+    if (wide || misc[kSat] != 0u) {
+      lo = 0;
+      hi = (int)maxp;
+    }
+    const int W = hi - lo + 1;
+
+    // ---- finest partitions' bit tables (PrcBitTable::from_errors, rice.rs:65-103), one lane per (partition, p) ----
+    for (int item = tid; item < nparts * W; item += kOsThreads) {
+      const int i = item / W;
+      const int pp = lo + item % W;
+      const int start = i * psize > q ? i * psize : q;
+      const int end = (i + 1) * psize;
+      uint32_t acc = 0;
+      for (int c0 = start; c0 < end; c0 += 16) {
+        const int ce = c0 + 16 < end ? c0 + 16 : end;
+        for (int t = c0; t < ce; ++t) acc += ubuf[t] >> pp;
+        acc = acc > kMaxBits ? kMaxBits : acc;
+      }
+      const uint32_t v = acc + 4u + (uint32_t)(end - start) * (uint32_t)(pp + 1);
+      tab[i * kTabStride + pp] = v > kMaxBits ? kMaxBits : v;
+    }
+    __syncthreads();
+
+    // ---- the partition orders, finest first; strict < keeps the finer order (rice.rs:285) ----
+    unsigned long long best_bits = ~0ull;
+    int best_lvl = 0;
+    bool best_r2 = false;
+    const int levels = a.rice_finest_only ? 1 : fo + 1;
+    for (int k = 0; k < levels; ++k) {
+      const int np = nparts >> k;
+      if (k > 0) {
+        // PrcBitTable::merge (rice.rs:144-152); level k's partition i lives in row i << k
+        for (int item = tid; item < np * W; item += kOsThreads) {
+          const int i = item / W;
+          const int pp = lo + item % W;
+          const uint32_t x = tab[(i << k) * kTabStride + pp];
+          const uint32_t y = tab[((2 * i + 1) << (k - 1)) * kTabStride + pp];
+          const uint32_t v = x + y - 4u;
+          tab[(i << k) * kTabStride + pp] = v > kMaxBits ? kMaxBits : v;
+        }
+        __syncthreads();
+      }
+      if (tid < np) {
+        uint32_t m = 0xFFFFFFFFu;  // PrcBitTable::minimizer (rice.rs:115-141): min over (bits << 5) | p
+        for (int pp = lo; pp <= hi; ++pp) {
+          const uint32_t packed = (tab[(tid << k) * kTabStride + pp] << 5) | (uint32_t)pp;
+          m = packed < m ? packed : m;
+        }
+        pl[tid] = (uint8_t)(m & 31u);
+        atomicAdd(&lvl_bits[k], (unsigned long long)(m >> 5));
+        if ((m & 31u) > 14u) atomicOr(&misc[kRice2], 1u << k);
+      }
+      __syncthreads();
+      const unsigned long long lb = lvl_bits[k];
+      if (lb < best_bits) {
+        best_bits = lb;
+        best_lvl = k;
+        best_r2 = ((misc[kRice2] >> k) & 1u) != 0u;
+        if (wide && tid < np) psel[tid] = pl[tid];  // (each lane its own entry)
+      }
+    }
+
+    // ---- Lpc::count_bits (bitrepr.rs:492-499, 533-544) ----
+    const int nb = nparts >> best_lvl;
+    const unsigned long long wq = (unsigned long long)q;
+    unsigned long long key;
+    if (!wide) {
+      // no entry of the chosen level saturates or wraps: code_bits is the exact sum, and the residual's bits are
+      // 2 + 4 + nb * (4 or 5) + quotients + remainders = 6 + code_bits (+ nb with the 5-bit parameters)
+      key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + 6ull + best_bits + (best_r2 ? (unsigned long long)nb : 0ull);
+    } else {
+      __syncthreads();  // (psel complete)
+      const int pb = psize << best_lvl;
+      unsigned long long s = 0;
+      for (int t = q + tid; t < n; t += kOsThreads) s += (unsigned long long)(ubuf[t] >> psel[t / pb]);
+      s = wave_sum_u64(s);
+      if (lane == 0) atomicAdd(&acc64[0], s);
+      __syncthreads();
+      const unsigned long long sum_q = acc64[0];
+      unsigned long long sum_p = 0;
+      for (int i = 0; i < nb; ++i) sum_p += psel[i];
+      const unsigned long long rbits = 6ull + (unsigned long long)nb * (best_r2 ? 5ull : 4ull) + sum_q +
+                                       (unsigned long long)(n - q) + (sum_p * (unsigned long long)pb - wq * psel[0]);
+      key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + rbits;
+    }
+    if (key < best_key) {  // strict: the lower order wins a tie
+      best_key = key;
+      best_o = (uint32_t)o;
+    }
+  }
+  if (tid == 0) a.best[sf] = best_o;
+}
+
+template <int MAXP>
+hipError_t launch_levinson_and_pick(bool pick, const double* racc, const QlpcKernelArgs& a, int32_t* cand, uint32_t* best,
+                                    int32_t* pred, hipStream_t stream) {
+  if (!pick) {
+    const size_t items = (size_t)a.n_subframes * a.lpc_order;
+    hipLaunchKernelGGL(order_levinson_kernel<MAXP>, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, racc,
+                       a.n_subframes, a.lpc_order, a.precision, cand);
+  } else {
+    hipLaunchKernelGGL(order_pick_kernel<MAXP>, dim3((a.n_subframes + 63) / 64), dim3(64), 0, stream, racc, a.n_subframes,
+                       a.lpc_order, a.precision, best, pred, a.lpc_coefs);
+  }
+  return hipGetLastError();
+}
+
+hipError_t levinson_bucket(bool pick, const double* racc, const QlpcKernelArgs& a, int32_t* cand, uint32_t* best,
+                           int32_t* pred, hipStream_t stream) {
+  const uint32_t P = a.lpc_order;
+  if (P <= 8) return launch_levinson_and_pick<8>(pick, racc, a, cand, best, pred, stream);
+  if (P <= 12) return launch_levinson_and_pick<12>(pick, racc, a, cand, best, pred, stream);
+  if (P <= 16) return launch_levinson_and_pick<16>(pick, racc, a, cand, best, pred, stream);
+  if (P <= 24) return launch_levinson_and_pick<24>(pick, racc, a, cand, best, pred, stream);
+  return launch_levinson_and_pick<32>(pick, racc, a, cand, best, pred, stream);
+}
+
+}  // namespace
+
+size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order) {
+  return static_cast<size_t>(n_subframes) * (static_cast<size_t>(lpc_order) * kCandWords * 4 + 4);
+}
+
+hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly, void* scratch,
+                               hipStream_t stream) {
+  if (a.n_subframes == 0) return hipSuccess;
+  if (a.split_scratch == nullptr || scratch == nullptr || a.lpc_order < 1 || a.lpc_order > 32 || a.block_size < 64 ||
+      a.block_size > 32767)
+    return hipErrorInvalidValue;
+  const size_t n = a.n_subframes;
+  double* racc = a.autocorr ? a.autocorr : reinterpret_cast<double*>(a.split_scratch);
+  int32_t* pred = reinterpret_cast<int32_t*>(reinterpret_cast<double*>(a.split_scratch) + n * 33);
+  int32_t* cand = static_cast<int32_t*>(scratch);
+  uint32_t* best = reinterpret_cast<uint32_t*>(cand + n * a.lpc_order * kCandWords);
+
+  // 1. R[0..P] in the stable build's order (or nightly's)
+  AcorrRefArgs r{};
+  r.samples = a.samples;
+  r.stride = a.stride;
+  r.block_size = a.block_size;
+  r.n_subframes = a.n_subframes;
+  r.stereo = a.stereo;
+  r.window = a.window;
+  r.lpc_order = a.lpc_order;
+  r.nightly = nightly;
+  r.out = racc;
+  hipError_t err = launch_acorr_reference(r, stream);
+  if (err != hipSuccess) return err;
+  // 2. every candidate's predictor
+  if ((err = levinson_bucket(false, racc, a, cand, best, pred, stream)) != hipSuccess) return err;
+  // 3. the search
+  OrderSearchArgs s{};
+  s.samples = a.samples;
+  s.stride = a.stride;
+  s.block_size = a.block_size;
+  s.n_subframes = a.n_subframes;
+  s.stereo = a.stereo;
+  s.bps = a.bps;
+  s.bps_uniform = a.bps_uniform;
+  s.lpc_order = a.lpc_order;
+  s.precision = a.precision;
+  s.max_rice_parameter = a.max_rice_parameter;
+  s.rice_finest_only = a.rice_finest_only;
+  s.cand = cand;
+  s.best = best;
+  s.residual = a.residual;
+  s.residual_stride = a.residual_stride;
+  const bool lds_u = search_lds_bytes(a.block_size, true) <= 160 * 1024;
+  const size_t smem = search_lds_bytes(a.block_size, lds_u);
+  if (smem > 160 * 1024) return hipErrorInvalidValue;
+  if (lds_u) {
+    static DynamicLdsOptIn opt_in;
+    if ((err = opt_in.ensure(reinterpret_cast<const void*>(order_search_kernel<true>), smem)) != hipSuccess) return err;
+    hipLaunchKernelGGL(order_search_kernel<true>, dim3(a.n_subframes), dim3(kOsThreads), smem, stream, s);
+  } else {
+    if (a.residual == nullptr) return hipErrorInvalidValue;
+    static DynamicLdsOptIn opt_in;
+    if ((err = opt_in.ensure(reinterpret_cast<const void*>(order_search_kernel<false>), smem)) != hipSuccess) return err;
+    hipLaunchKernelGGL(order_search_kernel<false>, dim3(a.n_subframes), dim3(kOsThreads), smem, stream, s);
+  }
+  if ((err = hipGetLastError()) != hipSuccess) return err;
+  // 4. the chosen order's predictor record (+ unquantised coefficients)
+  if ((err = levinson_bucket(true, racc, a, cand, best, pred, stream)) != hipSuccess) return err;
+  // 5. records and residual rows by the unflagged stage-3 kernels (as behind direct_mse_kernel)
+  QlpcKernelArgs s3 = a;
+  s3.lpc_stage = 3;
+  s3.pred = pred;
+  s3.autocorr = nullptr;
+  s3.lpc_coefs = nullptr;
+  s3.acorr_in = nullptr;
+  s3.reference_order = 0;
+  s3.certify = 0;
+  s3.cert_subwave = 0;
+  s3.integer_parity_only = 0;
+  s3.direct_mse = 0;
+  s3.sumabs_in = nullptr;
+  s3.sumabs_scratch = nullptr;
+  if (bigblock_shape_eligible(a)) {
+    if ((err = launch_bigblock_residual(s3, stream)) != hipSuccess) return err;
+    s3.only_marked = 1;  // residuals of 2^26 and more: redone by the generic kernel
+  }
+#define FLACENC_HIP_OS3(MP, BG) \
+  if (plan.maxp == MP && plan.big == (BG != 0)) return launch_qlpc_##MP##_##BG(s3, plan.threads, plan.smem_bytes, stream);
+  FLACENC_HIP_FOR_EACH_INSTANCE(FLACENC_HIP_OS3)
+#undef FLACENC_HIP_OS3
+  return hipErrorInvalidValue;
+}
+
+}  // namespace flacenc_hip

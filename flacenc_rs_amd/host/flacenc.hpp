@@ -513,11 +513,16 @@ class HipContext {
   SumOrder sum_order() const { return sum_order_; }
   // (never FLACENC_HIP_FLAG_WASTED_BITS: the SubFrame rebuilt from the records has no wasted-bits field; a caller of
   // encode_variable may pass it in cfg, and the frames' bytes then carry the wasted bits)
+  // FLACENC_HIP_FLAG_ORDER_SEARCH: every LPC subframe's order searched over 1..lpc_order (the records stay ordinary
+  // SubFrame::Lpc of the chosen order); off by default
+  void set_order_search(bool on) { order_search_ = on; }
+  bool order_search() const { return order_search_; }
   uint32_t sum_order_flags(size_t lpc_order) const {
+    const uint32_t os = order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u;
     // (the mirror consumes integers only: certified shapes keep their own order, INTEGER_PARITY_ONLY)
-    if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY;
-    if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER;
-    return 0u;
+    if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY | os;
+    if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER | os;
+    return os;
   }
 
   // The block-size search (flacenc_hip_encode_variable, host memory): `frames` in FrameBuf layout, channel c of
@@ -552,6 +557,7 @@ class HipContext {
  private:
   flacenc_hip_handle* h_ = nullptr;
   SumOrder sum_order_ = SumOrder::Canonical;
+  bool order_search_ = false;
 };
 
 // Staging memory for the host-pointer entry points: page-locked (flacenc_hip_host_alloc), so that the

@@ -171,6 +171,29 @@ extern "C" {
  * flacenc_hip_destroy.  Callers that bound memory bound the frames per call. */
 #define FLACENC_HIP_FLAG_WASTED_BITS 512u
 
+/* LPC order search, an extension like FLACENC_HIP_FLAG_WASTED_BITS (libFLAC searches the order; the reference always codes
+ * lpc_order coefficients, src/coding.rs:360-381).  For every LPC candidate subframe with lpc_order = P (a role L, R, M, S
+ * of a stereo frame, a channel, or a row of a candidate batch):
+ *   - R[0..P] is the autocorrelation FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER gives (the stable build's chains), or the
+ *     simd-nightly build's with FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER; CANONICAL_SUM_ORDER and INTEGER_PARITY_ONLY have no
+ *     effect under this flag;
+ *   - candidate o = 1..P: the recursion on R[0..o] with levinson_quantize's status checks on lags 0..o,
+ *     quantize_parameters, the residual and the reference's exhaustive Rice search (max_rice_parameter and
+ *     FINEST_RICE_ORDER honoured); its key is the exact Lpc::count_bits;
+ *   - the candidate with status 0 and the smallest key is coded, the lower order on a tie; if no order has status 0 the
+ *     record is the order-P record, status included.
+ * The record and residual row are the chosen order's (order = o after quantize_parameters' tail-zero truncation),
+ * `autocorr` holds R[0..P], `lpc_coefs` the chosen order's unquantised coefficients with zeros from o on.  Candidate P is
+ * the REFERENCE_SUM_ORDER record, so no flagged LPC record -- and, since encode_subframe and try_stereo_coding compare
+ * exact bit counts, no flagged frame -- is longer than the REFERENCE_SUM_ORDER one; at lpc_order 1 no byte changes.
+ * Honoured by the candidate batches (flacenc_hip_qlpc_batch[_async], _stereo_qlpc_batch[_async]) and every frame-level
+ * call, which then take the candidate batches and the stand-alone deciding kernels for every shape; composes with
+ * FLACENC_HIP_FLAG_WASTED_BITS; FUSED_PACK is ignored; flacenc_hip_fixed_lpc_batch accepts and ignores the flag.
+ * use_direct_mse with this flag answers FLACENC_HIP_ERR_UNSUPPORTED (flacenc_hip_verify_config and every call).
+ * Scratch: P predictor records of 144 bytes per subframe (about 0.7 GB for 393 216 subframes at order 12), kept by the
+ * handle until flacenc_hip_destroy. */
+#define FLACENC_HIP_FLAG_ORDER_SEARCH 1024u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1

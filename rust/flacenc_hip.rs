@@ -52,6 +52,10 @@ pub const FLAG_INTEGER_PARITY_ONLY: u32 = 256;
 /// binding sets it -- `encode_with_fixed_block_size` must not, because the reference's `SubFrame` it rebuilds has no
 /// wasted-bits field.
 pub const FLAG_WASTED_BITS: u32 = 512;
+/// `FLACENC_HIP_FLAG_ORDER_SEARCH`: every LPC candidate's order is chosen by an exhaustive search over `1..=lpc_order`
+/// (smallest exact bit count, the lower order on a tie), on the stable build's autocorrelation.  The records stay
+/// ordinary `SubFrame::Lpc` of the chosen order, so `encode_with_fixed_block_size` may pass it.
+pub const FLAG_ORDER_SEARCH: u32 = 1024;
 
 /// `flacenc_hip_qlpc_config` (include/flacenc_hip.h): the path's fields of `config::Qlpc` /
 /// `config::Prc` (`src/config.rs:271-288`, `211-214`).

@@ -7,7 +7,7 @@ What stays on the host is what the reference keeps serial too: the container's 4
 MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-frame) batch: the
 frame-level entry points take any block size.
 
-    python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits]
+    python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -15,6 +15,8 @@ the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINF
 With --wasted-bits (FLACENC_HIP_FLAG_WASTED_BITS) a subframe whose samples all end in k zero bits -- 16-bit content in a
 24-bit WAV, say -- is coded as x >> k at bits_per_sample - k bits; the reference never writes them, every decoder reads
 them.
+With --order-search (FLACENC_HIP_FLAG_ORDER_SEARCH) every LPC subframe's order is the one of 1..--lpc-order whose exact
+bit count is smallest; the histogram of the chosen orders is printed.
 """
 import argparse
 import hashlib
@@ -109,8 +111,11 @@ def main():
     ap.add_argument("--levels", type=int, default=0, help="block-size search over 1..5 levels (variable blocking)")
     ap.add_argument("--wasted-bits", action="store_true",
                     help="code subframes whose low bits are all zero at reduced width (FLACENC_HIP_FLAG_WASTED_BITS)")
+    ap.add_argument("--order-search", action="store_true",
+                    help="search the LPC order of every subframe (FLACENC_HIP_FLAG_ORDER_SEARCH)")
+    ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
-    flags = _capi.FLAG_WASTED_BITS if args.wasted_bits else 0
+    flags = (_capi.FLAG_WASTED_BITS if args.wasted_bits else 0) | (_capi.FLAG_ORDER_SEARCH if args.order_search else 0)
     n = 4096
     if len(args.paths) == 2:
         with wave.open(args.paths[0], "rb") as w:
@@ -127,14 +132,14 @@ def main():
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
     if args.levels:
         data, v = encode_pcm_variable(pcm, bps, rate, _capi.Handle(0), block_size=n, levels=args.levels,
-                                      flags=flags)
+                                      lpc_order=args.lpc_order, flags=flags)
         with open(args.paths[-1], "wb") as f:
             f.write(data)
         sizes = np.bincount(v["block_sizes"]).nonzero()[0]
         print(f"{v['frames']} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM "
               f"size; block sizes {dict((int(b), int((v['block_sizes'] == b).sum())) for b in sizes)}")
         return
-    data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n, flags=flags)
+    data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n, lpc_order=args.lpc_order, flags=flags)
     nf = len(res)
     with open(args.paths[-1], "wb") as f:
         f.write(data)
@@ -142,6 +147,10 @@ def main():
     wasted = int((res["pad"] != 0).sum())
     print(f"{nf} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM size; "
           f"subframes constant/verbatim/fixed/lpc = {kinds.tolist()}, with wasted bits {wasted}")
+    if args.order_search:
+        orders = res["lpc"]["order"][res["kind"] == 3]
+        hist = np.bincount(orders, minlength=args.lpc_order + 1)
+        print("chosen LPC orders: " + ", ".join(f"{o}: {int(c)}" for o, c in enumerate(hist) if c))
 
 
 if __name__ == "__main__":
