@@ -18,7 +18,7 @@ constexpr uint32_t kWideU = 1u << 27;             // zig-zag codes from here on 
 constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, 0 (levinson_batch_kernel's record)
 constexpr size_t kSmallBytes = 1024 + 16 * 8 + 2 * 8 + 16 * 4 + 256 + 256;  // psum, level bits, sums, misc, two ps rows
 
-enum { kMaxAbs = 0, kUMax, kSat, kLo, kHi, kRice2 };
+enum { kMaxAbs = 0, kUMax, kSat, kLo, kHi, kRice2, kClamp };
 
 struct OrderSearchArgs {
   const int32_t* samples;
@@ -121,10 +121,15 @@ __global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict
 // does not decrease with p, and is > 0 once len 2^p > sum(u), < 0 while 3 len 2^p <= sum(u).  So every partition's minimisers
 // lie in [lo_i, hi_i] (the smallest p with 3 len 2^p > S_i, resp. len 2^p > S_i, both capped at max_p), a merged table is
 // a sum of such functions, and its minimisers lie inside [min lo_i, max hi_i]: outside it every table is strictly
-// monotone.  Entries that saturate at MAX_P_TO_BITS are far above any minimum (a partition's at hi_i stays below
-// 32 len).  The argument needs every entry to be min(MAX, exact sum): zig-zag codes below 2^27 (no 16-sample chunk can
+// monotone.  The argument needs every entry to be min(MAX, exact sum): zig-zag codes below 2^27 (no 16-sample chunk can
 // wrap the u32 accumulator) and every S_i below 2^32 here; otherwise the window is all of 0..max_p.  The entries
 // themselves are always computed as the reference does -- u32 adds, the clamp after each 16-sample chunk.
+//
+// Saturated entries: when max_p caps hi_i far below the residual's scale, a merged partition's entries can all be
+// MAX_P_TO_BITS, inside the window and (the table only grows away from it) outside.  The reference's minimiser then picks
+// p = 0, and its count_bits is the true sum at p = 0, not the clamped table value.  So such a partition takes p = 0 here
+// too, and a chosen level with one -- or any chosen level when codes reach 2^27 -- gets its key from a pass over the true
+// quotients.  Otherwise (S_i of 2^32 and more included) every chosen entry is below MAX and hence the exact sum.
 template <bool LDS_U>
 __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -213,6 +218,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
       misc[kLo] = 31u;
       misc[kHi] = 0u;
       misc[kRice2] = 0u;
+      misc[kClamp] = 0u;
     }
     __syncthreads();
 
@@ -312,6 +318,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
     unsigned long long best_bits = ~0ull;
     int best_lvl = 0;
     bool best_r2 = false;
+    bool best_clamp = false;
     const int levels = a.rice_finest_only ? 1 : fo + 1;
     for (int k = 0; k < levels; ++k) {
       const int np = nparts >> k;
@@ -333,6 +340,10 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
           const uint32_t packed = (tab[(tid << k) * kTabStride + pp] << 5) | (uint32_t)pp;
           m = packed < m ? packed : m;
         }
+        if ((m >> 5) >= kMaxBits) {  // every entry of 0..max_p saturates: the reference's minimiser picks p = 0
+          m = kMaxBits << 5;
+          atomicOr(&misc[kClamp], 1u << k);
+        }
         pl[tid] = (uint8_t)(m & 31u);
         atomicAdd(&lvl_bits[k], (unsigned long long)(m >> 5));
         if ((m & 31u) > 14u) atomicOr(&misc[kRice2], 1u << k);
@@ -343,7 +354,8 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
         best_bits = lb;
         best_lvl = k;
         best_r2 = ((misc[kRice2] >> k) & 1u) != 0u;
-        if (wide && tid < np) psel[tid] = pl[tid];  // (each lane its own entry)
+        best_clamp = ((misc[kClamp] >> k) & 1u) != 0u;
+        if ((wide || best_clamp) && tid < np) psel[tid] = pl[tid];  // (each lane its own entry)
       }
     }
 
@@ -351,7 +363,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
     const int nb = nparts >> best_lvl;
     const unsigned long long wq = (unsigned long long)q;
     unsigned long long key;
-    if (!wide) {
+    if (!wide && !best_clamp) {
       // no entry of the chosen level saturates or wraps: code_bits is the exact sum, and the residual's bits are
       // 2 + 4 + nb * (4 or 5) + quotients + remainders = 6 + code_bits (+ nb with the 5-bit parameters)
       key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + 6ull + best_bits + (best_r2 ? (unsigned long long)nb : 0ull);

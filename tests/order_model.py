@@ -150,3 +150,55 @@ def channel_frame_bytes(xs, bps, fc, number=0, sample_rate=44100) -> bytes:
     """An Independent(len(xs)) frame."""
     subs = [encode_subframe(x, bps, fc)[2] for x in xs]
     return oracle.write_frame(len(xs[0]), 0, bps, sample_rate, number, subs)
+
+
+# ---- composed with FLACENC_HIP_FLAG_WASTED_BITS (tests/wasted_model.py) ----
+def wasted_subframe(x, w, fc) -> dict:
+    """encode_subframe under both flags: k = wasted_model.wasted_of(x), then encode_subframe(x >> k, w - k) with the
+    flagged LPC candidate, at its bits + k."""
+    import wasted_model
+    x = np.ascontiguousarray(x, np.int32)
+    k = wasted_model.wasted_of(x, fc)
+    kind, bits, kw = encode_subframe(x >> k, w - k, fc)
+    return {"kind": kind, "bits": bits + k, "k": k, "kw": kw}
+
+
+def _flac_write_args(s) -> dict:
+    """flac_write.write_subframe keywords for one composed subframe."""
+    kind, kw, k = s["kind"], s["kw"], s["k"]
+    if kind == 0:
+        return {"kind": "constant", "wasted": k}
+    if kind == 1:
+        return {"kind": "verbatim", "wasted": k}
+    porder = int(kw["rice_order"])
+    params = [int(p) for p in kw["rice_params"][:1 << porder]]
+    out = {"kind": "fixed" if kind == 2 else "lpc", "order": int(kw["order"]), "wasted": k, "porder": porder,
+           "params": params, "method": 1 if max(params) > 14 else 0}
+    if kind == 3:
+        out.update(coefs=[int(c) for c in kw["coefs"][:int(kw["order"])]], precision=int(kw["precision"]),
+                   shift=int(kw["shift"]))
+    return out
+
+
+def wasted_stereo_frame_bytes(l, r, bps, fc, number=0) -> bytes:
+    """A 2-channel frame under both flags, written by flac_write (the oracle's writer has no wasted bits)."""
+    import flac_write
+    import wasted_model
+    subs = [wasted_subframe(x, bps + (1 if k == 3 else 0), fc) for k, x in enumerate(wasted_model.roles(l, r))]
+    b = [s["bits"] for s in subs]
+    best, a = b[0] + b[1], 0
+    if fc.use_leftside and b[0] + b[3] < best:
+        best, a = b[0] + b[3], 1
+    if fc.use_rightside and b[1] + b[3] < best:
+        best, a = b[1] + b[3], 2
+    if fc.use_midside and b[2] + b[3] < best:
+        best, a = b[2] + b[3], 3
+    return flac_write.frame([l, r], wasted_model.STEREO_TAGS[a], bps, [_flac_write_args(subs[k]) for k in STEREO_ROLES[a]],
+                            number=number)
+
+
+def wasted_channel_frame_bytes(xs, bps, fc, number=0) -> bytes:
+    """An Independent(len(xs)) frame under both flags."""
+    import flac_write
+    subs = [wasted_subframe(x, bps, fc) for x in xs]
+    return flac_write.frame(xs, len(xs) - 1, bps, [_flac_write_args(s) for s in subs], number=number)

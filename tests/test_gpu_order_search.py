@@ -8,6 +8,7 @@ import torch
 
 import order_model as om
 import util
+from extreme_signals import check_rows
 from flacenc_rs_amd import _capi
 from oracle import oracle as orc
 
@@ -43,24 +44,6 @@ def gcfg(order, flags=0, **kw):
 
 def ocfg(order, nightly=False, finest=False):
     return om.config(order=order, nightly=nightly, rice_finest_only=finest)
-
-
-def check_rows(params, residual, R, A, x, bps, cfg, where):
-    for i in range(len(x)):
-        rec, resid, ac, lc = om.record(x[i], bps[i] if np.ndim(bps) else bps, cfg)
-        p = params[i]
-        assert int(p["status"]) == rec["status"], (where, i)
-        assert np.array_equal(R[i], ac), (where, i)
-        assert np.array_equal(A[i], lc), (where, i)
-        if rec["status"] != 0:
-            continue
-        got = {"order": int(p["order"]), "shift": int(p["shift"]), "precision": int(p["precision"]),
-               "coefs": [int(c) for c in p["coefs"]], "rice_order": int(p["rice_order"]),
-               "rice_params": [int(c) for c in p["rice_params"][:1 << int(p["rice_order"])]], "status": 0,
-               "code_bits": int(p["code_bits"]), "subframe_bits": int(p["subframe_bits"]),
-               "sum_quotients": int(p["sum_quotients"])}
-        assert got == rec, (where, i)
-        assert np.array_equal(residual[i], resid), (where, i)
 
 
 BATCH_CASES = [
@@ -218,6 +201,8 @@ def test_with_wasted_bits_equals_the_model_and_decodes(h):
     got = gpu_stereo(h, frame_cfg(8, _capi.FLAG_WASTED_BITS), x, 24)
     fc = orc.make_frame_config(ocfg(8))
     assert got[0] == om.stereo_frame_bytes(x[0, 0], x[0, 1], 24, fc, number=0)
+    for f in range(len(x)):  # (the wasted-bits frames against the composed model)
+        assert got[f] == om.wasted_stereo_frame_bytes(x[f, 0], x[f, 1], 24, fc, number=f), f
     decode_check(h, got, x, 24)
     plain = gpu_stereo(h, frame_cfg(8, 0), x, 24)
     assert len(got[1]) < len(plain[1])

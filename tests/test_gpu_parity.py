@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import util
+from extreme_signals import extreme_frames
 from flacenc_rs_amd import _capi
 from oracle import oracle as orc
 
@@ -1167,46 +1168,6 @@ def test_candidate_and_channel_api_fuzz(handle, seed):
             raise AssertionError(f"configuration {tag}: {e}") from e
 
 
-def _extreme_frames(rng, n, bps):
-    """Stereo frames built from worst-case material: full-scale alternation and square waves,
-    impulses, full-range ramps, clipped sines, one channel silent / constant / inverted."""
-    lo, hi = -(1 << (bps - 1)), (1 << (bps - 1)) - 1
-    t = np.arange(n)
-
-    def one():
-        k = int(rng.integers(0, 8))
-        if k == 0:
-            return np.where(t % 2 == 0, hi, lo)
-        if k == 1:
-            return np.where((t // int(rng.integers(1, 200))) % 2 == 0, hi, lo)
-        if k == 2:
-            x = np.zeros(n, np.int64)
-            x[rng.integers(0, n, int(rng.integers(1, 6)))] = rng.choice([lo, hi])
-            return x
-        if k == 3:
-            return np.linspace(lo, hi, n).astype(np.int64)
-        if k == 4:
-            return np.clip(np.sin(t / float(rng.uniform(1.5, 300.0))) * hi * float(rng.uniform(1.0, 4.0)), lo, hi).astype(np.int64)
-        if k == 5:
-            return np.full(n, int(rng.integers(lo, hi + 1)))
-        if k == 6:
-            return rng.integers(lo, hi + 1, n)
-        return (rng.integers(-3, 4, n)).cumsum().clip(lo, hi)
-
-    frames = []
-    for _ in range(6):
-        l, r = one(), one()
-        m = int(rng.integers(0, 5))
-        if m == 0:
-            r = l.copy()
-        elif m == 1:
-            r = np.clip(-l, lo, hi)
-        elif m == 2:
-            r = np.clip(l + rng.integers(-2, 3, n), lo, hi)
-        frames.append(np.stack([l, r]))
-    return np.stack(frames).astype(np.int32)
-
-
 # 2616: full-scale 24-bit alternation whose order-24 residual wraps i32 -- the reference's u32-wrapping
 # table sums (rice.rs:88-93) stay small while the true quotient sum is ~2e12 bits; found by the sweep
 @pytest.mark.parametrize("seed", list(range(4)) + [2616])
@@ -1227,7 +1188,7 @@ def test_extreme_signals_and_layout_fuzz(handle, monkeypatch, seed):
         use_fixed = bool(rng.random() < 0.6)
         fx = dict(fixed_max_order=int(rng.integers(0, 5)), fixed_order_sel=int(rng.random() < 0.7),
                   fixed_partitions=int(rng.choice([1, 4, 16, 64, 7])))
-        x = _extreme_frames(rng, n, bps)
+        x = extreme_frames(rng, n, bps)
         F = x.shape[0]
         stride = n + int(rng.choice([0, 0, 4, 8, 3, 5]))
         rstride = n + int(rng.choice([0, 0, 4, 1]))
@@ -1327,7 +1288,7 @@ def test_extreme_candidates_fuzz(handle, seed):
         qcfg = dict(lpc_order=order, quant_precision=int(rng.integers(2, 16)),
                     window=("rectangle" if rng.random() < 0.3 else ("tukey", float(np.round(rng.random(), 2)))),
                     max_rice_parameter=int(rng.choice([0, 4, 14, 15, 30, 30])))
-        x = _extreme_frames(rng, n, bps)          # [6, 2, n]
+        x = extreme_frames(rng, n, bps)          # [6, 2, n]
         flat = x.reshape(-1, n)
         bpsv = np.full(flat.shape[0], bps, np.uint8)
         if bps < 24:

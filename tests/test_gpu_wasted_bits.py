@@ -281,6 +281,33 @@ def test_encode_variable_round_trip(h, levels):
     assert h.verify_frames(r["data"], r["offsets"], r["lengths"], 2, 24, S, want).tolist() == [0] * n
 
 
+def late_break_cases(b):
+    """Stereo frames at 24 bits whose samples are all multiples of 2^k except one odd sample, at index 64, 65 or
+    n - 1, in L only (L, M and S break late), in R only (R, M and S), or in L and R both (L, R and M; S keeps its wasted
+    bits -- a break in S alone is impossible): the wasted-bits scan must not stop early."""
+    x = content(1, 2, b, start=5 * b)[0] << 4
+    frames = []
+    for t in sorted({min(64, b - 1), min(65, b - 1), b - 1}):
+        for where in ("L", "R", "LR"):
+            l, r = x[0].copy(), x[1].copy()
+            if "L" in where:
+                l[t] |= 1
+            if "R" in where:
+                r[t] |= 1
+            frames.append((l, r))
+    return np.stack([np.stack(f) for f in frames]).astype(np.int32)
+
+
+@pytest.mark.parametrize("b", STEREO_SHAPES)
+def test_one_late_odd_sample_equals_the_model(h, b):
+    x = late_break_cases(b)
+    fc = wm.frame_config(order=8)
+    got, _ = gpu_stereo(h, cfg_of(), x, 24)
+    for f in range(len(x)):
+        assert got[f] == wm.stereo_frame_bytes(x[f, 0], x[f, 1], 24, fc, number=f), (b, f)
+    decode_check(h, got, x, 24)
+
+
 def test_frame_lengths_agree_with_the_packer(h):
     b = 4096
     x = stereo_cases(b)
