@@ -37,6 +37,18 @@ _ERR_NAMES = {
 
 WINDOW_RECTANGLE = 0
 WINDOW_TUKEY = 1
+WINDOW_PARTIAL_TUKEY = 2  # FLAG_WINDOW_SEARCH's extra windows only: T(e - s) on [s, e)
+WINDOW_PUNCHOUT_TUKEY = 3  # T(s) on [0, s), zero on [s, e), T(n - e) on [e, n)
+MAX_LPC_WINDOWS = 8  # FLACENC_HIP_MAX_LPC_WINDOWS: the config's window + at most 7 extra windows
+WINDOW_UNIT = 65536  # FLACENC_HIP_WINDOW_UNIT: start / end of an extra window in 1/65536 of the block
+# the extra windows of a fresh handle, (type, alpha, start, end) -- include/flacenc_hip.h, FLACENC_HIP_FLAG_WINDOW_SEARCH
+DEFAULT_LPC_WINDOWS = (
+    (WINDOW_PARTIAL_TUKEY, 0.2, 0, 36044),
+    (WINDOW_PARTIAL_TUKEY, 0.2, 29492, 65536),
+    (WINDOW_PUNCHOUT_TUKEY, 0.2, 0, 21845),
+    (WINDOW_PUNCHOUT_TUKEY, 0.2, 21845, 43690),
+    (WINDOW_PUNCHOUT_TUKEY, 0.2, 43690, 65536),
+)
 FLAG_ALLOW_ORDER_32 = 1
 MEM_HOST = 0
 MEM_DEVICE = 1
@@ -59,6 +71,8 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_last_error",
     "flacenc_hip_verify_config",
     "flacenc_hip_window_weights",
+    "flacenc_hip_set_lpc_windows",
+    "flacenc_hip_lpc_window_weights",
     "flacenc_hip_qlpc_batch",
     "flacenc_hip_qlpc_batch_async",
     "flacenc_hip_stereo_qlpc_batch",
@@ -254,6 +268,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_verify_config.restype = C.c_int
     L.flacenc_hip_window_weights.argtypes = [C.POINTER(QlpcConfig), C.c_uint32, vp]
     L.flacenc_hip_window_weights.restype = C.c_int
+    L.flacenc_hip_set_lpc_windows.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
+    L.flacenc_hip_set_lpc_windows.restype = C.c_int
+    L.flacenc_hip_lpc_window_weights.argtypes = [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.flacenc_hip_lpc_window_weights.restype = C.c_int
     L.flacenc_hip_synchronize.argtypes = [vp]
     L.flacenc_hip_synchronize.restype = C.c_int
     # test / profiling hooks (csrc/flacenc_hip_debug.h): present in builds with -DFLACENC_HIP_DEBUG_HOOKS only
@@ -405,6 +423,7 @@ FLAG_CANONICAL_SUM_ORDER = 128  # the kernels' own order without the order certi
 FLAG_INTEGER_PARITY_ONLY = 256  # with FLAG_REFERENCE_SUM_ORDER: certified shapes keep their own order (integers only)
 FLAG_WASTED_BITS = 512  # frame-level calls code subframes whose low bits are all zero as x >> k at w - k bits
 FLAG_ORDER_SEARCH = 1024  # every LPC candidate's order chosen by an exhaustive search over 1..lpc_order
+FLAG_WINDOW_SEARCH = 2048  # every LPC candidate analysed under the config's window and the handle's extra windows
 
 
 def wasted_bits(results) -> np.ndarray:
@@ -439,6 +458,22 @@ def window_weights(cfg: QlpcConfig, block_size: int) -> np.ndarray:
     if rc != OK:
         raise FlacencHipError(rc)
     return out
+
+
+def lpc_window_weights(window_type: int, alpha: float, start: int, end: int, block_size: int) -> np.ndarray:
+    """flacenc_hip_lpc_window_weights: one extra-window entry's weights over a block (host only, no GPU)."""
+    out = np.empty(max(block_size, 1), np.float32)
+    rc = load().flacenc_hip_lpc_window_weights(window_type, alpha, start, end, block_size, out.ctypes.data)
+    if rc != OK:
+        raise FlacencHipError(rc, "flacenc_hip_lpc_window_weights")
+    return out[:block_size]
+
+
+def _window_arrays(entries):
+    """(type, alpha, start, end) entries -> the four parallel arrays flacenc_hip_set_lpc_windows takes."""
+    entries = list(entries)
+    return (np.array([e[0] for e in entries], np.uint32), np.array([e[1] for e in entries], np.float32),
+            np.array([e[2] for e in entries], np.uint32), np.array([e[3] for e in entries], np.uint32))
 
 
 def sigen_frames(n_frames: int, channels: int, block_size: int, bits_per_sample: int,
@@ -516,6 +551,14 @@ class Handle:
     def _check(self, rc):
         if rc != OK:
             raise FlacencHipError(rc, self._lib.flacenc_hip_last_error(self._h).decode())
+
+    def set_lpc_windows(self, entries):
+        """flacenc_hip_set_lpc_windows: the extra analysis windows of FLAG_WINDOW_SEARCH, (type, alpha, start, end)
+        each (DEFAULT_LPC_WINDOWS on a fresh handle; [] leaves the config's window only)."""
+        t, a, s, e = _window_arrays(entries)
+        n = len(t)
+        ptr = (lambda x: x.ctypes.data) if n else (lambda x: None)
+        self._check(self._lib.flacenc_hip_set_lpc_windows(self._h, ptr(t), ptr(a), ptr(s), ptr(e), n))
 
     def _hook(self, name):
         if not hasattr(self._lib, name):

@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(NIGHTLY ? 384 : 576) acorr_reference_kernel(Ac
   }
   const uint32_t sf = sf0 + (uint32_t)lane;
   if (sf < a.n_subframes) {
-    double* __restrict__ o = a.out + (size_t)sf * 33;
+    double* __restrict__ o = a.out + (size_t)sf * a.out_stride;
     if (!NIGHTLY) {
 #pragma unroll
       for (int j = 0; j < LPL; ++j)
@@ -434,10 +434,10 @@ __global__ void __launch_bounds__(256) acorr_nightly_kernel(AcorrRefArgs a) {
       acc += f;
       r = acc + lanesum;
     }
-    a.out[(size_t)sf * 33 + d] = r;
+    a.out[(size_t)sf * a.out_stride + d] = r;
   }
   // lags 16..32 are not produced in this mode: written as 0 like every lag above P
-  if (tid >= 192 && tid < 192 + 17) a.out[(size_t)sf * 33 + 16 + (tid - 192)] = 0.0;
+  if (tid >= 192 && tid < 192 + 17) a.out[(size_t)sf * a.out_stride + 16 + (tid - 192)] = 0.0;
 }
 
 hipError_t launch_nightly(const AcorrRefArgs& a, hipStream_t stream) {
@@ -645,7 +645,7 @@ __global__ void __launch_bounds__(256) acorr_reference_mfma_kernel(AcorrRefArgs 
     const int i = lane >> 4, bo = (lane >> 2) & 3, j = lane & 3;
     const uint32_t sf = sf0 + (uint32_t)bo;
     if (sf < a.n_subframes) {
-      double* __restrict__ o = a.out + (size_t)sf * 33;
+      double* __restrict__ o = a.out + (size_t)sf * a.out_stride;
 #pragma unroll
       for (int s_ = 0; s_ < NS; ++s_) {
         const int lag = i + 4 * j + 16 * s_;

@@ -18,7 +18,8 @@ struct AcorrRefArgs {
   const float* window;     // device table with 32 leading pad floats, nullptr = all ones
   uint32_t lpc_order;      // P: lags 0..P are produced
   uint32_t nightly;        // 0: the stable build's single chain per lag; 1: simd-nightly's lane chains (P <= 15)
-  double* out;             // device, [n_subframes][33]; lags above P are written as 0
+  double* out;             // device, [n_subframes][out_stride]: lags 0..32 of each; lags above P are written as 0
+  uint32_t out_stride = 33;  // doubles from one subframe's R[] to the next (>= 33)
   // Clean-up behind the sub-wave kernel's order certificate (round 6): only the subframes whose record carries status -2
   // (flacenc_hip_subframe_params, 352 bytes each; stable order only) -- a wave whose four subframes have none returns at
   // once, the whole launch when *marked_count is 0.  nullptr: every subframe.

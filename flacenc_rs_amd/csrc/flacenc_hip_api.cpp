@@ -38,8 +38,25 @@ struct WindowEntry {
   uint32_t n;
   uint32_t type;
   uint32_t alpha_bits;
+  uint32_t start, end;  // FLACENC_HIP_WINDOW_PARTIAL_TUKEY / _PUNCHOUT_TUKEY: the piece, in FLACENC_HIP_WINDOW_UNIT; else 0
   float* dev;  // 32 pad + rows*16 floats
   int32_t flat_lo, flat_hi;
+};
+
+// an extra analysis window of FLACENC_HIP_FLAG_WINDOW_SEARCH (flacenc_hip_set_lpc_windows)
+struct LpcWindow {
+  uint32_t type;
+  float alpha;
+  uint32_t start, end;
+};
+
+// the default extra windows of a fresh handle (include/flacenc_hip.h, _capi.DEFAULT_LPC_WINDOWS)
+const LpcWindow kDefaultLpcWindows[] = {
+    {FLACENC_HIP_WINDOW_PARTIAL_TUKEY, 0.2f, 0, 36044},
+    {FLACENC_HIP_WINDOW_PARTIAL_TUKEY, 0.2f, 29492, 65536},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 0, 21845},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 21845, 43690},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 43690, 65536},
 };
 
 struct DeviceBuffer {
@@ -141,13 +158,15 @@ struct flacenc_hip_handle {
   hipStream_t stream = nullptr;
   std::string last_error;
   std::vector<WindowEntry> windows;
+  // FLACENC_HIP_FLAG_WINDOW_SEARCH: the extra analysis windows (windows 1 .. W-1; window 0 is the config's)
+  std::vector<LpcWindow> lpc_windows{std::begin(kDefaultLpcWindows), std::end(kDefaultLpcWindows)};
   DeviceBuffer d_samples, d_residual, d_params, d_bps, d_autocorr, d_lpc, d_tables, d_keys, d_sel, d_results, d_out, d_outlen, d_cparams, d_cresid, d_fparams, d_fresid, d_fkeys, d_split, d_presid, d_sumabs, d_minmax, d_marked, d_irlsw, d_gram;
   DeviceBuffer d_dec, d_dec_io, d_idx;  // frame decoder: skim records, host-pointer staging, index candidates
   // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
   DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
   // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
   DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
-  // order search: every candidate order's predictor record and the chosen order (order_search.h)
+  // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
   DeviceBuffer d_order;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
@@ -240,19 +259,62 @@ void window_weights(uint32_t type, float alpha, size_t len, float* out) {
   }
 }
 
+// T(m), the reference's Tukey weights of length m (lpc::window_weights); all zeros below 2 samples, where the reference's
+// formula gives NaN
+void tukey_piece(float alpha, size_t m, float* out) {
+  if (m < 2) {
+    for (size_t t = 0; t < m; ++t) out[t] = 0.0f;
+    return;
+  }
+  window_weights(FLACENC_HIP_WINDOW_TUKEY, alpha, m, out);
+}
+
+// An analysis window of FLACENC_HIP_FLAG_WINDOW_SEARCH over a block of n samples: s = (start n) >> 16, e = (end n) >> 16
+// (64-bit integers, no floating point), RECTANGLE all ones, TUKEY T(n), PARTIAL_TUKEY T(e - s) on [s, e) and zeros
+// elsewhere, PUNCHOUT_TUKEY T(s) on [0, s), zeros on [s, e), T(n - e) on [e, n).
+void lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, size_t n, float* out) {
+  if (type == FLACENC_HIP_WINDOW_RECTANGLE) {
+    window_weights(type, alpha, n, out);
+    return;
+  }
+  if (type == FLACENC_HIP_WINDOW_TUKEY) {
+    tukey_piece(alpha, n, out);
+    return;
+  }
+  const size_t s = static_cast<size_t>((static_cast<uint64_t>(start) * n) >> 16);
+  const size_t e = static_cast<size_t>((static_cast<uint64_t>(end) * n) >> 16);
+  for (size_t t = 0; t < n; ++t) out[t] = 0.0f;
+  if (type == FLACENC_HIP_WINDOW_PARTIAL_TUKEY) {
+    tukey_piece(alpha, e - s, out + s);
+  } else {
+    tukey_piece(alpha, s, out);
+    tukey_piece(alpha, n - e, out + e);
+  }
+}
+
+// flacenc_hip_set_lpc_windows / flacenc_hip_lpc_window_weights: an entry's validity
+bool lpc_window_ok(uint32_t type, float alpha, uint32_t start, uint32_t end) {
+  if (type > FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY) return false;
+  if (!(alpha >= 0.0f && alpha <= 1.0f)) return false;  // (NaN included)
+  if (type >= FLACENC_HIP_WINDOW_PARTIAL_TUKEY && (start >= end || end > FLACENC_HIP_WINDOW_UNIT)) return false;
+  return true;
+}
+
 // get_window, src/lpc.rs:222-231.  The reference keys its cache by
 // (size, fingerprint) where the fingerprint quantises alpha to 16 bits
 // (src/lpc.rs:123-132), so two alphas closer than 1/65535 share the first
-// one's table; this cache keys by the exact alpha bits instead.
-int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32_t n,
-               const WindowEntry** out) {
+// one's table; this cache keys by the exact alpha bits instead (and by the
+// piece of the window search's partial / punch-out windows).  Entries stay
+// until flacenc_hip_destroy: a queued launch may still read any of them.
+int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t n,
+                     const WindowEntry** out) {
   uint32_t alpha_bits;
-  std::memcpy(&alpha_bits, &cfg->tukey_alpha, 4);
-  uint32_t type = cfg->window_type;
-  if (type == FLACENC_HIP_WINDOW_TUKEY && cfg->tukey_alpha == 0.0f) type = FLACENC_HIP_WINDOW_RECTANGLE;
+  std::memcpy(&alpha_bits, &alpha, 4);
+  if (type == FLACENC_HIP_WINDOW_TUKEY && alpha == 0.0f) type = FLACENC_HIP_WINDOW_RECTANGLE;
   if (type == FLACENC_HIP_WINDOW_RECTANGLE) alpha_bits = 0;
+  if (type < FLACENC_HIP_WINDOW_PARTIAL_TUKEY) start = end = 0;
   for (const WindowEntry& e : h->windows) {
-    if (e.n == n && e.type == type && e.alpha_bits == alpha_bits) {
+    if (e.n == n && e.type == type && e.alpha_bits == alpha_bits && e.start == start && e.end == end) {
       *out = &e;
       return FLACENC_HIP_OK;
     }
@@ -261,6 +323,8 @@ int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32
   e.n = n;
   e.type = type;
   e.alpha_bits = alpha_bits;
+  e.start = start;
+  e.end = end;
   e.dev = nullptr;
   e.flat_lo = -64;
   e.flat_hi = 0x7FFFFFFF;
@@ -268,7 +332,7 @@ int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32
     const size_t rows = (n + 15) / 16;
     const size_t total = 32 + rows * 16 + 16;
     std::vector<float> host(total, 0.0f);
-    window_weights(type, cfg->tukey_alpha, n, host.data() + 32);
+    lpc_window_weights(type, alpha, start, end, n, host.data() + 32);
     // longest run of exactly-1.0 weights: chunks inside it skip the table
     int best_lo = 0, best_hi = 0, run_lo = -1;
     for (int t = 0; t <= static_cast<int>(n); ++t) {
@@ -290,6 +354,28 @@ int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32
   h->windows.push_back(e);
   *out = &h->windows.back();
   return FLACENC_HIP_OK;
+}
+
+int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32_t n, const WindowEntry** out) {
+  return get_window_entry(h, cfg->window_type, cfg->tukey_alpha, 0, 0, n, out);
+}
+
+// FLACENC_HIP_FLAG_WINDOW_SEARCH with no extra window is exactly the call with the summation-order flag in its place
+// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call).  Callers of the flagged entry points run their config
+// through this once, after flacenc_hip_verify_config.
+uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags) {
+  if (!(flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) || !h->lpc_windows.empty()) return flags;
+  flags &= ~FLACENC_HIP_FLAG_WINDOW_SEARCH;
+  if (flags & FLACENC_HIP_FLAG_ORDER_SEARCH) return flags;
+  flags &= ~(FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY);
+  if (!(flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER)) flags |= FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER;
+  return flags;
+}
+
+// The LPC candidate of a (normalised) config comes from the search over windows and orders (order_search.h): the frame
+// -level calls then take the candidate batches and the stand-alone deciding kernels for every shape.
+bool lpc_search(uint32_t flags) {
+  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH)) != 0;
 }
 
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
@@ -501,9 +587,13 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
             uint32_t bps_uniform = 16, int32_t* residual_lr = nullptr, size_t residual_lr_stride = 0,
             int32_t* minmax_out = nullptr, bool* placed = nullptr, uint32_t residual_mode = 0) {
   if (placed) *placed = false;
+  flacenc_hip_qlpc_config qcfg = *cfg;
+  qcfg.flags = search_flags(h, cfg->flags);
+  cfg = &qcfg;
   const WindowEntry* win = nullptr;
   int rc = get_window(h, cfg, block_size, &win);
   if (rc != FLACENC_HIP_OK) return rc;
+  const float* const win_dev = win->dev;  // (get_window_entry may grow h->windows below)
   flacenc_hip::QlpcLaunchPlan plan = flacenc_hip::plan_qlpc_launch(block_size, cfg->lpc_order);
   if (plan.smem_bytes > 160 * 1024) {
     h->last_error = "internal: LDS plan exceeds 160 KiB";
@@ -572,7 +662,7 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
   // (R[] and the predictor records between the launches of the split pipelines: orders from 13, and blocks of
   // 8192 / 16384 at any order -- the big-block kernels)
   // (... and, round 6, every unflagged launch: the reference's chains go in front of whatever kernel takes the shape)
-  const bool order_search = (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) != 0;
+  const bool order_search = lpc_search(cfg->flags);
   if (cfg->lpc_order >= 13 || a.reference_order || a.direct_mse || block_size == 8192 || block_size == 16384 ||
       flacenc_hip::subwave_shape(block_size) || a.certify != 0u || order_search) {
     if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
@@ -583,14 +673,27 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
     a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
   }
   if (order_search) {
-    // FLACENC_HIP_FLAG_ORDER_SEARCH: R[] in the stable build's order (nightly's with its flag; the
-    // certificate and INTEGER_PARITY_ONLY do not apply), every order 1..P searched, the records written by stage 3
+    // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: R[] of every window in the stable build's
+    // order (nightly's with its flag; the certificate and INTEGER_PARITY_ONLY do not apply), every candidate (window,
+    // order) searched, the records written by stage 3
     a.certify = 0;
     a.integer_parity_only = 0;
     a.cert_stats = nullptr;
-    rc = ensure(h, h->d_order, flacenc_hip::order_search_scratch_bytes(a.n_subframes, cfg->lpc_order));
+    flacenc_hip::SearchShape shape{};
+    shape.windows[0] = win_dev;
+    shape.n_windows = 1;
+    shape.search_orders = (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) ? 1u : 0u;
+    if (cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) {
+      for (const LpcWindow& w : h->lpc_windows) {
+        const WindowEntry* e = nullptr;
+        if ((rc = get_window_entry(h, w.type, w.alpha, w.start, w.end, block_size, &e)) != FLACENC_HIP_OK) return rc;
+        shape.windows[shape.n_windows++] = e->dev;
+      }
+    }
+    rc = ensure(h, h->d_order, flacenc_hip::order_search_scratch_bytes(a.n_subframes, cfg->lpc_order, shape));
     if (rc != FLACENC_HIP_OK) return rc;
-    HIP_TRY(h, flacenc_hip::launch_order_search(a, plan, a.reference_order == 2u ? 1u : 0u, h->d_order.ptr, stream));
+    HIP_TRY(h, flacenc_hip::launch_order_search(a, plan, a.reference_order == 2u ? 1u : 0u, shape, h->d_order.ptr,
+                                                stream));
     return FLACENC_HIP_OK;
   }
   // frame-level callers on the big-block shapes: L / R candidates straight into the output rows, role min / max
@@ -870,7 +973,7 @@ static int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* 
   if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
   // the unflagged configuration (FUSED_PACK: a kernel choice the fix-up's packer has no part in)
   flacenc_hip_frame_config plain = *cfg;
-  plain.qlpc.flags &= ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
+  plain.qlpc.flags = search_flags(h, plain.qlpc.flags) & ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = ensure(h, h->d_wk, n_frames * rows)) != FLACENC_HIP_OK) return rc;
@@ -1038,6 +1141,7 @@ int flacenc_hip_verify_config(const flacenc_hip_qlpc_config* cfg) {
   if ((cfg->flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER) && cfg->lpc_order > 15) return FLACENC_HIP_ERR_UNSUPPORTED;
   // the order search runs on the autocorrelation's R[]; the covariance-method estimator has none
   if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
+  if ((cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
   return FLACENC_HIP_OK;
 }
 
@@ -1046,6 +1150,34 @@ int flacenc_hip_window_weights(const flacenc_hip_qlpc_config* cfg, uint32_t bloc
   int rc = flacenc_hip_verify_config(cfg);
   if (rc != FLACENC_HIP_OK) return rc;
   window_weights(cfg->window_type, cfg->tukey_alpha, block_size, out);
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_set_lpc_windows(flacenc_hip_handle* h, const uint32_t* types, const float* alphas,
+                                const uint32_t* starts, const uint32_t* ends, uint32_t n_extra) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (n_extra > FLACENC_HIP_MAX_LPC_WINDOWS - 1 || (n_extra > 0 && (!types || !alphas || !starts || !ends))) {
+    h->last_error = "flacenc_hip_set_lpc_windows: at most 7 extra windows, arrays required";
+    return FLACENC_HIP_ERR_BAD_CONFIG;
+  }
+  std::vector<LpcWindow> list;
+  for (uint32_t i = 0; i < n_extra; ++i) {
+    if (!lpc_window_ok(types[i], alphas[i], starts[i], ends[i])) {
+      h->last_error = "flacenc_hip_set_lpc_windows: unknown type, alpha outside [0, 1], or a piece outside 0 <= start < "
+                      "end <= 65536";
+      return FLACENC_HIP_ERR_BAD_CONFIG;
+    }
+    list.push_back(LpcWindow{types[i], alphas[i], starts[i], ends[i]});
+  }
+  h->lpc_windows.swap(list);  // (the weights already cached stay until flacenc_hip_destroy)
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,
+                                   float* out) {
+  if (!lpc_window_ok(type, alpha, start, end)) return FLACENC_HIP_ERR_BAD_CONFIG;
+  if (block_size > FLACENC_HIP_MAX_BLOCK_SIZE || (!out && block_size > 0)) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  lpc_window_weights(type, alpha, start, end, block_size, out);
   return FLACENC_HIP_OK;
 }
 
@@ -1400,16 +1532,14 @@ int flacenc_hip_encode_frames_async(flacenc_hip_handle* h, const flacenc_hip_fra
   }
   if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
   // too_short (coding.rs:396): neither fixed_lpc nor estimated_qlpc is tried; Constant or Verbatim
-  flacenc_hip_frame_config short_cfg;
-  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) {
-    short_cfg = *cfg;
-    short_cfg.use_fixed = short_cfg.use_lpc = 0;
-    cfg = &short_cfg;
-  }
+  flacenc_hip_frame_config short_cfg = *cfg;
+  short_cfg.qlpc.flags = search_flags(h, cfg->qlpc.flags);
+  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) short_cfg.use_fixed = short_cfg.use_lpc = 0;
+  cfg = &short_cfg;
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // FLACENC_HIP_FLAG_ORDER_SEARCH: the candidate batches + channel_decide_kernel for every shape
-  if (!((cfg->qlpc.flags & FLACENC_HIP_FLAG_ORDER_SEARCH) && cfg->use_lpc)) {
+  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: the candidate batches + channel_decide_kernel for every shape
+  if (!(lpc_search(cfg->qlpc.flags) && cfg->use_lpc)) {
     // block size 4096, order <= 12: one fused kernel, a wave per channel (analysis, fixed-LPC
     // candidate, encode_subframe's choice, only the chosen residual written)
     uint32_t glog = 0;
@@ -2559,12 +2689,10 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   // too_short (coding.rs:396): neither fixed_lpc nor estimated_qlpc is tried; Constant or Verbatim
-  flacenc_hip_frame_config short_cfg;
-  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) {
-    short_cfg = *cfg;
-    short_cfg.use_fixed = short_cfg.use_lpc = 0;
-    cfg = &short_cfg;
-  }
+  flacenc_hip_frame_config short_cfg = *cfg;
+  short_cfg.qlpc.flags = search_flags(h, cfg->qlpc.flags);
+  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) short_cfg.use_fixed = short_cfg.use_lpc = 0;
+  cfg = &short_cfg;
   uint32_t fixed_group_log2 = 0;
   bool fixed_composite = false;
   if (cfg->use_fixed) {
@@ -2651,8 +2779,9 @@ static int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_fr
   bool want_fused = false;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_FUSED_PACK) want_fused = true;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_TWO_STAGE_PACK) want_fused = false;
-  // FLACENC_HIP_FLAG_ORDER_SEARCH: the candidate batches + frame_decide_kernel for every shape (FUSED_PACK ignored)
-  const bool order_search = (cfg->qlpc.flags & FLACENC_HIP_FLAG_ORDER_SEARCH) != 0 && cfg->use_lpc;
+  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: the candidate batches + frame_decide_kernel for every shape
+  // (FUSED_PACK ignored)
+  const bool order_search = lpc_search(cfg->qlpc.flags) && cfg->use_lpc;
   if (pack && want_fused && !fixed_composite && !order_search && block_size == 4096 && flacenc_hip::wave_kernel_eligible(a)) {
     const size_t bound = flacenc_hip_stereo_frame_bytes_bound(block_size, bits_per_sample);
     flacenc_hip::FramePackArgs pa{};

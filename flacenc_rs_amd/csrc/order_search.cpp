@@ -1,7 +1,8 @@
-// order_search.cpp -- FLACENC_HIP_FLAG_ORDER_SEARCH: per QLPC candidate subframe, the LPC order
-// 1..P whose exact Lpc::count_bits is smallest.  Every candidate comes from the one R[0..P] the reference-order pass
-// produces: levinson_quantize at order o reads lags 0..o only, so candidate o is bit for bit the order-o run, and
-// candidate P is the unflagged FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER record.
+// order_search.cpp -- FLACENC_HIP_FLAG_ORDER_SEARCH and FLACENC_HIP_FLAG_WINDOW_SEARCH (DESIGN.md sections 4.10, 4.11):
+// per QLPC candidate subframe, the candidate (window j, order o) whose exact Lpc::count_bits is smallest.  Every candidate
+// of window j comes from the one R_j[0..P] the reference-order pass produces under that window: levinson_quantize at order
+// o reads lags 0..o only, so candidate (j, o) is bit for bit the order-o run under window j, and candidate (0, P) is the
+// unflagged FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER record.  ORDER_SEARCH alone is the W = 1 case.
 #include "order_search.h"
 
 #include "acorr_reference.h"
@@ -29,11 +30,12 @@ struct OrderSearchArgs {
   const uint8_t* bps;
   uint32_t bps_uniform;
   uint32_t lpc_order;
+  uint32_t n_cand;      // C candidates per subframe
   uint32_t precision;
   uint32_t max_rice_parameter;
   uint32_t rice_finest_only;
-  const int32_t* cand;  // [n][P][36]
-  uint32_t* best;       // [n]: chosen order, 0 = no candidate with status 0
+  const int32_t* cand;  // [n][C][36]
+  uint32_t* best;       // [n]: chosen candidate + 1, 0 = no candidate with status 0
   int32_t* residual;    // zig-zag rows of the order under test when they do not fit the LDS (the output rows; stage 3
   size_t residual_stride;  // overwrites them)
 };
@@ -61,18 +63,29 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// candidate o of subframe sf at [(sf * P + o - 1) * 36]: levinson_quantize on R[0..o] (lpc.rs:633-705, 273-302)
+// Candidate c = j * Pc + (o - 1 - (P - Pc)) of a subframe: window j, order o (Pc = P orders per window with the order
+// search, else 1: order P only).  R_j of subframe sf at racc[(sf * W + j) * 33].
+__device__ __forceinline__ void candidate_of(uint32_t c, uint32_t P, uint32_t Pc, uint32_t* j, int* o) {
+  *j = c / Pc;
+  *o = (int)(P - Pc + 1u + c % Pc);
+}
+
+// candidate c of subframe sf at [(sf * C + c) * 36]: levinson_quantize on R_j[0..o] (lpc.rs:633-705, 273-302)
 template <int MAXP>
 __global__ void __launch_bounds__(64) order_levinson_kernel(const double* __restrict__ racc, uint32_t n_subframes,
-                                                             uint32_t P, uint32_t precision, int32_t* __restrict__ cand) {
+                                                             uint32_t W, uint32_t P, uint32_t Pc, uint32_t precision,
+                                                             int32_t* __restrict__ cand) {
   const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
-  if (i >= (size_t)n_subframes * P) return;
-  const size_t sf = i / P;
-  const int o = (int)(i % P) + 1;
+  const uint32_t C = W * Pc;
+  if (i >= (size_t)n_subframes * C) return;
+  const size_t sf = i / C;
+  uint32_t j;
+  int o;
+  candidate_of((uint32_t)(i % C), P, Pc, &j, &o);
   double coef[MAXP];
   int32_t qc[MAXP];
   int order, shift;
-  const int status = levinson_quantize<MAXP>(racc + sf * 33, o, (int)precision, coef, qc, &order, &shift);
+  const int status = levinson_quantize<MAXP>(racc + (sf * W + j) * 33, o, (int)precision, coef, qc, &order, &shift);
   int32_t* pr = cand + i * kCandWords;
 #pragma unroll
   for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
@@ -83,19 +96,26 @@ __global__ void __launch_bounds__(64) order_levinson_kernel(const double* __rest
   pr[35] = 0;
 }
 
-// the chosen order's predictor record for the stage-3 kernels, and its unquantised coefficients (zeros from o on)
+// the chosen candidate's predictor record for the stage-3 kernels, its unquantised coefficients (zeros from o on) and
+// its window's R[0..P] (zeros above P)
 template <int MAXP>
-__global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict__ racc, uint32_t n_subframes, uint32_t P,
-                                                         uint32_t precision, const uint32_t* __restrict__ best,
-                                                         int32_t* __restrict__ pred, double* __restrict__ lpc_coefs) {
+__global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict__ racc, uint32_t n_subframes, uint32_t W,
+                                                         uint32_t P, uint32_t Pc, uint32_t precision,
+                                                         const uint32_t* __restrict__ best, int32_t* __restrict__ pred,
+                                                         double* __restrict__ lpc_coefs, double* __restrict__ autocorr) {
   const size_t sf = (size_t)blockIdx.x * 64u + threadIdx.x;
   if (sf >= n_subframes) return;
-  int o = (int)best[sf];
-  if (o < 1 || o > (int)P) o = (int)P;  // no candidate with status 0: the order-P record, status included
+  const uint32_t b = best[sf];
+  // no candidate with status 0: candidate (0, P), status included
+  const uint32_t c = (b >= 1u && b <= W * Pc) ? b - 1u : Pc - 1u;
+  uint32_t j;
+  int o;
+  candidate_of(c, P, Pc, &j, &o);
+  const double* rj = racc + (sf * W + j) * 33;
   double coef[MAXP];
   int32_t qc[MAXP];
   int order, shift;
-  const int status = levinson_quantize<MAXP>(racc + sf * 33, o, (int)precision, coef, qc, &order, &shift);
+  const int status = levinson_quantize<MAXP>(rj, o, (int)precision, coef, qc, &order, &shift);
   int32_t* pr = pred + sf * kCandWords;
 #pragma unroll
   for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
@@ -109,9 +129,12 @@ __global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict
     for (int k = 0; k < MAXP; ++k) lpc_coefs[sf * 32 + k] = (k < o && status == 0) ? coef[k] : 0.0;
     for (int k = MAXP; k < 32; ++k) lpc_coefs[sf * 32 + k] = 0.0;
   }
+  if (autocorr) {
+    for (int k = 0; k < 33; ++k) autocorr[sf * 33 + k] = k <= (int)P ? rj[k] : 0.0;
+  }
 }
 
-// One workgroup per subframe: the samples staged in LDS once, then for every candidate order with status 0 the residual
+// One workgroup per subframe: the samples staged in LDS once, then for every candidate (j, o) with status 0 the residual
 // (compute_error, lpc.rs:359-390), the finest partitions' Rice bit tables over a parameter window and the reference's
 // merge / minimiser walk (PrcParameterFinder::find, rice.rs:246-298) -> the exact Lpc::count_bits (bitrepr.rs:492-499,
 // 533-544) as the candidate's key.  LDS_U: the zig-zag residual row of the order under test lives in LDS (blocks up to
@@ -138,7 +161,6 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
   const int wave = tid >> 6;
   const uint32_t sf = blockIdx.x;
   const int n = (int)a.block_size;
-  const int P = (int)a.lpc_order;
   const int fo = finest_order(n);
   const int nparts = 1 << fo;
   const int psize = n >> fo;
@@ -192,9 +214,10 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
                                        : (unsigned long long)(a.bps_uniform + (role == 3 ? 1u : 0u));
 
   unsigned long long best_key = ~0ull;
-  uint32_t best_o = 0;
-  for (int o = 1; o <= P; ++o) {
-    const int32_t* pr = a.cand + ((size_t)sf * (size_t)P + (size_t)(o - 1)) * kCandWords;
+  uint32_t best_c = 0;
+  const int C = (int)a.n_cand;
+  for (int cand = 0; cand < C; ++cand) {
+    const int32_t* pr = a.cand + ((size_t)sf * (size_t)C + (size_t)cand) * kCandWords;
     if (pr[34] != 0) continue;  // (uniform: every thread reads the same record)
     const int q = pr[32];
     const int shift = pr[33];
@@ -382,104 +405,152 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
                                        (unsigned long long)(n - q) + (sum_p * (unsigned long long)pb - wq * psel[0]);
       key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + rbits;
     }
-    if (key < best_key) {  // strict: the lower order wins a tie
+    if (key < best_key) {  // strict: the lower candidate -- window, then order -- wins a tie
       best_key = key;
-      best_o = (uint32_t)o;
+      best_c = (uint32_t)cand + 1u;
     }
   }
-  if (tid == 0) a.best[sf] = best_o;
+  if (tid == 0) a.best[sf] = best_c;
 }
 
+// One slice of subframes of the flagged batch: racc [n][W][33], cand [n][C][36], best [n] in the scratch; pred, lpc_coefs and
+// autocorr already offset to the slice's first subframe.
+struct SliceArgs {
+  const double* racc;
+  int32_t* cand;
+  uint32_t* best;
+  int32_t* pred;
+  double* lpc_coefs;
+  double* autocorr;
+  uint32_t n_subframes;
+  uint32_t W, P, Pc, precision;
+};
+
 template <int MAXP>
-hipError_t launch_levinson_and_pick(bool pick, const double* racc, const QlpcKernelArgs& a, int32_t* cand, uint32_t* best,
-                                    int32_t* pred, hipStream_t stream) {
+hipError_t launch_levinson_and_pick(bool pick, const SliceArgs& s, hipStream_t stream) {
   if (!pick) {
-    const size_t items = (size_t)a.n_subframes * a.lpc_order;
-    hipLaunchKernelGGL(order_levinson_kernel<MAXP>, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, racc,
-                       a.n_subframes, a.lpc_order, a.precision, cand);
+    const size_t items = (size_t)s.n_subframes * s.W * s.Pc;
+    hipLaunchKernelGGL(order_levinson_kernel<MAXP>, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, s.racc,
+                       s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand);
   } else {
-    hipLaunchKernelGGL(order_pick_kernel<MAXP>, dim3((a.n_subframes + 63) / 64), dim3(64), 0, stream, racc, a.n_subframes,
-                       a.lpc_order, a.precision, best, pred, a.lpc_coefs);
+    hipLaunchKernelGGL(order_pick_kernel<MAXP>, dim3((s.n_subframes + 63) / 64), dim3(64), 0, stream, s.racc, s.n_subframes,
+                       s.W, s.P, s.Pc, s.precision, s.best, s.pred, s.lpc_coefs, s.autocorr);
   }
   return hipGetLastError();
 }
 
-hipError_t levinson_bucket(bool pick, const double* racc, const QlpcKernelArgs& a, int32_t* cand, uint32_t* best,
-                           int32_t* pred, hipStream_t stream) {
-  const uint32_t P = a.lpc_order;
-  if (P <= 8) return launch_levinson_and_pick<8>(pick, racc, a, cand, best, pred, stream);
-  if (P <= 12) return launch_levinson_and_pick<12>(pick, racc, a, cand, best, pred, stream);
-  if (P <= 16) return launch_levinson_and_pick<16>(pick, racc, a, cand, best, pred, stream);
-  if (P <= 24) return launch_levinson_and_pick<24>(pick, racc, a, cand, best, pred, stream);
-  return launch_levinson_and_pick<32>(pick, racc, a, cand, best, pred, stream);
+hipError_t levinson_bucket(bool pick, const SliceArgs& s, hipStream_t stream) {
+  const uint32_t P = s.P;
+  if (P <= 8) return launch_levinson_and_pick<8>(pick, s, stream);
+  if (P <= 12) return launch_levinson_and_pick<12>(pick, s, stream);
+  if (P <= 16) return launch_levinson_and_pick<16>(pick, s, stream);
+  if (P <= 24) return launch_levinson_and_pick<24>(pick, s, stream);
+  return launch_levinson_and_pick<32>(pick, s, stream);
+}
+
+size_t bytes_per_subframe(uint32_t lpc_order, const SearchShape& shape) {
+  const size_t W = shape.n_windows, C = W * (shape.search_orders ? lpc_order : 1u);
+  return W * 33 * sizeof(double) + C * kCandWords * 4 + 4;
+}
+
+// subframes per slice: as many as kSearchScratchCap holds, whole stereo frames (a multiple of 4), at least 4
+size_t slice_subframes(size_t n, uint32_t lpc_order, const SearchShape& shape) {
+  size_t k = kSearchScratchCap / bytes_per_subframe(lpc_order, shape);
+  k = k < 4 ? 4 : (k & ~static_cast<size_t>(3));
+  return n < k ? n : k;
 }
 
 }  // namespace
 
-size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order) {
-  return static_cast<size_t>(n_subframes) * (static_cast<size_t>(lpc_order) * kCandWords * 4 + 4);
+size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order, const SearchShape& shape) {
+  return slice_subframes(n_subframes, lpc_order, shape) * bytes_per_subframe(lpc_order, shape);
 }
 
-hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly, void* scratch,
-                               hipStream_t stream) {
+hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly,
+                               const SearchShape& shape, void* scratch, hipStream_t stream) {
   if (a.n_subframes == 0) return hipSuccess;
   if (a.split_scratch == nullptr || scratch == nullptr || a.lpc_order < 1 || a.lpc_order > 32 || a.block_size < 64 ||
-      a.block_size > 32767)
+      a.block_size > 32767 || shape.n_windows < 1 || shape.n_windows > kMaxSearchWindows)
     return hipErrorInvalidValue;
   const size_t n = a.n_subframes;
-  double* racc = a.autocorr ? a.autocorr : reinterpret_cast<double*>(a.split_scratch);
+  const uint32_t W = shape.n_windows;
+  const uint32_t Pc = shape.search_orders ? a.lpc_order : 1u;
+  const uint32_t C = W * Pc;
+  const size_t slice = slice_subframes(n, a.lpc_order, shape);
   int32_t* pred = reinterpret_cast<int32_t*>(reinterpret_cast<double*>(a.split_scratch) + n * 33);
-  int32_t* cand = static_cast<int32_t*>(scratch);
-  uint32_t* best = reinterpret_cast<uint32_t*>(cand + n * a.lpc_order * kCandWords);
+  double* racc = static_cast<double*>(scratch);
+  int32_t* cand = reinterpret_cast<int32_t*>(racc + slice * W * 33);
+  uint32_t* best = reinterpret_cast<uint32_t*>(cand + slice * C * kCandWords);
 
-  // 1. R[0..P] in the stable build's order (or nightly's)
-  AcorrRefArgs r{};
-  r.samples = a.samples;
-  r.stride = a.stride;
-  r.block_size = a.block_size;
-  r.n_subframes = a.n_subframes;
-  r.stereo = a.stereo;
-  r.window = a.window;
-  r.lpc_order = a.lpc_order;
-  r.nightly = nightly;
-  r.out = racc;
-  hipError_t err = launch_acorr_reference(r, stream);
-  if (err != hipSuccess) return err;
-  // 2. every candidate's predictor
-  if ((err = levinson_bucket(false, racc, a, cand, best, pred, stream)) != hipSuccess) return err;
-  // 3. the search
-  OrderSearchArgs s{};
-  s.samples = a.samples;
-  s.stride = a.stride;
-  s.block_size = a.block_size;
-  s.n_subframes = a.n_subframes;
-  s.stereo = a.stereo;
-  s.bps = a.bps;
-  s.bps_uniform = a.bps_uniform;
-  s.lpc_order = a.lpc_order;
-  s.precision = a.precision;
-  s.max_rice_parameter = a.max_rice_parameter;
-  s.rice_finest_only = a.rice_finest_only;
-  s.cand = cand;
-  s.best = best;
-  s.residual = a.residual;
-  s.residual_stride = a.residual_stride;
   const bool lds_u = search_lds_bytes(a.block_size, true) <= 160 * 1024;
   const size_t smem = search_lds_bytes(a.block_size, lds_u);
   if (smem > 160 * 1024) return hipErrorInvalidValue;
+  if (!lds_u && a.residual == nullptr) return hipErrorInvalidValue;
+  hipError_t err;
   if (lds_u) {
     static DynamicLdsOptIn opt_in;
     if ((err = opt_in.ensure(reinterpret_cast<const void*>(order_search_kernel<true>), smem)) != hipSuccess) return err;
-    hipLaunchKernelGGL(order_search_kernel<true>, dim3(a.n_subframes), dim3(kOsThreads), smem, stream, s);
   } else {
-    if (a.residual == nullptr) return hipErrorInvalidValue;
     static DynamicLdsOptIn opt_in;
     if ((err = opt_in.ensure(reinterpret_cast<const void*>(order_search_kernel<false>), smem)) != hipSuccess) return err;
-    hipLaunchKernelGGL(order_search_kernel<false>, dim3(a.n_subframes), dim3(kOsThreads), smem, stream, s);
   }
-  if ((err = hipGetLastError()) != hipSuccess) return err;
-  // 4. the chosen order's predictor record (+ unquantised coefficients)
-  if ((err = levinson_bucket(true, racc, a, cand, best, pred, stream)) != hipSuccess) return err;
+  for (size_t sf0 = 0; sf0 < n; sf0 += slice) {
+    const uint32_t ns = static_cast<uint32_t>(n - sf0 < slice ? n - sf0 : slice);
+    // (stereo slices are whole frames: frame f's two channels at samples + 2 f stride)
+    const int32_t* samples = a.samples + (a.stereo ? sf0 / 2 : sf0) * a.stride;
+    // 1. R[0..P] of every window in the stable build's order (or nightly's)
+    for (uint32_t j = 0; j < W; ++j) {
+      AcorrRefArgs r{};
+      r.samples = samples;
+      r.stride = a.stride;
+      r.block_size = a.block_size;
+      r.n_subframes = ns;
+      r.stereo = a.stereo;
+      r.window = shape.windows[j];
+      r.lpc_order = a.lpc_order;
+      r.nightly = nightly;
+      r.out = racc + j * 33;
+      r.out_stride = W * 33;
+      if ((err = launch_acorr_reference(r, stream)) != hipSuccess) return err;
+    }
+    SliceArgs sl{};
+    sl.racc = racc;
+    sl.cand = cand;
+    sl.best = best;
+    sl.pred = pred + sf0 * kCandWords;
+    sl.lpc_coefs = a.lpc_coefs ? a.lpc_coefs + sf0 * 32 : nullptr;
+    sl.autocorr = a.autocorr ? a.autocorr + sf0 * 33 : nullptr;
+    sl.n_subframes = ns;
+    sl.W = W;
+    sl.P = a.lpc_order;
+    sl.Pc = Pc;
+    sl.precision = a.precision;
+    // 2. every candidate's predictor
+    if ((err = levinson_bucket(false, sl, stream)) != hipSuccess) return err;
+    // 3. the search
+    OrderSearchArgs s{};
+    s.samples = samples;
+    s.stride = a.stride;
+    s.block_size = a.block_size;
+    s.n_subframes = ns;
+    s.stereo = a.stereo;
+    s.bps = a.bps ? a.bps + sf0 : nullptr;
+    s.bps_uniform = a.bps_uniform;
+    s.lpc_order = a.lpc_order;
+    s.n_cand = C;
+    s.precision = a.precision;
+    s.max_rice_parameter = a.max_rice_parameter;
+    s.rice_finest_only = a.rice_finest_only;
+    s.cand = cand;
+    s.best = best;
+    s.residual = a.residual ? a.residual + sf0 * a.residual_stride : nullptr;
+    s.residual_stride = a.residual_stride;
+    if (lds_u) hipLaunchKernelGGL(order_search_kernel<true>, dim3(ns), dim3(kOsThreads), smem, stream, s);
+    else hipLaunchKernelGGL(order_search_kernel<false>, dim3(ns), dim3(kOsThreads), smem, stream, s);
+    if ((err = hipGetLastError()) != hipSuccess) return err;
+    // 4. the chosen candidate's predictor record (+ unquantised coefficients, + its window's R[])
+    if ((err = levinson_bucket(true, sl, stream)) != hipSuccess) return err;
+  }
   // 5. records and residual rows by the unflagged stage-3 kernels (as behind direct_mse_kernel)
   QlpcKernelArgs s3 = a;
   s3.lpc_stage = 3;

@@ -1,5 +1,7 @@
-// order_search.h -- FLACENC_HIP_FLAG_ORDER_SEARCH: the LPC order of every QLPC candidate subframe chosen by an exhaustive
-// search over orders 1..P, in front of the unflagged stage-3 residual kernels.
+// order_search.h -- FLACENC_HIP_FLAG_ORDER_SEARCH and FLACENC_HIP_FLAG_WINDOW_SEARCH: the LPC predictor of every QLPC
+// candidate subframe chosen by an exhaustive search over candidates (window j, order o) -- the analysis windows 0..W-1
+// and, with the order search, every order 1..P (DESIGN.md sections 4.10, 4.11) -- in front of the unflagged stage-3
+// residual kernels.
 #ifndef FLACENC_HIP_ORDER_SEARCH_H_
 #define FLACENC_HIP_ORDER_SEARCH_H_
 #include <hip/hip_runtime.h>
@@ -10,19 +12,38 @@
 
 namespace flacenc_hip {
 
-// Handle scratch of one flagged candidate batch of n subframes at lpc_order P: the P candidate predictor records
-// ([n][P][36] int32: qc[32], order, shift, status, 0) and the chosen order per subframe ([n] uint32).
-size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order);
+constexpr uint32_t kMaxSearchWindows = 8;  // FLACENC_HIP_MAX_LPC_WINDOWS
+// Bound of the search scratch of one call: steps 1..4 below run over slices of at most this many bytes' worth of
+// subframes (the handle's growth slack on top keeps the allocation below 1 GiB).
+constexpr size_t kSearchScratchCap = static_cast<size_t>(768) << 20;
 
-// The whole flagged pipeline of a candidate batch `a` (split scratch attached; autocorr / lpc_coefs as the caller asked):
-//   1. R[0..P] in the stable build's order (nightly's with `nightly`) into a.autocorr or the split scratch;
-//   2. order_levinson_kernel: levinson_quantize at every order o = 1..P, one lane per (subframe, o);
-//   3. order_search_kernel: one workgroup per subframe, every candidate's residual and exact Rice search -> the order whose
-//      Lpc::count_bits is smallest (ties: the lower order; no candidate with status 0: order P);
-//   4. order_pick_kernel: the chosen order's predictor record (and unquantised coefficients into a.lpc_coefs);
-//   5. the unflagged stage-3 kernels write the records and residual rows from that predictor.
-hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly, void* scratch,
-                               hipStream_t stream);
+// The candidates of one flagged candidate batch: W analysis windows (window 0 the config's), and the orders searched
+// per window (P with FLACENC_HIP_FLAG_ORDER_SEARCH, else 1: lpc_order only).
+struct SearchShape {
+  const float* windows[kMaxSearchWindows];  // device weight tables (32 leading pad floats), nullptr = all ones
+  uint32_t n_windows;                       // W, 1..8
+  uint32_t search_orders;                   // 1: orders 1..P per window; 0: order P only
+};
+
+// Handle scratch of a flagged candidate batch of n subframes at lpc_order P: per subframe R[0..32] of every window
+// ([W][33] f64, 264 B each), the C = W x (P or 1) candidate predictor records ([C][36] int32: qc[32], order, shift,
+// status, 0; 144 B each) and the chosen candidate (uint32) -- for the largest slice the call runs, so never above
+// kSearchScratchCap.
+size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order, const SearchShape& shape);
+
+// The whole flagged pipeline of a candidate batch `a` (split scratch attached; autocorr / lpc_coefs as the caller asked),
+// steps 1..4 per slice of subframes:
+//   1. R[0..P] of every window in the stable build's order (nightly's with `nightly`);
+//   2. order_levinson_kernel: levinson_quantize at every candidate (j, o), one lane per (subframe, candidate);
+//   3. order_search_kernel: one workgroup per subframe, every candidate's residual and exact Rice search -> the
+//      candidate whose Lpc::count_bits is smallest (ties: the lower window, then the lower order; no candidate with
+//      status 0: (0, P));
+//   4. order_pick_kernel: the chosen candidate's predictor record (and unquantised coefficients into a.lpc_coefs, its
+//      window's R[] into a.autocorr);
+// then over the whole batch
+//   5. the unflagged stage-3 kernels write the records and residual rows from those predictors.
+hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly,
+                               const SearchShape& shape, void* scratch, hipStream_t stream);
 
 }  // namespace flacenc_hip
 #endif

@@ -487,12 +487,17 @@ class HipContext {
   }
   HipContext(const HipContext&) = delete;
   HipContext& operator=(const HipContext&) = delete;
-  HipContext(HipContext&& o) noexcept : h_(o.h_), sum_order_(o.sum_order_) { o.h_ = nullptr; }  // std::vector<HipContext>: one per GPU
+  HipContext(HipContext&& o) noexcept  // std::vector<HipContext>: one per GPU
+      : h_(o.h_), sum_order_(o.sum_order_), order_search_(o.order_search_), window_search_(o.window_search_) {
+    o.h_ = nullptr;
+  }
   HipContext& operator=(HipContext&& o) noexcept {
     if (this != &o) {
       if (h_) flacenc_hip_destroy(h_);
       h_ = o.h_;
       sum_order_ = o.sum_order_;
+      order_search_ = o.order_search_;
+      window_search_ = o.window_search_;
       o.h_ = nullptr;
     }
     return *this;
@@ -517,8 +522,18 @@ class HipContext {
   // SubFrame::Lpc of the chosen order); off by default
   void set_order_search(bool on) { order_search_ = on; }
   bool order_search() const { return order_search_; }
+  // FLACENC_HIP_FLAG_WINDOW_SEARCH: every LPC subframe analysed under the config's window and the handle's extra windows
+  // (set_lpc_windows; a fresh handle holds the header's default list), the shortest kept; off by default
+  void set_window_search(bool on) { window_search_ = on; }
+  bool window_search() const { return window_search_; }
+  // the extra windows, (type, alpha, start, end) entry by entry (flacenc_hip_set_lpc_windows; n_extra <= 7)
+  void set_lpc_windows(const uint32_t* types, const float* alphas, const uint32_t* starts, const uint32_t* ends,
+                       uint32_t n_extra) {
+    if (flacenc_hip_set_lpc_windows(h_, types, alphas, starts, ends, n_extra) != FLACENC_HIP_OK)
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+  }
   uint32_t sum_order_flags(size_t lpc_order) const {
-    const uint32_t os = order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u;
+    const uint32_t os = (order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u) | (window_search_ ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u);
     // (the mirror consumes integers only: certified shapes keep their own order, INTEGER_PARITY_ONLY)
     if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY | os;
     if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER | os;
@@ -558,6 +573,7 @@ class HipContext {
   flacenc_hip_handle* h_ = nullptr;
   SumOrder sum_order_ = SumOrder::Canonical;
   bool order_search_ = false;
+  bool window_search_ = false;
 };
 
 // Staging memory for the host-pointer entry points: page-locked (flacenc_hip_host_alloc), so that the

@@ -77,6 +77,16 @@ extern "C" {
 /* config::Window, src/config.rs:344-359 */
 #define FLACENC_HIP_WINDOW_RECTANGLE 0
 #define FLACENC_HIP_WINDOW_TUKEY 1
+/* Extra analysis windows of FLACENC_HIP_FLAG_WINDOW_SEARCH only (flacenc_hip_set_lpc_windows); the config's
+ * window_type keeps rejecting them.  Pieces of a block of n samples: s = (start * n) >> 16, e = (end * n) >> 16 in 64-bit
+ * integers; T(m) = the reference's Tukey weights of length m with the entry's alpha (lpc::window_weights, src/lpc.rs:96-120),
+ * all zeros for m < 2.
+ *   PARTIAL_TUKEY:  T(e - s) on [s, e), zero elsewhere;
+ *   PUNCHOUT_TUKEY: T(s) on [0, s), zero on [s, e), T(n - e) on [e, n). */
+#define FLACENC_HIP_WINDOW_PARTIAL_TUKEY 2
+#define FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY 3
+#define FLACENC_HIP_MAX_LPC_WINDOWS 8      /* the config's window + at most 7 extra windows */
+#define FLACENC_HIP_WINDOW_UNIT 65536      /* start / end of an extra window: fractions of the block in 1/65536 */
 
 #define FLACENC_HIP_FLAG_ALLOW_ORDER_32 1u
 /* Build extension, NOT a reference mode (the reference always runs the exhaustive search,
@@ -194,6 +204,35 @@ extern "C" {
  * handle until flacenc_hip_destroy. */
 #define FLACENC_HIP_FLAG_ORDER_SEARCH 1024u
 
+/* LPC window search (libFLAC's apodization), an extension like FLACENC_HIP_FLAG_ORDER_SEARCH: every LPC candidate subframe
+ * with lpc_order = P (a role, a channel, a row of a candidate batch, a shifted row under WASTED_BITS) is analysed under
+ * W windows and the shortest result is coded.  Window 0 is the config's (window_type, tukey_alpha); windows 1 .. W-1 are
+ * the handle's extra windows (flacenc_hip_set_lpc_windows; W <= FLACENC_HIP_MAX_LPC_WINDOWS).  A fresh handle holds five:
+ *   PARTIAL_TUKEY(0.2) [0, 36044), PARTIAL_TUKEY(0.2) [29492, 65536), PUNCHOUT_TUKEY(0.2) [0, 21845),
+ *   PUNCHOUT_TUKEY(0.2) [21845, 43690), PUNCHOUT_TUKEY(0.2) [43690, 65536)   (in FLACENC_HIP_WINDOW_UNIT)
+ * -- shaped after libFLAC's partial_tukey(2) and punchout_tukey(3), not its weights.
+ *   - R_j[0..P] is the autocorrelation of the signal under window j in the stable build's order (the simd-nightly build's
+ *     with NIGHTLY_SUM_ORDER); CANONICAL_SUM_ORDER and INTEGER_PARITY_ONLY have no effect under this flag;
+ *   - the candidates are (j, P) for every window j -- with FLACENC_HIP_FLAG_ORDER_SEARCH (j, o) for every j and o = 1..P --
+ *     each built from R_j as ORDER_SEARCH builds one from R[] (status checks, quantize_parameters, residual, exhaustive
+ *     Rice search), keyed by the exact Lpc::count_bits;
+ *   - the candidate with status 0 and the smallest key is coded, ties to the lower window, then the lower order; if none
+ *     has status 0, candidate (0, P), status included.
+ * The record and residual row are the winner's, `autocorr` its window's R[0..P], `lpc_coefs` its unquantised coefficients
+ * with zeros from o on.  Candidate (0, P) is the REFERENCE_SUM_ORDER record (NIGHTLY_SUM_ORDER's under that flag), so no
+ * flagged record or frame is longer than that call's -- nor, with ORDER_SEARCH as well, than the ORDER_SEARCH call's.  With
+ * no extra window every output and launch is that of the same call with REFERENCE_SUM_ORDER (or NIGHTLY_SUM_ORDER) in
+ * this flag's place, or with ORDER_SEARCH set of the ORDER_SEARCH call.  The extra-window list has no effect without the
+ * flag.  Honoured where ORDER_SEARCH is (candidate batches, every frame-level call; composes with WASTED_BITS; FUSED_PACK
+ * ignored; flacenc_hip_fixed_lpc_batch accepts and ignores it); use_direct_mse with this flag answers
+ * FLACENC_HIP_ERR_UNSUPPORTED.  No host synchronisation: a flagged call is capturable wherever the ORDER_SEARCH call is
+ * (the first call at a new block size builds the extra windows' weights, as every first call does the config's).
+ * Scratch: 264 B per (subframe, window) for R[] and 144 B per (subframe, candidate); the handle runs the search over slices
+ * of subframes that keep it at or below 768 MiB (1 GiB with the handle's growth slack) whatever n, W and P are -- this
+ * bound covers FLACENC_HIP_FLAG_ORDER_SEARCH as well.  Extra windows' weights (4 bytes per sample and block size) stay in
+ * the handle's window cache until flacenc_hip_destroy. */
+#define FLACENC_HIP_FLAG_WINDOW_SEARCH 2048u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1
@@ -266,6 +305,18 @@ int flacenc_hip_verify_config(const flacenc_hip_qlpc_config* cfg);
 /* lpc::window_weights (src/lpc.rs:96-120), evaluated on the host in f32 with
  * libm cosf exactly as the reference does; this is the table the kernels use. */
 int flacenc_hip_window_weights(const flacenc_hip_qlpc_config* cfg, uint32_t block_size, float* out);
+
+/* FLACENC_HIP_FLAG_WINDOW_SEARCH: the handle's extra analysis windows, entry i = (types[i], alphas[i], starts[i], ends[i]),
+ * n_extra <= FLACENC_HIP_MAX_LPC_WINDOWS - 1 (0: the config's window only).  FLACENC_HIP_ERR_BAD_CONFIG for an unknown
+ * type, an alpha outside [0, 1] (NaN included), for PARTIAL_ / PUNCHOUT_TUKEY start >= end or end > 65536, n_extra > 7,
+ * or NULL arrays with n_extra > 0; a rejected call leaves the list as it was.  start / end are ignored for RECTANGLE and
+ * TUKEY.  Takes effect for the calls enqueued after it; the list travels with no call that lacks the flag. */
+int flacenc_hip_set_lpc_windows(flacenc_hip_handle* h, const uint32_t* types, const float* alphas,
+                                const uint32_t* starts, const uint32_t* ends, uint32_t n_extra);
+/* The weights of one extra-window entry over a block of block_size (<= 32767) samples, on the host: no handle, no GPU.
+ * The same validation as flacenc_hip_set_lpc_windows (FLACENC_HIP_ERR_BAD_CONFIG). */
+int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,
+                                   float* out);
 
 /* ---- the hot path ----------------------------------------------------- */
 /*

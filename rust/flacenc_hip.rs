@@ -56,6 +56,15 @@ pub const FLAG_WASTED_BITS: u32 = 512;
 /// (smallest exact bit count, the lower order on a tie), on the stable build's autocorrelation.  The records stay
 /// ordinary `SubFrame::Lpc` of the chosen order, so `encode_with_fixed_block_size` may pass it.
 pub const FLAG_ORDER_SEARCH: u32 = 1024;
+/// `FLACENC_HIP_FLAG_WINDOW_SEARCH`: every LPC candidate is analysed under the config's window and the handle's extra
+/// windows (`flacenc_hip_set_lpc_windows`) and the shortest is coded.  The drop-in never sets it.
+pub const FLAG_WINDOW_SEARCH: u32 = 2048;
+/// Extra-window types of `FLAG_WINDOW_SEARCH` (the config's `window_type` keeps rejecting them), the most windows per
+/// subframe, and the unit of an extra window's `start` / `end`.
+pub const WINDOW_PARTIAL_TUKEY: u32 = 2;
+pub const WINDOW_PUNCHOUT_TUKEY: u32 = 3;
+pub const MAX_LPC_WINDOWS: u32 = 8;
+pub const WINDOW_UNIT: u32 = 65536;
 
 /// `flacenc_hip_qlpc_config` (include/flacenc_hip.h): the path's fields of `config::Qlpc` /
 /// `config::Prc` (`src/config.rs:271-288`, `211-214`).
@@ -269,6 +278,14 @@ extern "C" {
     pub fn flacenc_hip_device_count() -> c_int;
     /// `lpc::window_weights` (`src/lpc.rs:96-120`) as the kernels use it.
     pub fn flacenc_hip_window_weights(cfg: *const QlpcConfig, block_size: u32, out: *mut f32) -> c_int;
+    /// `FLAG_WINDOW_SEARCH`'s extra windows of a handle, as parallel arrays of `n_extra` (<= 7) entries.
+    pub fn flacenc_hip_set_lpc_windows(
+        h: *mut Handle, types: *const u32, alphas: *const f32, starts: *const u32, ends: *const u32, n_extra: u32,
+    ) -> c_int;
+    /// One extra-window entry's weights over a block, on the host.
+    pub fn flacenc_hip_lpc_window_weights(
+        window_type: u32, alpha: f32, start: u32, end: u32, block_size: u32, out: *mut f32,
+    ) -> c_int;
     pub fn flacenc_hip_stereo_qlpc_batch_async(
         h: *mut Handle, cfg: *const QlpcConfig, frames: *const i32, n_frames: usize, block_size: u32, stride: usize,
         bits_per_sample: u32, params: *mut SubframeParams, residual: *mut i32, residual_stride: usize,

@@ -8,6 +8,7 @@ MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-f
 frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
+                                  [--window-search]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -17,6 +18,8 @@ With --wasted-bits (FLACENC_HIP_FLAG_WASTED_BITS) a subframe whose samples all e
 them.
 With --order-search (FLACENC_HIP_FLAG_ORDER_SEARCH) every LPC subframe's order is the one of 1..--lpc-order whose exact
 bit count is smallest; the histogram of the chosen orders is printed.
+With --window-search (FLACENC_HIP_FLAG_WINDOW_SEARCH) every LPC subframe is also analysed under the default extra windows
+(partial and punch-out Tukey windows, _capi.DEFAULT_LPC_WINDOWS) and the shortest result is coded.
 """
 import argparse
 import hashlib
@@ -113,9 +116,13 @@ def main():
                     help="code subframes whose low bits are all zero at reduced width (FLACENC_HIP_FLAG_WASTED_BITS)")
     ap.add_argument("--order-search", action="store_true",
                     help="search the LPC order of every subframe (FLACENC_HIP_FLAG_ORDER_SEARCH)")
+    ap.add_argument("--window-search", action="store_true",
+                    help="analyse every LPC subframe under the config's window and the default extra windows, keep the "
+                         "shortest (FLACENC_HIP_FLAG_WINDOW_SEARCH); composes with --order-search")
     ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
     flags = (_capi.FLAG_WASTED_BITS if args.wasted_bits else 0) | (_capi.FLAG_ORDER_SEARCH if args.order_search else 0)
+    flags |= _capi.FLAG_WINDOW_SEARCH if args.window_search else 0  # (a fresh handle holds DEFAULT_LPC_WINDOWS)
     n = 4096
     if len(args.paths) == 2:
         with wave.open(args.paths[0], "rb") as w:
