@@ -1,6 +1,7 @@
-"""Worst-case material shared by the parity and order-search suites, the record check of the flagged candidate batch
-against tests/order_model.py, and predicates saying which branch of order_search_kernel a subframe reaches (computed
-from the model on the CPU, so a case can assert that it reaches its branch)."""
+"""Worst-case material shared by the parity, order-search and window-search suites, the record check of the flagged
+candidate batch against tests/order_model.py or tests/window_model.py, and predicates saying which branch of
+order_search_kernel every candidate of a subframe reaches (computed from the model on the CPU, so a case can assert that
+it reaches its branch, and in which candidate)."""
 import numpy as np
 
 import order_model as om
@@ -49,24 +50,37 @@ def extreme_frames(rng, n, bps):
     return np.stack(frames).astype(np.int32)
 
 
-def check_rows(params, residual, R, A, x, bps, cfg, where):
+def params_record(p):
+    """A status-0 flacenc_hip_subframe_params record as the models' record functions state one."""
+    return {"order": int(p["order"]), "shift": int(p["shift"]), "precision": int(p["precision"]),
+            "coefs": [int(c) for c in p["coefs"]], "rice_order": int(p["rice_order"]),
+            "rice_params": [int(c) for c in p["rice_params"][:1 << int(p["rice_order"])]], "status": 0,
+            "code_bits": int(p["code_bits"]), "subframe_bits": int(p["subframe_bits"]),
+            "sum_quotients": int(p["sum_quotients"])}
+
+
+def check_rows(params, residual, R, A, x, bps, cfg, where, record=om.record):
     """Status, R[], unquantised coefficients, record fields and residual rows of a flagged candidate batch == the
-    model's, row by row."""
+    model's, row by row.  record(x, bps, cfg) -> (record fields, residual row, autocorr [33], lpc_coefs [32]):
+    order_model.record, or window_record(extras, orders) for FLACENC_HIP_FLAG_WINDOW_SEARCH, whose autocorr is the winning
+    window's R_j."""
     for i in range(len(x)):
-        rec, resid, ac, lc = om.record(x[i], bps[i] if np.ndim(bps) else bps, cfg)
+        rec, resid, ac, lc = record(x[i], int(bps[i]) if np.ndim(bps) else bps, cfg)
         p = params[i]
         assert int(p["status"]) == rec["status"], (where, i)
         assert np.array_equal(R[i], ac), (where, i)
         assert np.array_equal(A[i], lc), (where, i)
         if rec["status"] != 0:
             continue
-        got = {"order": int(p["order"]), "shift": int(p["shift"]), "precision": int(p["precision"]),
-               "coefs": [int(c) for c in p["coefs"]], "rice_order": int(p["rice_order"]),
-               "rice_params": [int(c) for c in p["rice_params"][:1 << int(p["rice_order"])]], "status": 0,
-               "code_bits": int(p["code_bits"]), "subframe_bits": int(p["subframe_bits"]),
-               "sum_quotients": int(p["sum_quotients"])}
+        got = params_record(p)
         assert got == rec, (where, i, got, rec)
         assert np.array_equal(residual[i], resid), (where, i)
+
+
+def window_record(extras, orders):
+    """check_rows' record function for one extra-window list (tests/window_model.py) and the orders switch."""
+    import window_model as wm
+    return lambda x, bps, cfg: wm.record(x, bps, cfg, extras, orders)
 
 
 # ---- material ----
@@ -130,39 +144,57 @@ def zigzag(e):
     return np.where(e < 0, -2 * e - 1, 2 * e).astype(np.uint64)
 
 
-def branches(x, bps, cfg):
-    """Which branches order_search_kernel takes on one subframe over its candidates with status 0: a set of
-    'i24' (v_mad_i32_i24 residuals), 'i64' (64-bit residuals), 'wide' (zig-zag codes of 2^27 and more), 'ksat'
-    (a finest partition's sum of codes reaches 2^32, codes below 2^27), 'clamp' (the chosen level's table sum
-    differs from the exact bits: a saturated entry), 'rice2' (a chosen parameter above 14), 'status' (some order
-    with a non-zero status)."""
-    x = np.ascontiguousarray(x, np.int32)
-    R = om.autocorr(x, bps, cfg)
+def candidate_branches(c, x, bps):
+    """The branch set of one candidate (order_model.candidate's dict) of subframe x: see branches."""
+    if c["status"] != om.STATUS_OK:
+        return {"status"}
     n = len(x)
     fo = finest_order(n)
     psize = n >> fo
-    maxabs = int(np.max(np.abs(x.astype(np.int64)))) if n else 0
+    maxabs = int(np.max(np.abs(np.asarray(x, np.int64)))) if n else 0
     out = set()
-    for o in range(1, cfg.lpc_order + 1):
-        c = om.candidate(x, bps, R, o, cfg)
-        if c["status"] != om.STATUS_OK:
-            out.add("status")
-            continue
-        qp = c["qp"]
-        sumabs = int(np.sum(np.abs(np.asarray(qp.coefs[:32], np.int64))))
-        out.add("i24" if maxabs * sumabs < 0x7FFFFFFF and maxabs < (1 << 23) else "i64")
-        u = zigzag(c["residual"])
-        u[:qp.order] = 0
-        wide = int(u.max()) >= (1 << 27)
-        if wide:
-            out.add("wide")
-        elif max(int(u[i * psize:(i + 1) * psize].sum()) for i in range(1 << fo)) >= (1 << 32):
-            out.add("ksat")
-        params = [int(p) for p in c["rice_params"]]
-        if max(params) > 14:
-            out.add("rice2")
-        nb = 1 << c["rice_order"]
-        narrow = 8 + bps * qp.order + 9 + qp.precision * qp.order + 6 + c["code_bits"] + (nb if max(params) > 14 else 0)
-        if not wide and narrow != c["subframe_bits"]:
-            out.add("clamp")
+    qp = c["qp"]
+    sumabs = int(np.sum(np.abs(np.asarray(qp.coefs[:32], np.int64))))
+    out.add("i24" if maxabs * sumabs < 0x7FFFFFFF and maxabs < (1 << 23) else "i64")
+    u = zigzag(c["residual"])
+    u[:qp.order] = 0
+    wide = int(u.max()) >= (1 << 27)
+    if wide:
+        out.add("wide")
+    elif max(int(u[i * psize:(i + 1) * psize].sum()) for i in range(1 << fo)) >= (1 << 32):
+        out.add("ksat")
+    params = [int(p) for p in c["rice_params"]]
+    if max(params) > 14:
+        out.add("rice2")
+    nb = 1 << c["rice_order"]
+    narrow = 8 + bps * qp.order + 9 + qp.precision * qp.order + 6 + c["code_bits"] + (nb if max(params) > 14 else 0)
+    if not wide and narrow != c["subframe_bits"]:
+        out.add("clamp")
     return out
+
+
+def branches_by_candidate(x, bps, cfg, extras, orders):
+    """Which branches order_search_kernel takes on every candidate of window_model.search, in kernel order
+    (c = j * Pc + ...): a list of sets of 'i24' (v_mad_i32_i24 residuals), 'i64' (64-bit residuals), 'wide' (zig-zag
+    codes of 2^27 and more), 'ksat' (a finest partition's sum of codes reaches 2^32, codes below 2^27), 'clamp' (the
+    chosen level's table sum differs from the exact bits: a saturated entry), 'rice2' (a chosen parameter above 14),
+    'status' (a non-zero status)."""
+    import window_model as wm
+    x = np.ascontiguousarray(x, np.int32)
+    _, cands = wm.search(x, bps, cfg, extras, orders)
+    return [candidate_branches(c, x, bps) for c in cands]
+
+
+def regime(b):
+    """One letter per candidate's key regime: W wide, K kSat alone, C clamp, . an ordinary candidate."""
+    return "W" if "wide" in b else "C" if "clamp" in b else "K" if "ksat" in b else "."
+
+
+def regimes(x, bps, cfg, extras, orders):
+    return "".join(regime(b) for b in branches_by_candidate(x, bps, cfg, extras, orders))
+
+
+def branches(x, bps, cfg):
+    """The union of branches_by_candidate over the one-window case with every order: what the order search alone
+    reaches on one subframe."""
+    return set().union(*branches_by_candidate(x, bps, cfg, (), True))

@@ -199,6 +199,23 @@ def test_parity_modes_carry_through(h, flags):
     check(h, cfg_of(flags=flags), x, 3 * S, S, 3, 16)
 
 
+SEARCH_FLAGS = {"wasted": _capi.FLAG_WASTED_BITS, "orders": _capi.FLAG_ORDER_SEARCH, "windows": _capi.FLAG_WINDOW_SEARCH,
+                "all": _capi.FLAG_WASTED_BITS | _capi.FLAG_ORDER_SEARCH | _capi.FLAG_WINDOW_SEARCH}
+
+
+@pytest.mark.parametrize("S", [4096, 2048])  # (three levels: leaves of 1024 and 512 samples, the sub-wave shapes)
+@pytest.mark.parametrize("name", list(SEARCH_FLAGS))
+def test_wasted_bits_and_the_lpc_searches_carry_through(h, name, S):
+    """Under WASTED_BITS, ORDER_SEARCH, WINDOW_SEARCH (the handle's default list) and all three, the search is held as
+    under the parity modes: body parity with the fixed path frame by frame, the tree-minimum tilings, decode, verify
+    and index."""
+    x = material(5, 2, S, 16, seed=S + len(name)).astype(np.int64)
+    x[1] <<= 8         # 16-bit content in a 24-bit container: wasted bits in some superblocks only,
+    x[3, 0] <<= 3      # in one channel of another,
+    x[4, :, S // 2:] <<= 5  # and in one half of the last
+    check(h, cfg_of(flags=SEARCH_FLAGS[name]), x.astype(np.int32), 5 * S - 321, S, 3, 24)
+
+
 def test_strict_gain_on_changing_material(h):
     """Quarters alternate between digital silence and a loud tone: coding the quarters alone wins."""
     S, n_sb = 4096, 8

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import extreme_signals as es
 import util
 import window_model as wm
 from extreme_signals import alternation, extreme_frames, noise
@@ -51,21 +52,7 @@ def with_silence(x):
 
 
 def check_rows(params, residual, R, A, x, bps, cfg, extras, orders, where):
-    for i in range(len(x)):
-        rec, resid, ac, lc = wm.record(x[i], bps, cfg, extras, orders)
-        p = params[i]
-        assert int(p["status"]) == rec["status"], (where, i)
-        assert np.array_equal(R[i], ac), (where, i)
-        assert np.array_equal(A[i], lc), (where, i)
-        if rec["status"] != 0:
-            continue
-        got = {"order": int(p["order"]), "shift": int(p["shift"]), "precision": int(p["precision"]),
-               "coefs": [int(c) for c in p["coefs"]], "rice_order": int(p["rice_order"]),
-               "rice_params": [int(c) for c in p["rice_params"][:1 << int(p["rice_order"])]], "status": 0,
-               "code_bits": int(p["code_bits"]), "subframe_bits": int(p["subframe_bits"]),
-               "sum_quotients": int(p["sum_quotients"])}
-        assert got == rec, (where, i, got, rec)
-        assert np.array_equal(residual[i], resid), (where, i)
+    es.check_rows(params, residual, R, A, x, bps, cfg, where, es.window_record(extras, orders))
 
 
 BATCH_CASES = [

@@ -49,6 +49,48 @@ def weights(entry, n) -> np.ndarray:
     return w
 
 
+ALPHAS = (0.0, 0.1, 0.2, 0.5, 1.0)
+
+
+def unit_of(sample, n) -> int:
+    """The smallest start / end value whose piece boundary over n samples is `sample` (0 <= sample <= n)."""
+    return -((-sample << 16) // n)
+
+
+def random_extras(rng, n) -> tuple:
+    """A valid extra-window list for blocks of n samples: 0 to 7 entries of all four types, alphas from ALPHAS, and
+    among the pieces some that are empty or one sample long on n (a partial window's piece, a punch-out's head or
+    tail).  Every entry passes flacenc_hip_set_lpc_windows' validation: 0 <= start < end <= 65536 for the two piece
+    types."""
+    out = []
+    for _ in range(int(rng.integers(0, 8))):
+        t = int(rng.integers(0, 4))
+        alpha = float(rng.choice(ALPHAS))
+        start = end = 0
+        if t >= PARTIAL_TUKEY:
+            m = int(rng.integers(0, 2))  # the degenerate length
+            shape = int(rng.integers(0, 3))
+            if shape > 0:
+                start = int(rng.integers(0, UNIT))
+                end = int(rng.integers(start + 1, UNIT + 1))
+            elif t == PARTIAL_TUKEY:
+                s = int(rng.integers(0, n - m + 1 if m else n))
+                start = unit_of(s, n)
+                end = unit_of(s + m, n) if m else start + 1
+                assert piece(start, end, n) == (s, s + m)
+            elif rng.random() < 0.5:  # a head of m samples
+                start = unit_of(m, n) if m else 0
+                end = int(rng.integers(start + 1, UNIT + 1))
+                assert piece(start, end, n)[0] == m
+            else:  # a tail of m samples
+                end = unit_of(n - m, n)
+                start = int(rng.integers(0, end))
+                assert n - piece(start, end, n)[1] == m
+            assert 0 <= start < end <= UNIT
+        out.append((t, alpha, start, end))
+    return tuple(out)
+
+
 def config_window(cfg, n) -> np.ndarray:
     """Window 0: the config's own (window_type, tukey_alpha)."""
     if cfg.window_type == RECTANGLE:
