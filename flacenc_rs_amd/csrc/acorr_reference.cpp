@@ -24,8 +24,10 @@
 // the last tile of a block that is not a multiple of 64.
 #include "acorr_reference.h"
 
+#include <cstddef>
 #include <type_traits>
 
+#include "flacenc_hip.h"
 #include "lds_opt_in.h"
 
 namespace flacenc_hip {
@@ -495,6 +497,8 @@ __global__ void __launch_bounds__(256) acorr_reference_mfma_kernel(AcorrRefArgs 
   // the sub-wave kernel's clean-up (marked_params; round 6), the units of a small grid's stride that hold a record of
   // status -2 (int32 at byte 68 of the 352-byte record): the launch normally finds the count of marked records at 0 and
   // must cost next to nothing then
+  static_assert(sizeof(flacenc_hip_subframe_params) == 352u && offsetof(flacenc_hip_subframe_params, status) == 68u,
+                "the marked-record scan below reads flacenc_hip_subframe_params::status by these two numbers");
   auto process = [&](const uint32_t unit) __attribute__((always_inline)) {
   const uint32_t sf0 = unit * 4u;
   if (sf0 >= a.n_subframes) return;  // (whole wave; no barriers in this kernel)

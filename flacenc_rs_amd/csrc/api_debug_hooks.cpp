@@ -1,0 +1,41 @@
+// api_debug_hooks.cpp -- the test and profiling hooks of flacenc_hip_debug.h and nothing else: this object is linked into
+// libflacenc_hip_hooks.so only, so the product library has none of them.
+#include "api_internal.h"
+#include "flacenc_hip_debug.h"
+
+extern "C" {
+
+int flacenc_hip_debug_set_fixed_keys(flacenc_hip_handle* h, unsigned long long* device_keys) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->fixed_keys = device_keys;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_set_stamps(flacenc_hip_handle* h, unsigned long long* device_stamps) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->stamps = device_stamps;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_set_adaptive_order(flacenc_hip_handle* h, int on) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->adaptive_order = on ? 1 : 0;
+  h->two_pass_left = h->two_pass_span = 0;
+  h->fb_probe_out = false;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_adaptive_state(flacenc_hip_handle* h, int* span, int* left) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (span) *span = h->two_pass_span;
+  if (left) *left = h->two_pass_left;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_set_cert_stats(flacenc_hip_handle* h, uint32_t* device_counters) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->cert_stats = device_counters;
+  return FLACENC_HIP_OK;
+}
+
+}  // extern "C"

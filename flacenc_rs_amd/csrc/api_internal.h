@@ -1,0 +1,280 @@
+// api_internal.h -- what the translation units of the C ABI (include/flacenc_hip.h) share: the handle, its device
+// buffers, the error helpers and the functions one unit calls in another.  Not installed, not part of any boundary.
+//
+// The handle owns the per-handle state the reference keeps in thread-locals (`reusable!`,
+// src/lib.rs:92-116): the window cache (WINDOW_CACHE, src/lpc.rs:219-231) and
+// the scratch buffers, here as device memory.  No allocation happens on the
+// device-pointer path once the window for a block size is cached.
+//
+//   api_handle.cpp       create / destroy / synchronize, verify_config, pinned memory, set_error, ensure
+//   api_windows.cpp      the analysis windows and their cache
+//   api_candidates.cpp   the candidate batches: argument checks, scratch, the order mode, enqueue, enqueue_fixed
+//   api_frames.cpp       encode_frame's decisions: independent channels, stereo, wasted bits, encode + pack
+//   api_pack.cpp         Frame::write, frame lengths, the wire format, stream offsets
+//   api_stream.cpp       the streaming host path (flacenc_hip_encode_pcm)
+//   api_decode.cpp       decode / verify / index
+//   api_variable.cpp     the block-size search
+//   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
+#ifndef FLACENC_HIP_API_INTERNAL_H_
+#define FLACENC_HIP_API_INTERNAL_H_
+
+#include <hip/hip_runtime.h>
+
+#include <condition_variable>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "comm.h"
+#include "flacenc_hip.h"
+#include "frame_pack.h"
+#include "qlpc_kernel.h"
+
+namespace flacenc_hip {
+
+struct WindowEntry {
+  uint32_t n;
+  uint32_t type;
+  uint32_t alpha_bits;
+  uint32_t start, end;  // FLACENC_HIP_WINDOW_PARTIAL_TUKEY / _PUNCHOUT_TUKEY: the piece, in FLACENC_HIP_WINDOW_UNIT; else 0
+  float* dev;  // 32 pad + rows*16 floats
+  int32_t flat_lo, flat_hi;
+};
+
+// an extra analysis window of FLACENC_HIP_FLAG_WINDOW_SEARCH (flacenc_hip_set_lpc_windows)
+struct LpcWindow {
+  uint32_t type;
+  float alpha;
+  uint32_t start, end;
+};
+
+// the default extra windows of a fresh handle (include/flacenc_hip.h, _capi.DEFAULT_LPC_WINDOWS)
+const LpcWindow kDefaultLpcWindows[] = {
+    {FLACENC_HIP_WINDOW_PARTIAL_TUKEY, 0.2f, 0, 36044},
+    {FLACENC_HIP_WINDOW_PARTIAL_TUKEY, 0.2f, 29492, 65536},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 0, 21845},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 21845, 43690},
+    {FLACENC_HIP_WINDOW_PUNCHOUT_TUKEY, 0.2f, 43690, 65536},
+};
+
+struct DeviceBuffer {
+  void* ptr = nullptr;
+  size_t cap = 0;
+};
+
+// Staging copies between ordinary (pageable) caller memory and the pinned slots of the streaming path: one
+// memcpy stream moves ~20 GB/s on the host, well under what PCIe takes in both directions at once, so a
+// copy is cut into slices for a few helper threads (the caller's thread takes one slice itself).
+class CopyPool {
+ public:
+  explicit CopyPool(unsigned workers) : tasks_(workers) {
+    try {
+      threads_.reserve(workers);
+      for (unsigned i = 0; i < workers; ++i) threads_.emplace_back([this, i] { run(i); });
+    } catch (...) {  // a thread that did start must be joined before its std::thread is destroyed
+      {
+        std::lock_guard<std::mutex> g(m_);
+        stop_ = true;
+      }
+      cv_.notify_all();
+      for (std::thread& t : threads_) t.join();
+      throw;
+    }
+  }
+  ~CopyPool() {
+    {
+      std::lock_guard<std::mutex> g(m_);
+      stop_ = true;
+    }
+    cv_.notify_all();
+    for (std::thread& t : threads_) t.join();
+  }
+  unsigned workers() const { return static_cast<unsigned>(threads_.size()); }
+  void copy(void* dst, const void* src, size_t n) {
+    const size_t parts = threads_.size() + 1;
+    if (threads_.empty() || n < (size_t(1) << 20)) {
+      std::memcpy(dst, src, n);
+      return;
+    }
+    const size_t slice = ((n + parts - 1) / parts + 4095) & ~size_t(4095);
+    char* d = static_cast<char*>(dst);
+    const char* sp = static_cast<const char*>(src);
+    {
+      std::lock_guard<std::mutex> g(m_);
+      for (size_t i = 0; i < threads_.size(); ++i) {
+        const size_t lo = (i + 1) * slice;
+        const size_t len = lo >= n ? 0 : (n - lo < slice ? n - lo : slice);
+        tasks_[i] = Task{d + lo, sp + lo, len};
+      }
+      pending_ = static_cast<unsigned>(threads_.size());
+      ++generation_;
+    }
+    cv_.notify_all();
+    std::memcpy(d, sp, slice < n ? slice : n);
+    std::unique_lock<std::mutex> g(m_);
+    done_cv_.wait(g, [this] { return pending_ == 0; });
+  }
+
+ private:
+  struct Task {
+    char* d = nullptr;
+    const char* s = nullptr;
+    size_t n = 0;
+  };
+  void run(unsigned idx) {
+    unsigned long long seen = 0;
+    for (;;) {
+      Task t;
+      {
+        std::unique_lock<std::mutex> g(m_);
+        cv_.wait(g, [&] { return stop_ || generation_ != seen; });
+        if (stop_) return;
+        seen = generation_;
+        t = tasks_[idx];
+      }
+      if (t.n) std::memcpy(t.d, t.s, t.n);
+      {
+        std::lock_guard<std::mutex> g(m_);
+        --pending_;
+      }
+      done_cv_.notify_one();
+    }
+  }
+  std::vector<std::thread> threads_;
+  std::vector<Task> tasks_;
+  std::mutex m_;
+  std::condition_variable cv_, done_cv_;
+  unsigned long long generation_ = 0;
+  unsigned pending_ = 0;
+  bool stop_ = false;
+};
+
+}  // namespace flacenc_hip
+
+struct flacenc_hip_handle {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string last_error;
+  std::vector<flacenc_hip::WindowEntry> windows;
+  // FLACENC_HIP_FLAG_WINDOW_SEARCH: the extra analysis windows (windows 1 .. W-1; window 0 is the config's)
+  std::vector<flacenc_hip::LpcWindow> lpc_windows{std::begin(flacenc_hip::kDefaultLpcWindows), std::end(flacenc_hip::kDefaultLpcWindows)};
+  flacenc_hip::DeviceBuffer d_samples, d_residual, d_params, d_bps, d_autocorr, d_lpc, d_tables, d_keys, d_sel, d_results, d_out, d_outlen, d_cparams, d_cresid, d_fparams, d_fresid, d_fkeys, d_split, d_presid, d_sumabs, d_minmax, d_marked, d_irlsw, d_gram;
+  flacenc_hip::DeviceBuffer d_dec, d_dec_io, d_idx;  // frame decoder: skim records, host-pointer staging, index candidates
+  // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
+  flacenc_hip::DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
+  // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
+  flacenc_hip::DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
+  // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
+  flacenc_hip::DeviceBuffer d_order;
+  // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
+  // staging and device buffers, the events that order them
+  uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into
+  hipStream_t s_in = nullptr, s_out = nullptr;
+  hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_fill[2] = {nullptr, nullptr}, ev_pack[2] = {nullptr, nullptr},
+             ev_d2h[2] = {nullptr, nullptr};
+  flacenc_hip::DeviceBuffer d_pcm[2], d_pack[2], d_plen[2], d_poff[2], d_cont[2];
+  void* pin_in[2] = {nullptr, nullptr};
+  void* pin_out[2] = {nullptr, nullptr};
+  void* pin_meta[2] = {nullptr, nullptr};
+  size_t pin_in_cap = 0, pin_out_cap = 0, pin_meta_cap = 0;
+  int host_threads = -1;  // staging-copy threads of the streaming path: -1 = default, see flacenc_hip_set_host_threads
+  std::unique_ptr<flacenc_hip::CopyPool> copy_pool;
+  unsigned long long* stamps = nullptr;  // profiling hook, see flacenc_hip_debug_set_stamps
+  unsigned long long* fixed_keys = nullptr;  // test hook, see flacenc_hip_debug_set_fixed_keys
+  uint32_t* cert_stats = nullptr;  // statistics hook, see flacenc_hip_debug_set_cert_stats
+  flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
+  // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
+  // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch
+  uint32_t* d_cert_fb = nullptr;               // device: the three counters of QlpcKernelArgs::cert_stats
+  unsigned long long* h_cert_fb = nullptr;     // pinned, device-visible: the latest verdict (cert_feedback_kernel)
+  uint32_t fb_seq = 0, fb_seen_seq = 0, fb_probe_seq = 0;  // sequence numbers of the launches that carried the counters
+  uint32_t fb_pending = 0;  // subframes counted on the device since the last verdict went out
+  bool fb_probe_out = false;
+  int two_pass_left = 0, two_pass_span = 0;
+  int adaptive_order = 1;                      // flacenc_hip_debug_set_adaptive_order(h, 0) pins the certified kernel
+};
+
+#define HIP_TRY(h, expr)                          \
+  do {                                            \
+    hipError_t err__ = (expr);                    \
+    if (err__ != hipSuccess) {                    \
+      flacenc_hip::set_error((h), #expr, err__);  \
+      return FLACENC_HIP_ERR_DEVICE;              \
+    }                                             \
+  } while (0)
+
+namespace flacenc_hip {
+
+// ---- api_handle.cpp ----
+bool set_error(flacenc_hip_handle* h, const char* what, hipError_t err);
+// grows by 25 % + 256 bytes, frees what it held: the contents do not survive
+int ensure(flacenc_hip_handle* h, DeviceBuffer& b, size_t bytes);
+// the tail of a blocking call on device pointers: the async entry's code, or the handle's stream drained
+int drained(flacenc_hip_handle* h, int rc, bool nothing_queued);
+// the blocking calls on host pointers: `n_rows` rows of `block_size` words between the caller's buffer (row stride
+// `stride` words) and handle scratch at padded_stride(block_size), on the handle's stream
+int rows_to_device(flacenc_hip_handle* h, const DeviceBuffer& b, const int32_t* rows, size_t stride, uint32_t block_size,
+                   size_t n_rows);
+int rows_to_host(flacenc_hip_handle* h, int32_t* rows, size_t stride, const DeviceBuffer& b, uint32_t block_size,
+                 size_t n_rows);
+
+// row stride of every scratch buffer of sample or residual rows: whole 16-byte groups
+inline size_t padded_stride(uint32_t block_size) { return (static_cast<size_t>(block_size) + 3) & ~static_cast<size_t>(3); }
+inline size_t a256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+// ---- api_windows.cpp ----
+int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t n,
+                     const WindowEntry** out);
+int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32_t n, const WindowEntry** out);
+
+// ---- api_candidates.cpp ----
+uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags);
+bool lpc_search(uint32_t flags);
+int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
+                     size_t n_subframes, uint32_t block_size, size_t stride, flacenc_hip_subframe_params* params,
+                     int32_t* residual, size_t residual_stride, uint32_t min_block = FLACENC_HIP_MIN_BLOCK_SIZE);
+int verify_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg);
+// What every launch record shares, from (handle, qlpc config, shape): the rows, the window entry (`win` null: no window,
+// flat range 0), order and precision, max_rice_parameter, the three flag-derived words, set_certify and direct_mse.
+// Everything else is as QlpcKernelArgs initialises it; each caller sets what is its own.
+QlpcKernelArgs base_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, const WindowEntry* win,
+                         const int32_t* samples, size_t stride, uint32_t block_size, size_t n_subframes,
+                         const uint8_t* bps, uint32_t bps_uniform, bool stereo);
+bool certify_needs_scratch(const QlpcKernelArgs& a);
+int attach_sumabs_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, bool approx_ent);
+int attach_split_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, void* stream);
+int launch_adaptive(flacenc_hip_handle* h, QlpcKernelArgs& a, const QlpcLaunchPlan& plan, hipStream_t stream);
+// The candidates' scratch of a frame-level call, `n_rows` candidates of `block_size` samples in the handle's buffers:
+// records, rows at padded_stride(block_size) and (LPC, on request) the roles' min / max resp. (fixed) the selector keys
+struct LpcScratch {
+  flacenc_hip_subframe_params* params;
+  int32_t* rows;
+  int32_t* minmax;  // null unless asked for
+};
+struct FixedScratch {
+  flacenc_hip_subframe_params* params;
+  int32_t* rows;
+  unsigned long long* keys;
+};
+int lpc_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, bool with_minmax, LpcScratch* out);
+int fixed_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, FixedScratch* out);
+int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples, size_t n_subframes,
+            uint32_t block_size, size_t stride, const uint8_t* bps, flacenc_hip_subframe_params* params,
+            int32_t* residual, size_t residual_stride, double* autocorr, double* lpc_coefs, hipStream_t stream,
+            bool stereo = false, uint32_t bps_uniform = 16, int32_t* residual_lr = nullptr,
+            size_t residual_lr_stride = 0, int32_t* minmax_out = nullptr, bool* placed = nullptr,
+            uint32_t residual_mode = 0);
+int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* samples,
+                  size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps, uint32_t bps_uniform,
+                  bool stereo, flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
+                  unsigned long long* selector_keys, hipStream_t stream, uint32_t residual_mode = 0);
+
+// ---- api_pack.cpp ----
+void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);
+void fill_header_specs(FramePackArgs& a, uint32_t block_size, uint32_t sample_rate, uint32_t bits_per_sample);
+
+}  // namespace flacenc_hip
+#endif

@@ -10,7 +10,7 @@
 namespace flacenc_hip {
 
 struct CommState;  // comm.cpp
-// the handle's slot for it, its device and its error string (flacenc_hip_api.cpp)
+// the handle's slot for it, its device and its error string (api_handle.cpp)
 CommState*& handle_comm_slot(flacenc_hip_handle* h);
 int handle_device(const flacenc_hip_handle* h);
 void handle_set_error(flacenc_hip_handle* h, const std::string& what);

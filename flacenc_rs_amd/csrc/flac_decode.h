@@ -1,4 +1,4 @@
-// flac_decode.h -- launchers of the frame decoder's kernels (flac_decode.cpp) for flacenc_hip_api.cpp.
+// flac_decode.h -- launchers of the frame decoder's kernels (flac_decode.cpp) for api_decode.cpp.
 #ifndef FLACENC_FLAC_DECODE_H_
 #define FLACENC_FLAC_DECODE_H_
 

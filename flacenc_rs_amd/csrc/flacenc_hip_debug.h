@@ -1,6 +1,6 @@
 /* flacenc_hip_debug.h -- test and profiling hooks.  NOT part of the drop-in boundary (include/flacenc_hip.h) and NOT in
- * the product library: the Makefile links libflacenc_hip.so without them and a second library, libflacenc_hip_hooks.so --
- * the same objects, flacenc_hip_api.cpp compiled once more with -DFLACENC_HIP_DEBUG_HOOKS -- for tests/ and tools/
+ * the product library: they are api_debug_hooks.cpp, whose object the Makefile leaves out of libflacenc_hip.so and links
+ * into a second library, libflacenc_hip_hooks.so -- otherwise the same objects -- for tests/ and tools/
  * (flacenc_rs_amd/_capi.py: Handle(dev, hooks=True)). */
 #ifndef FLACENC_HIP_DEBUG_H_
 #define FLACENC_HIP_DEBUG_H_
@@ -29,7 +29,7 @@ int flacenc_hip_debug_set_stamps(flacenc_hip_handle* h, unsigned long long* devi
 int flacenc_hip_debug_set_cert_stats(flacenc_hip_handle* h, uint32_t* device_counters);
 /* 0: launches of the certified shapes always take the fused kernel's certificate; 1 (default): integer-only launches of
  * any size take the two-pass form (the reference's chains for every subframe, same integers) while the
- * certificate's counters of the launches before them say the material is hard (flacenc_hip_api.cpp, launch_adaptive) */
+ * certificate's counters of the launches before them say the material is hard (api_candidates.cpp, launch_adaptive) */
 int flacenc_hip_debug_set_adaptive_order(flacenc_hip_handle* h, int on);
 /* the current span of two-pass launches (0: the material last seen was easy) and how many of it are left */
 int flacenc_hip_debug_adaptive_state(flacenc_hip_handle* h, int* span, int* left);

@@ -17,26 +17,26 @@ namespace flacenc_hip {
 constexpr int kAcorrChunk = 16;
 
 struct QlpcKernelArgs {
-  const int32_t* samples;   // device; subframe k at samples + k*stride
-  size_t stride;
-  uint32_t block_size;
-  uint32_t n_subframes;
-  const uint8_t* bps;       // device, per subframe (nullable -> bps_uniform)
-  uint32_t bps_uniform;
-  uint32_t stereo;          // 1: workgroups 4f..4f+3 = L, R, M, S of 2-channel frame f
-  const float* window;      // device table with 32 leading pad floats, nullptr = all ones
-  int32_t flat_lo;          // window[t] == 1.0f for flat_lo <= t < flat_hi
-  int32_t flat_hi;
-  uint32_t lpc_order;
-  uint32_t precision;
-  uint32_t max_rice_parameter;
-  uint32_t rice_finest_only;  // FLACENC_HIP_FLAG_FINEST_RICE_ORDER: no merging below the finest order
-  uint32_t force_generic;     // FLACENC_HIP_FLAG_GENERIC_KERNEL: never the wave-per-subframe kernel
+  const int32_t* samples = nullptr;   // device; subframe k at samples + k*stride
+  size_t stride = 0;
+  uint32_t block_size = 0;
+  uint32_t n_subframes = 0;
+  const uint8_t* bps = nullptr;       // device, per subframe (nullable -> bps_uniform)
+  uint32_t bps_uniform = 0;
+  uint32_t stereo = 0;          // 1: workgroups 4f..4f+3 = L, R, M, S of 2-channel frame f
+  const float* window = nullptr;      // device table with 32 leading pad floats, nullptr = all ones
+  int32_t flat_lo = 0;          // window[t] == 1.0f for flat_lo <= t < flat_hi
+  int32_t flat_hi = 0;
+  uint32_t lpc_order = 0;
+  uint32_t precision = 0;
+  uint32_t max_rice_parameter = 0;
+  uint32_t rice_finest_only = 0;  // FLACENC_HIP_FLAG_FINEST_RICE_ORDER: no merging below the finest order
+  uint32_t force_generic = 0;     // FLACENC_HIP_FLAG_GENERIC_KERNEL: never the wave-per-subframe kernel
   // FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER: R[] comes from acorr_reference_kernel (the reference's stable
   // summation order, one sequential chain per lag) instead of the kernels' canonical chunk tree;
   // launch_qlpc runs it into split_scratch (or `autocorr`) and hands the result on as `acorr_in`
-  uint32_t reference_order;
-  const double* acorr_in;     // device, [n][33]: precomputed R[], skips phase 1 (wave kernel)
+  uint32_t reference_order = 0;
+  const double* acorr_in = nullptr;     // device, [n][33]: precomputed R[], skips phase 1 (wave kernel)
   // The unflagged order on blocks of 4096 / 4608 samples at orders up to 12 (set by launch_qlpc): the chunk tree's R[]
   // is kept where it CERTIFIES the quantised parameters against the reference's chains (levinson_quantize<.., CERT>) and
   // the subframe is redone from those chains where it does not -- by the fused kernel itself (reference_chains_from_lds);
@@ -88,7 +88,7 @@ struct QlpcKernelArgs {
   const int32_t* cand_lpc_rows = nullptr;                          // rows the generic clean-up wrote for marked subframes
   const int32_t* cand_fixed_rows = nullptr;
   size_t cand_stride = 0;
-  uint32_t only_marked;       // generic kernel: redo only subframes whose record says status == -1
+  uint32_t only_marked = 0;       // generic kernel: redo only subframes whose record says status == -1
   // subframes bigblock_residual_kernel marked for that clean-up launch: qlpc_marked_kernel returns at once on 0.  The
   // handle alternates between two counters from pipeline to pipeline; the clean-up launch clears `marked_next`, the one
   // the following pipeline counts into, and attaching the scratch clears the pipeline's own (so a pipeline without a
@@ -104,48 +104,49 @@ struct QlpcKernelArgs {
   uint32_t* marked_list = nullptr;
   uint32_t marked_cap = 0;
   uint32_t marked_unit = 1;
-  flacenc_hip_subframe_params* params;  // device
-  int32_t* residual;                    // device
-  size_t residual_stride;
-  double* autocorr;                     // device, nullable, [n][33]
-  double* lpc_coefs;                    // device, nullable, [n][32]
-  uint32_t* table_scratch;              // device, only for blocks > 16384 samples
-  unsigned long long* stamps;           // device, nullable: [n][8] phase timestamps (profiling)
+  flacenc_hip_subframe_params* params = nullptr;  // device
+  int32_t* residual = nullptr;                    // device
+  size_t residual_stride = 0;
+  double* autocorr = nullptr;                     // device, nullable, [n][33]
+  double* lpc_coefs = nullptr;                    // device, nullable, [n][32]
+  uint32_t* table_scratch = nullptr;              // device, only for blocks > 16384 samples
+  unsigned long long* stamps = nullptr;           // device, nullable: [n][8] phase timestamps (profiling)
   // on-device encode_frame decision (stereo, wave kernel only)
-  flacenc_hip_stereo_frame_result* frame_results;  // device, [n_frames]; non-null selects DECIDE
-  flacenc_hip_channel_result* chan_results;        // device, [n_subframes]; non-null selects the
-                                                   // independent-channel DECIDE variant (stereo = 0)
-  uint32_t use_constant, use_lpc, use_leftside, use_rightside, use_midside;
+  flacenc_hip_stereo_frame_result* frame_results = nullptr;  // device, [n_frames]; non-null selects DECIDE
+  flacenc_hip_channel_result* chan_results = nullptr;  // device, [n_subframes]; non-null selects the
+                                                       // independent-channel DECIDE variant (stereo = 0)
+  // (1: the candidate-level launches, which have no such switches, need not name them)
+  uint32_t use_constant = 1, use_lpc = 1, use_leftside = 1, use_rightside = 1, use_midside = 1;
   // fixed-LPC candidate (config::Fixed, src/config.rs:236-244); wave kernel variant 3 only
-  uint32_t use_fixed;
-  uint32_t fixed_max_order;    // 0..4
-  uint32_t fixed_order_sel;    // 0 BitCount, 1 ApproxEnt
-  uint32_t fixed_group_log2;   // ApproxEnt: lanes per estimator partition = 2^g (4096 / partitions / 64)
-  unsigned long long* fixed_keys;  // device, nullable: [n][8] the selector's key per order (tests)
+  uint32_t use_fixed = 0;
+  uint32_t fixed_max_order = 0;    // 0..4
+  uint32_t fixed_order_sel = 0;    // 0 BitCount, 1 ApproxEnt
+  uint32_t fixed_group_log2 = 0;   // ApproxEnt: lanes per estimator partition = 2^g (4096 / partitions / 64)
+  unsigned long long* fixed_keys = nullptr;  // device, nullable: [n][8] the selector's key per order (tests)
   // generic kernel as `fixed_lpc` (src/coding.rs:298-331): 0 = QLPC analysis (default),
   // 1 = ApproxEnt order selection + coding, 2 = code order forced_uniform, 3 = code forced_orders[sf]
-  uint32_t fixed_mode;
-  uint32_t fixed_partitions;       // mode 1: OrderSel::ApproxEnt.partitions (1..64)
-  uint32_t forced_uniform;         // mode 2
-  const uint8_t* forced_orders;    // mode 3, device, [n]
-  unsigned long long* selector_keys;  // device, nullable, [n]: the chosen order's selector key
+  uint32_t fixed_mode = 0;
+  uint32_t fixed_partitions = 0;       // mode 1: OrderSel::ApproxEnt.partitions (1..64)
+  uint32_t forced_uniform = 0;         // mode 2
+  const uint8_t* forced_orders = nullptr;    // mode 3, device, [n]
+  unsigned long long* selector_keys = nullptr;  // device, nullable, [n]: the chosen order's selector key
   // three-launch split of the generic kernel for large orders (launch_qlpc): 0 = fused,
   // 1 = window + autocorrelation only (R[] to `autocorr`), 3 = residual + Rice with the predictor
   // levinson_batch_kernel left in `pred` ([n][36] int32: qc[32], order, shift, status, 0)
-  uint32_t lpc_stage;
-  const int32_t* pred;
-  int32_t* pred_out;
-  void* split_scratch;  // device, n * (33 * 8 + 36 * 4) bytes, or nullptr: no split
+  uint32_t lpc_stage = 0;
+  const int32_t* pred = nullptr;
+  int32_t* pred_out = nullptr;
+  void* split_scratch = nullptr;  // device, n * (33 * 8 + 36 * 4) bytes, or nullptr: no split
   // Frame::write fused into the deciding wave kernel (variant 5): non-null pack_out selects it.
   // Header constants and CRC combination powers as in FramePackArgs (frame_pack.h).
-  uint8_t* pack_out;          // device, 16-byte aligned; frame f at pack_out + f*pack_out_stride
-  size_t pack_out_stride;     // multiple of 16
-  uint32_t* pack_out_len;     // device, [n_frames]
-  uint32_t pack_header_mid, pack_extra_len;
-  uint8_t pack_extra[4];
-  uint32_t pack_first_frame, pack_frame_step;
-  uint32_t pack_lds_words, pack_crc_per;
-  uint16_t pack_crc_pow[32];
+  uint8_t* pack_out = nullptr;          // device, 16-byte aligned; frame f at pack_out + f*pack_out_stride
+  size_t pack_out_stride = 0;     // multiple of 16
+  uint32_t* pack_out_len = nullptr;     // device, [n_frames]
+  uint32_t pack_header_mid = 0, pack_extra_len = 0;
+  uint8_t pack_extra[4] = {};
+  uint32_t pack_first_frame = 0, pack_frame_step = 0;
+  uint32_t pack_lds_words = 0, pack_crc_per = 0;
+  uint16_t pack_crc_pow[32] = {};
 };
 
 // A record (or, unit 4, a stereo frame) is marked for the clean-up launches: counted, and entered in the list while it has room.

@@ -383,7 +383,7 @@ def test_integer_parity_only_keeps_the_certified_order_and_the_references_intege
 def test_two_pass_form_on_hard_material_gives_the_same_bytes(handle, order, use_fixed, nf):
     """Integer-only launches watch the certificate's counters (a verdict per 4096 subframes) and take the two-pass form (the
     reference's chains for every subframe on the matrix cores, then the fused kernel on their R[]) while the material last
-    seen was hard (flacenc_hip_api.cpp, launch_adaptive).  A choice of speed, never of result: on a batch of near-pure
+    seen was hard (api_candidates.cpp, launch_adaptive).  A choice of speed, never of result: on a batch of near-pure
     tones every launch -- certified kernel, two-pass, probe -- writes the same records and rows, the oracle's in the
     reference's order; a noisy batch never leaves the certified kernel.  Launches of 640 subframes: their counters add up to
     a verdict, the probe takes two of them."""

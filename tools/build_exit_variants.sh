@@ -6,7 +6,7 @@ set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $ROOT
 for k in 0 1 2 3; do
-  bash tools/variant_wave.sh exit$k 8 2 -DFLACENC_EXIT_AFTER=$k -DFLACENC_HIP_DEBUG_HOOKS | tail -1
+  bash tools/variant_wave.sh exit$k 8 2 -DFLACENC_EXIT_AFTER=$k | tail -1
   mv ab/libflacenc_hip_exit$k.so ab/libflacenc_exit$k.so
 done
 python3 -c "import bench; print(bench.kernel_source_sha())" > ab/exit_variants.sha
