@@ -544,6 +544,121 @@ __device__ int levinson_quantize(const double* __restrict__ Rl, int P, int preci
   return status;
 }
 
+// ---- the solver at full order, straight-line (the fused 4096 kernel's wave 0) ------------------------
+// levinson_core / levinson_quantize above with P == MAXP as a compile-time fact: no `n < P` / `i < P` guard, no
+// zero-fill that exists for the guards, and no divergent region per step -- every step is computed, and what the generic
+// code decides by branching is collected in flags instead.  Every floating-point operation is the operation of the generic
+// code, in its order (the fma's, the separate multiplies, the divisions, the sequential sums; where the generic code
+// reads a zero-filled entry -- forward[n] and a[n] on entering step n -- the literal +0.0 stands in the same operation:
+// beta * +0.0 is not +0.0 for an infinite beta, fma(x, y, +0.0) is not x * y for a product of -0.0).
+//
+// The return value `redo` is set wherever the generic code would have LEFT this line of operations: a zero denominator
+// (it skips the step; here the step ran with alpha = inf), R[0] not above zero (it solves nothing), a coefficient that is
+// not finite (it reports a status and quantises nothing).  The caller then solves again through the generic code, whose
+// records are today's by construction; without `redo` the status is 0 and everything below is what the generic code
+// computes for it.  The generic code's tests on R[] itself cannot fire on sums formed in the fused kernel and are not
+// repeated: |x_w| <= 2^31 and at most 4608 terms per lag keep every sum below 2^75 (finite), and R[0] is a chain of fma's
+// of squares started from +0.0 (never negative).  They stay where R[] is handed in: such launches take the generic code.
+// (Digital silence, R[0] = 0, goes through `redo`.  The one test that catches it -- R[0] is not a positive finite number --
+// also catches a negative, infinite or NaN R[0], and a non-finite R[k], k >= 1, makes a[k - 1] = fma(resid, forward[0],
+// +0.0) and every later value of it non-finite: should the argument above ever stop holding, such an R[] still ends in
+// the generic code and its tests.)
+template <int MAXP>
+__device__ __forceinline__ void levinson_core_full(const double (&R)[MAXP + 1], double (&a)[MAXP], double (&fwd)[MAXP],
+                                                   bool* skipped, bool* nonpd) {
+  fwd[0] = 1.0 / R[0];
+  a[0] = R[1] / R[0];
+#pragma unroll
+  for (int n = 1; n < MAXP; ++n) {
+    double err = 0.0;
+#pragma unroll
+    for (int d = 0; d < n; ++d) err = __builtin_fma(R[n - d], fwd[d], err);
+    const double denom = __builtin_fma(err, -err, 1.0);
+    *skipped |= denom == 0.0;
+    *nonpd |= !(denom > 0.0);
+    const double alpha = 1.0 / denom;
+    const double beta = -alpha * err;
+#pragma unroll
+    for (int d = 0; 2 * d <= n; ++d) {
+      const double fd = fwd[d], fe = d == 0 ? 0.0 : fwd[n - d];  // (forward[n] enters step n as +0.0)
+      const double nd = __builtin_fma(alpha, fd, beta * fe);
+      const double ne = __builtin_fma(alpha, fe, beta * fd);
+      fwd[d] = nd;
+      fwd[n - d] = ne;
+    }
+    double delta = 0.0;
+#pragma unroll
+    for (int d = 0; d < n; ++d) delta = __builtin_fma(R[n - d], a[d], delta);
+    const double resid = R[n + 1] - delta;
+#pragma unroll
+    for (int d = 0; d <= n; ++d) a[d] = __builtin_fma(resid, fwd[n - d], d == n ? 0.0 : a[d]);  // (a[n] likewise)
+  }
+}
+
+template <int MAXP, bool CERT>
+__device__ __forceinline__ bool levinson_quantize_full(const double* __restrict__ Rl, int precision, double (&a)[MAXP],
+                                                       int32_t* qc_out, int* order_out, int* shift_out, uint32_t max_abs_s,
+                                                       int n_sum, bool* certified_out, bool* tier2_out, bool do_cert) {
+  double R[MAXP + 1], fwd[MAXP];
+#pragma unroll
+  for (int i = 0; i <= MAXP; ++i) R[i] = Rl[i];
+  bool skipped = false, nonpd = false;
+  levinson_core_full<MAXP>(R, a, fwd, &skipped, &nonpd);
+  bool redo = skipped || !__builtin_amdgcn_class(R[0], 0x180);  // R[0] is not a positive finite number (normal or subnormal)
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) redo |= __builtin_amdgcn_class(a[i], 0x207);  // NaN or +-inf: exponent field 0x7FF (lpc.rs:797-799)
+
+  // quantize_parameters, as in levinson_quantize with status == 0
+  double max_abs = 0.0;
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) max_abs = fmax(max_abs, fabs(a[i]));
+  int abs_log2 = ceil_log2_pos(max_abs);
+  if (abs_log2 < -32752) abs_log2 = -32752;
+  int shift = (precision - 1) - abs_log2;
+  shift = shift < 0 ? 0 : (shift > 15 ? 15 : shift);
+  const double scalefac = (double)(1 << shift);
+  const int lo = -(1 << (precision - 1)), hi = (1 << (precision - 1)) - 1;
+  int order = 1;
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) {
+    double s = round(a[i] * scalefac);  // half away from zero
+    s = s < -32768.0 ? -32768.0 : (s > 32767.0 ? 32767.0 : s);
+    int q = (int)s;
+    q = q < lo ? lo : (q > hi ? hi : q);
+    qc_out[i] = q;
+    if (q != 0) order = i + 1;  // (nothing to clear above `order`: those entries are the zeros that ended it)
+  }
+  *order_out = order;
+  *shift_out = shift;
+  if (CERT) {
+    bool certified = true, tier2 = false;
+#ifndef FLACENC_CERT_NOBLOCK
+    if (do_cert) {  // (uniform over the launch)
+      CertArgs<MAXP> ca;
+#pragma unroll
+      for (int i = 0; i < MAXP; ++i) ca.a[i] = a[i];
+      double f1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < MAXP; ++i) f1 += fabs(fwd[i]);
+      ca.f1 = f1;
+      ca.f0 = fabs(fwd[0]);
+      ca.r0 = R[0];
+      ca.max_abs_s = max_abs_s;
+      ca.n_sum = n_sum;
+      ca.P = MAXP;
+      ca.shift = shift;
+      const int fl = quant_certified<MAXP>(ca);
+      // (a denominator that was not positive: no certificate, and no second tier either)
+      certified = !nonpd && (fl & 1) != 0;
+      tier2 = !nonpd && (fl & 2) != 0;
+    }
+#endif
+    *certified_out = certified;
+    *tier2_out = tier2;
+  }
+  return redo;
+}
+
 // ---------------------------------------------------------------------------
 // phase 1 inner block: 16 samples x (MAXP+1) lags, registers only
 // ---------------------------------------------------------------------------

@@ -40,6 +40,11 @@ namespace {
 #ifndef FLACENC_ORDER12_OCC3
 #define FLACENC_ORDER12_OCC3 14  // bit v: variant v (FLACENC_STEREO) of the order-12 bucket at three workgroups per CU
 #endif
+// The straight-line full-order solver (levinson_phase_full) at lpc_order == MAXP: 0 keeps the generic one everywhere
+// (diagnostic build, and the switch for an instance whose own A/B loses with it).
+#ifndef FLACENC_SOLVER_FULL_ORDER
+#define FLACENC_SOLVER_FULL_ORDER 1
+#endif
 #ifndef FLACENC_WAVE_OCC
 // 3 where the instance fits 168 VGPRs with (next to) nothing of its common path in scratch -- checked with
 // tools/kernel_resources.py and the Spill / Reload comments of tools/asm_variant.sh's output, then measured
@@ -923,6 +928,35 @@ __device__ __attribute__((noinline)) void levinson_phase_cold(const double* rsrc
   levinson_phase<MAXP, false>(rsrc, P, precision, xq_row, coefs_out, 0u, 0, false);
 }
 
+// levinson_phase for lpc_order == MAXP on R[] summed in this kernel: the straight-line solver (levinson_quantize_full).
+// Bit 2 of the return value: the generic code would have left the straight line (a skipped step, R[0] == 0, a status) --
+// what this call wrote is to be overwritten by levinson_phase on the same arguments.
+// -DFLACENC_SOLVER_FORCE_REDO (diagnostic build): every workgroup takes that second solve.
+template <int MAXP, bool CERT>
+__device__ __forceinline__ int levinson_phase_full(const double* rsrc, int precision, int32_t* xq_row, double* coefs_out,
+                                                   uint32_t max_abs_s, int n_sum, bool do_cert) {
+  double coef[MAXP];
+  int32_t cqv[MAXP];
+  int warm_v, shift_v;
+  bool certified = true, tier2 = false;
+  bool redo = levinson_quantize_full<MAXP, CERT>(rsrc, precision, coef, cqv, &warm_v, &shift_v, max_abs_s, n_sum, &certified,
+                                                 &tier2, do_cert);
+#ifdef FLACENC_SOLVER_FORCE_REDO
+  redo = true;
+#endif
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) xq_row[i] = cqv[i];
+  xq_row[12] = warm_v;
+  xq_row[13] = shift_v;
+  xq_row[14] = FLACENC_HIP_SUBFRAME_OK;
+  if (coefs_out) {
+#pragma unroll
+    for (int i = 0; i < MAXP; ++i) coefs_out[i] = coef[i];
+    for (int i = MAXP; i < 32; ++i) coefs_out[i] = 0.0;
+  }
+  return (certified ? 1 : 0) | (tier2 ? 2 : 0) | (redo ? 4 : 0);
+}
+
 // DECIDE (stereo only): run encode_subframe's candidate choice and try_stereo_coding's channel
 // assignment (coding.rs:384-418 without the fixed-LPC candidate, :493-522) on the device and
 // write one flacenc_hip_stereo_frame_result + the TWO chosen residual rows per frame.
@@ -1376,9 +1410,22 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
       if (sfl >= a.n_subframes) sfl = a.n_subframes - 1u;
       if (lane < 4) {
         __builtin_amdgcn_s_setprio(3);  // the other three waves of the workgroup wait for this one
-        const int fl = levinson_phase<MAXP, kCertSupported>(xr + lane * XR, P, (int)a.precision, xq + lane * 16,
-                                                            a.lpc_coefs ? a.lpc_coefs + (size_t)sfl * 32 : nullptr,
-                                                            kCertSupported ? xm[lane] : 0u, kWaveN, certify);
+        // lpc_order is uniform over the launch: at the instance's own MAXP the straight-line form of the solver
+        // (levinson_phase_full); at every other order, and on R[] that was handed in (which keeps the generic code's
+        // tests), today's generic one.  A workgroup in which a lane's system left the straight line -- a zero denominator,
+        // digital silence, a status: rare by nature -- is solved once more by the same generic code, all four lanes of it,
+        // and keeps that result.  (One inlined copy of the generic code behind a uniform branch serves both.  Out of line
+        // it would be a call in front of the three below, and one more value than the callee-saved registers hold is
+        // live across it: a scratch store and reload per wave on the common path.)
+        double* const coefs_dst = a.lpc_coefs ? a.lpc_coefs + (size_t)sfl * 32 : nullptr;
+        const uint32_t mabs = kCertSupported ? xm[lane] : 0u;
+        int fl = 4;
+        if (FLACENC_SOLVER_FULL_ORDER != 0 && P == MAXP && !from_in)
+          fl = levinson_phase_full<MAXP, kCertSupported>(xr + lane * XR, (int)a.precision, xq + lane * 16, coefs_dst, mabs,
+                                                         kWaveN, certify);
+        if (__builtin_amdgcn_ballot_w64((fl & 4) != 0) != 0ull)
+          fl = levinson_phase<MAXP, kCertSupported>(xr + lane * XR, P, (int)a.precision, xq + lane * 16, coefs_dst, mabs,
+                                                    kWaveN, certify);
         __builtin_amdgcn_s_setprio(0);
         certified = (fl & 1) != 0;
         need_rows = (fl & 2) != 0;
