@@ -433,9 +433,9 @@ __device__ __forceinline__ unsigned long long plane_sum_any64(const PlaneSums& p
 // whatever the span (typical material: one group).
 // Table entries Wp[j] = table[p_base + j] - 4 of this lane's 64-sample partition (see rice_search).
 // EXACT: from the bit-planes; otherwise the literal chunk-clamped sums of rice.rs:75-98 from e[].
-// NOSAT (only with EXACT; chosen per subframe, see rice_nosat_ok): no entry of any level can reach the
+// NOSAT (only with EXACT; chosen per subframe, see rice_search_scatter): no entry of any level can reach the
 // saturation value and every parameter of the window is legal or provably losing, so the clamps and the
-// validity selects are dropped and the entries are kept pre-shifted (W << 5) for the packed minimiser.
+// validity selects are dropped and entry j carries its additive tag, (W << 8) + j.
 template <bool EXACT, bool NOSAT = false, int SPL = 64, int NP>
 __device__ __forceinline__ void rice_build_tables(const PlaneSums& ps, const int32_t* e, uint32_t len0,
                                                   uint32_t p_base, uint32_t max_p, int lane, int warm,
@@ -448,7 +448,7 @@ __device__ __forceinline__ void rice_build_tables(const PlaneSums& ps, const int
       uint32_t sum;
       if (j == 0) sum = (pp == 0) ? 2u * ps.sum_m + ps.negs : plane_sum_ge1(ps, pp);
       else sum = plane_sum_ge1(ps, pp);
-      Wp[j] = (sum + len0 * (pp + 1u)) << 5;
+      Wp[j] = ((sum + len0 * (pp + 1u)) << 8) + (uint32_t)j;
     }
   } else if (EXACT) {
 #pragma unroll
@@ -489,9 +489,9 @@ __device__ __forceinline__ void rice_build_tables(const PlaneSums& ps, const int
   }
 }
 
-// Levels 0..6 of one group of 8 parameters: merges in place (afterwards Wp holds, on lane 0, the table of
+// Levels 0..6 of one group of NP parameters: merges in place (afterwards Wp holds, on lane 0, the table of
 // all 64 partitions merged) and lowers pk[level] to the group's packed minimum (bits << 5 | p).
-template <bool NOSAT = false, int NP = 8>
+template <int NP>
 __device__ __forceinline__ void rice_group_levels(uint32_t (&Wp)[NP], uint32_t (&pk)[7], uint32_t p_base,
                                                   bool finest_only) {
   constexpr uint32_t kWMax = kMaxPToBits - 4u;  // (the packed minimiser takes the entries in pairs, an odd last one alone)
@@ -502,17 +502,17 @@ __device__ __forceinline__ void rice_group_levels(uint32_t (&Wp)[NP], uint32_t (
       _Pragma("unroll") for (int j = 0; j < NP; ++j) part[j] = from_upper_half<S>(Wp[j]);     \
       _Pragma("unroll") for (int j = 0; j < NP; ++j) {                                        \
         uint32_t v = Wp[j] + part[j];                                                         \
-        Wp[j] = NOSAT ? v : (v < kWMax ? v : kWMax);                                          \
+        Wp[j] = v < kWMax ? v : kWMax;                                                        \
       }                                                                                       \
     }                                                                                         \
     uint32_t packed = pk[K];                                                                  \
     _Pragma("unroll") for (int j = 0; j + 1 < NP; j += 2) {                                   \
-      const uint32_t c0 = (NOSAT ? Wp[j] : (Wp[j] << 5)) | (p_base + (uint32_t)j);            \
-      const uint32_t c1 = (NOSAT ? Wp[j + 1] : (Wp[j + 1] << 5)) | (p_base + (uint32_t)j + 1u); \
+      const uint32_t c0 = (Wp[j] << 5) | (p_base + (uint32_t)j);                              \
+      const uint32_t c1 = (Wp[j + 1] << 5) | (p_base + (uint32_t)j + 1u);                     \
       packed = umin3(packed, c0, c1);                                                         \
     }                                                                                         \
     if (NP & 1) {                                                                             \
-      const uint32_t cl = (NOSAT ? Wp[NP - 1] : (Wp[NP - 1] << 5)) | (p_base + (uint32_t)(NP - 1)); \
+      const uint32_t cl = (Wp[NP - 1] << 5) | (p_base + (uint32_t)(NP - 1));                  \
       packed = cl < packed ? cl : packed;                                                     \
     }                                                                                         \
     pk[K] = packed;                                                                           \
@@ -529,29 +529,115 @@ __device__ __forceinline__ void rice_group_levels(uint32_t (&Wp)[NP], uint32_t (
 #undef FLACENC_RICE_LEVEL
 }
 
-// [p_lo, p_hi] is the parameter window (rice_window below); groups of 4: typical material -- partitions whose
-// means lie within a factor of two of each other -- needs exactly one, and a wider window just takes more turns
-// of the rolled loop (a group of 8 evaluated twice the entries for the common case).
-template <bool EXACT, bool NOSAT = false, int SPL = 64>
+// The common case of the search (rice_window: all partition means within two binades, nothing configured away), one
+// group of four parameters p_lo .. p_lo + 3 with the merges as a reduce-scatter -- the trick of lane_order_reduce.
+// Entry j of a table is  E_j = (W_j << 8) + j  (rice_build_tables, NOSAT).  A merge is a plain add; at level K the tag
+// has grown to j 2^K <= 192, so the minimum of the E_j orders by W first and then by j -- the minimiser's (bits << 5 | p)
+// with ties to the smaller parameter -- and  bits = (E >> 8) + 4,  p = p_lo + ((E & 255) >> K).
+// Nothing saturates: sum_i (u_i >> p) <= s0 >> p_lo < 512 on every lane (s0 < 64 * 2^(p0max + 1) and p_lo >= p0max - 2),
+// so below 2^15 over the wave, and len (p + 1) <= 4096 * 32 adds at most 2^17: every entry of every level is below 2^18.
+// Parameters of the group above max_p = bitlen are legal but losing (entry len (p + 1), strictly above the one at bitlen).
+//   level 0: every lane holds its partition's four entries;
+//   level 1: the lanes of a pair trade halves -- the even lane ends up with entries {0, 1} of the pair's table, the odd
+//            lane with {2, 3};
+//   level 2: the pairs of a quad trade again and every lane keeps ONE entry, number 2 (lane & 1) + ((lane >> 1) & 1);
+//   levels 3..6: a group's table sits on its first quad, one add per level fetches the partner quad's.
+// A level's minimum is two quad butterflies (one in-lane min and one butterfly at level 1), replicated over the quad, so
+// pk[K] is valid on every lane that is a multiple of 2^K as the level totals expect.
+__device__ __forceinline__ RiceResult rice_search_scatter(const PlaneSums& ps, uint32_t len0, uint32_t p_lo, int lane) {
+  uint32_t E[4], pk[7];
+  rice_build_tables<true, true>(ps, nullptr, len0, p_lo, 0u, lane, 0, E);
+#define FLACENC_QUAD_MIN(v, CTRL)                                                                        \
+  {                                                                                                      \
+    const uint32_t o_ = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)(v), CTRL, 0xF, 0xF, false); \
+    v = o_ < v ? o_ : v;                                                                                 \
+  }
+  const uint32_t m0 = umin3(E[0], E[1], E[2]);
+  pk[0] = E[3] < m0 ? E[3] : m0;
+  // quad_perm [1,0,3,2] = 0xB1: the other lane of the pair; quad_perm [2,3,0,1] = 0x4E: the other pair of the quad
+  const bool odd = (lane & 1) != 0, second = (lane & 2) != 0;
+  const uint32_t a0 = (odd ? E[2] : E[0]) + FLACENC_DPP(odd ? E[0] : E[2], 0xB1, 0xF);
+  const uint32_t a1 = (odd ? E[3] : E[1]) + FLACENC_DPP(odd ? E[1] : E[3], 0xB1, 0xF);
+  uint32_t m = a0 < a1 ? a0 : a1;
+  FLACENC_QUAD_MIN(m, 0xB1)
+  pk[1] = m;
+  uint32_t t = (second ? a1 : a0) + FLACENC_DPP(second ? a0 : a1, 0x4E, 0xF);
+#define FLACENC_SCATTER_LEVEL(K, PARTNER) \
+  if (K > 2) t += (PARTNER);              \
+  m = t;                                  \
+  FLACENC_QUAD_MIN(m, 0xB1)               \
+  FLACENC_QUAD_MIN(m, 0x4E)               \
+  pk[K] = m;
+  FLACENC_SCATTER_LEVEL(2, 0u)
+  FLACENC_SCATTER_LEVEL(3, from_upper_half<4>(t))
+  FLACENC_SCATTER_LEVEL(4, from_upper_half<8>(t))
+  FLACENC_SCATTER_LEVEL(5, from_upper_half<16>(t))
+  // (lane + 32: v_permlane32_swap hands the lower half the upper half's value; from_upper_half<32> is lane 32's alone)
+  FLACENC_SCATTER_LEVEL(6, __builtin_amdgcn_permlane32_swap(t, t, false, false)[1])
+#undef FLACENC_SCATTER_LEVEL
+#undef FLACENC_QUAD_MIN
+
+  // Level totals by ONE triangular reduction instead of seven wave sums (round 5): level K's minima live on the lanes
+  // that are multiples of 2^K, so their sum needs only the tree levels from K on -- at spacing S the leaders of 2 S
+  // add their partner's running totals of every level below log2(2 S): 1 + 2 + 3 + 4 + 5 + 6 = 21 adds (fifteen of
+  // them with the fetch folded in as a DPP operand or done by the LDS crossbar) where seven full sums took 42 and the
+  // leader masks 21 more.  No minimum can have saturated, totals fit 32 bits.  Lane 0 ends up with all seven.
+  uint32_t tot[7];
+#pragma unroll
+  for (int K = 0; K < 7; ++K) tot[K] = (pk[K] >> 8) + 4u;
+  tot[0] += from_upper_half<1>(tot[0]);
+#pragma unroll
+  for (int K = 0; K < 2; ++K) tot[K] += from_upper_half<2>(tot[K]);
+#pragma unroll
+  for (int K = 0; K < 3; ++K) tot[K] += from_upper_half<4>(tot[K]);
+#pragma unroll
+  for (int K = 0; K < 4; ++K) tot[K] += from_upper_half<8>(tot[K]);
+#pragma unroll
+  for (int K = 0; K < 5; ++K) tot[K] += from_upper_half<16>(tot[K]);
+#pragma unroll
+  for (int K = 0; K < 6; ++K) tot[K] += from_upper_half<32>(tot[K]);
+  // strict < keeps the finer order on ties (rice.rs:285); everything below is wave-uniform
+  uint32_t best = (uint32_t)__builtin_amdgcn_readfirstlane((int)tot[0]);
+  int bk = 0;
+#pragma unroll
+  for (int K = 1; K < 7; ++K) {
+    const uint32_t lvl = (uint32_t)__builtin_amdgcn_readfirstlane((int)tot[K]);
+    if (lvl < best) {
+      best = lvl;
+      bk = K;
+    }
+  }
+  RiceResult r;
+  r.best_bits = best;
+  r.bestk = bk;
+  uint32_t mp = pk[0];
+#pragma unroll
+  for (int K = 1; K < 7; ++K) mp = (bk == K) ? pk[K] : mp;
+  r.my_p = p_lo + ((mp & 255u) >> bk);
+  r.saturated = false;
+  r.sat_levels = 0;
+  return r;
+}
+
+// [p_lo, p_hi] is the parameter window (rice_window below) in groups of 4, what the window spans when the partition
+// means straddle one binade; a wider window just takes more turns of the rolled loop.  Correct for every input: the
+// entries are clamped as the reference clamps them.
+template <bool EXACT, int SPL = 64>
 __device__ __forceinline__ RiceResult rice_search(const PlaneSums& ps, const int32_t* e, uint32_t len0,
                                                   uint32_t p_lo, uint32_t p_hi, uint32_t max_p, bool small_bits,
                                                   int lane, int warm, bool finest_only) {
-  // (groups of 5 since round 5: the window is p0min - 2 .. p0max + 1, four wide when all partition means share a binade and
-  // five when they straddle one -- two thirds of the bench signal's subframes, which took a second turn of the loop for it)
 #ifndef FLACENC_RICE_NP
-#define FLACENC_RICE_NP 5
+#define FLACENC_RICE_NP 4
 #endif
   constexpr int NP = EXACT ? FLACENC_RICE_NP : 8;
-  constexpr uint32_t kWMax = kMaxPToBits - 4u;
-  (void)kWMax;
   uint32_t pk[7];
 #pragma unroll
   for (int k = 0; k < 7; ++k) pk[k] = 0xFFFFFFFFu;
 #pragma unroll 1
   for (uint32_t p_base = p_lo; p_base <= p_hi; p_base += (uint32_t)NP) {
     uint32_t Wp[NP];
-    rice_build_tables<EXACT, NOSAT, SPL>(ps, e, len0, p_base, max_p, lane, warm, Wp);
-    rice_group_levels<NOSAT>(Wp, pk, p_base, finest_only);
+    rice_build_tables<EXACT, false, SPL>(ps, e, len0, p_base, max_p, lane, warm, Wp);
+    rice_group_levels(Wp, pk, p_base, finest_only);
   }
 
   RiceResult r;
@@ -560,46 +646,6 @@ __device__ __forceinline__ RiceResult rice_search(const PlaneSums& ps, const int
   r.my_p = 0;
   r.saturated = false;
   uint32_t sat_any = 0;
-  if (NOSAT && !finest_only) {
-    // Level totals by ONE triangular reduction instead of seven wave sums (round 5): level K's minima live on the lanes
-    // that are multiples of 2^K, so their sum needs only the tree levels from K on -- at spacing S the leaders of 2 S
-    // add their partner's running totals of every level below log2(2 S): 1 + 2 + 3 + 4 + 5 + 6 = 21 adds (fifteen of
-    // them with the fetch folded in as a DPP operand or done by the LDS crossbar) where seven full sums took 42 and the
-    // leader masks 21 more.  NOSAT: no minimum can have saturated, totals fit 32 bits.  Lane 0 ends up with all seven.
-    uint32_t t[7];
-#pragma unroll
-    for (int K = 0; K < 7; ++K) t[K] = (pk[K] >> 5) + 4u;
-    t[0] += from_upper_half<1>(t[0]);
-#pragma unroll
-    for (int K = 0; K < 2; ++K) t[K] += from_upper_half<2>(t[K]);
-#pragma unroll
-    for (int K = 0; K < 3; ++K) t[K] += from_upper_half<4>(t[K]);
-#pragma unroll
-    for (int K = 0; K < 4; ++K) t[K] += from_upper_half<8>(t[K]);
-#pragma unroll
-    for (int K = 0; K < 5; ++K) t[K] += from_upper_half<16>(t[K]);
-#pragma unroll
-    for (int K = 0; K < 6; ++K) t[K] += from_upper_half<32>(t[K]);
-    // strict < keeps the finer order on ties (rice.rs:285); everything below is wave-uniform
-    uint32_t best = (uint32_t)__builtin_amdgcn_readfirstlane((int)t[0]);
-    int bk = 0;
-#pragma unroll
-    for (int K = 1; K < 7; ++K) {
-      const uint32_t tot = (uint32_t)__builtin_amdgcn_readfirstlane((int)t[K]);
-      if (tot < best) {
-        best = tot;
-        bk = K;
-      }
-    }
-    r.best_bits = best;
-    r.bestk = bk;
-    uint32_t mp = pk[0];
-#pragma unroll
-    for (int K = 1; K < 7; ++K) mp = (bk == K) ? pk[K] : mp;
-    r.my_p = mp & 31u;
-    r.sat_levels = 0;
-    return r;
-  }
   // level totals: the group leaders' minima summed over the wave; strict < keeps the finer order on
   // ties (rice.rs:285)
 #pragma unroll
@@ -643,7 +689,7 @@ __device__ __attribute__((noinline)) void rice_search_literal(const int32_t* e, 
 #pragma unroll
   for (int k = 0; k < 7; ++k) none.q[k] = 0;
   none.sum_m = none.negs = 0;
-  RiceResult rr = rice_search<false, false, SPL>(none, ev, len0, 0u, max_p, max_p, small_bits != 0, lane, warm, finest_only != 0);
+  RiceResult rr = rice_search<false, SPL>(none, ev, len0, 0u, max_p, max_p, small_bits != 0, lane, warm, finest_only != 0);
   // the table sums of this path are the reference's wrapping u32 adds (rice.rs:88-93): code_bits
   // does not determine the true quotient sum any more, saturated or not -- always count it
   rr.saturated = true;
@@ -1961,19 +2007,21 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
   unsigned long long sat_sum_q = 0;  // exact sum of quotients, only evaluated if a minimum saturated
   // (the exact sums of a partition must fit 32 bits: 64 codes below 2^26, 72 codes below 2^25)
   if (maxu < (1u << (SPL == 64 ? 26 : 25))) {
-    // rice_window: a lower end for the parameter search.  For a partition (or merged group)
-    // with sum S over len samples and mean m = S / len let p0 = floor(log2(m + 1)).  From
-    // S/2^p - len < sum_i (u_i >> p) <= S/2^p:  table[p0] - 4 < len (p0 + 3)  and, for
-    // p <= p0 - 3,  table[p] - 4 > len (m / 2^p + p) >= len (p0 + 4).  So no p <= p0 - 3 can
-    // win or tie.  A group's mean is at least the smallest 64-sample partition mean, so the
-    // wave-minimum of the (conservatively rounded) per-lane p0 bounds every order.  If the
-    // configured max_p lies below that, the same inequalities leave max_p as the only candidate.
+    // rice_window: a lower end for the parameter search.  For a partition (or merged group) with sum S over len
+    // samples and mean m = S / len let p0 = floor(log2(m + 1)); table[p] = 4 + sum_i (u_i >> p) + len (p + 1).
+    // With v = u_i >> (p - 1):  v - (v >> 1) = ceil(v / 2) >= v / 2,  and  sum_i (u_i >> (p - 1)) > S / 2^(p - 1) - len,
+    // so  table[p - 1] - table[p] = sum_i ceil(v_i / 2) - len > S / 2^p - 1.5 len,  positive whenever m >= 1.5 * 2^p.
+    // For p0 >= 2 and p <= p0 - 1 that holds: m >= 2^p0 - 1 >= 0.75 * 2^p0 >= 1.5 * 2^p.  The entries fall strictly
+    // as p rises up to p0 - 1, and no p <= p0 - 2 can win or tie (for p0 < 2 there is no such p).  A group's mean is at
+    // least the smallest 64-sample partition mean, so the wave-minimum of the (conservatively rounded) per-lane p0
+    // bounds every order.  If the configured max_p lies below that, the same inequality leaves max_p as the only
+    // candidate.
     const uint32_t s0 = 2u * ps.sum_m + ps.negs;  // sum of the lane's codes (< 2^32, see above)
     const uint32_t q0 = (s0 >> 6) + 1u;
     // (72-sample partitions: floor(S / 128) + 1 <= S / 72 + 1 keeps the lower end conservative)
     const uint32_t q0lo = SPL == 64 ? q0 : (s0 >> 7) + 1u;
     const uint32_t p0min = wave_min_dpp(31u - (uint32_t)__builtin_clz(q0lo));
-    uint32_t p_lo = p0min > 2u ? p0min - 2u : 0u;
+    uint32_t p_lo = p0min > 1u ? p0min - 1u : 0u;
     p_lo = p_lo < max_p ? p_lo : max_p;
     // Upper end: table[p + 1] - table[p] = len - sum_i ceil((u_i >> p) / 2) >= len - S / 2^p, which is positive
     // as soon as 2^p > m; 2^(p0 + 1) > m + 1, so from p0 + 1 on the entries grow strictly and no p > p0 + 1 can
@@ -1985,20 +2033,12 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
     const uint32_t p0max = wave_max_dpp(31u - (uint32_t)__builtin_clz(q0hi));
     uint32_t p_hi = p0max + 1u;
     p_hi = p_hi < max_p ? p_hi : max_p;
-    // NOSAT: (1) the configured limit does not cut the search (max_p == bitlen), so a parameter above
-    // max_p inside the last group of 8 is legal-but-losing -- for p > bitlen every table entry is
-    // len (p + 1), strictly above the entry at p = bitlen -- and needs no masking; (2) bitlen <= 24 keeps
-    // every shift amount below 32; (3) no entry of any level reaches the saturation value: an entry of the
-    // fully merged table is at most sum u + 4096 * 32, and the sum of the lanes' code sums is bounded from
-    // their 64-sample means.  Then clamps never bind and the search equals the clamped one.
-    // (Not in the fixed-LPC variants: a second instance of the search inside their candidate loop costs
-    // them 35 more spilled dwords at 168 registers.)
-    bool nosat = false;
-    if (!FIXED) {
-      const uint32_t tot_hi = wave_sum_dpp(s0 >> 6);  // sum over lanes of floor(s0 / 64): < 2^32
-      nosat = small_bits && bitlen <= 24u && tot_hi < ((kMaxPToBits - 4u - (uint32_t)kWaveN * 32u) >> 6) - 64u;
-    }
-    if (!FIXED && nosat) rr = rice_search<true, true>(ps, nullptr, len0, p_lo, p_hi, max_p, small_bits, lane, warm, finest_only);
+    // The common case takes rice_search_scatter: the configured limit does not cut the search (max_p == bitlen, and
+    // p0min <= bitlen since floor(s0 / 64) <= maxu, so the clamp of p_lo did not bind) and the partition means lie
+    // within two binades, so the window [p0min - 1, p0max + 1] fits its one group of four and nothing can saturate.
+    // (Not in the fixed-LPC variants: a second instance of the search inside their candidate loop costs them spills.)
+    if (!FIXED && SPL == 64 && small_bits && !finest_only && p0max - p0min <= 1u)
+      rr = rice_search_scatter(ps, len0, p_lo, lane);
     else rr = rice_search<true>(ps, nullptr, len0, p_lo, p_hi, max_p, small_bits, lane, warm, finest_only);
     // The window argument compares unclamped table values.  If any group minimum saturated at
     // MAX_P_TO_BITS, clamped entries outside the window could tie with it (ties go to the
