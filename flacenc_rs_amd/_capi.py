@@ -845,7 +845,10 @@ class Handle:
         return st.cpu().numpy().view(np.uint32)
 
     def index_frames(self, data, channels: int, bits_per_sample: int, max_frames: int):
-        """flacenc_hip_index_frames_async on a host buffer of frames -> (offsets uint64, lengths uint32, ok)."""
+        """flacenc_hip_index_frames_async on a host buffer of frames -> (offsets uint64, lengths uint32, ok).
+        ok is False (FLACENC_HIP_INDEX_ERROR) when the chain from byte 0 does not end at the buffer's end, holds more than
+        max_frames frames, or when the buffer holds more candidate headers than max_frames + max_frames // 4 + 4096 (a
+        larger max_frames clears that); the frames returned are then a verified prefix of the chain."""
         import torch
         buf = self._device_copy(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data)
         off = torch.zeros(max(1, max_frames), dtype=torch.int64, device="cuda")

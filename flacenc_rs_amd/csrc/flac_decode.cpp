@@ -290,7 +290,8 @@ __global__ void __launch_bounds__(256) cand_write_kernel(const uint8_t* __restri
     }
 }
 
-// jump[0][i]: the candidate that starts where candidate i ends, kEnd at n_bytes, kDead otherwise
+// jump[0][i]: the valid candidate (skim and CRC-16 passed) that starts where candidate i ends, kEnd at n_bytes, kDead
+// otherwise -- so a chain only ever walks over verified frames, also when candidates were dropped at `capacity`
 __global__ void __launch_bounds__(256) link_kernel(const uint64_t* __restrict__ cand_pos,
                                                    const FrameRec* __restrict__ recs, const uint32_t* __restrict__ n_dev,
                                                    uint32_t capacity, uint64_t n_bytes, uint32_t* __restrict__ jump) {
@@ -309,7 +310,7 @@ __global__ void __launch_bounds__(256) link_kernel(const uint64_t* __restrict__ 
         if (cand_pos[mid] < e) lo = mid + 1;
         else hi = mid;
       }
-      if (lo < n && cand_pos[lo] == e) nx = lo;
+      if (lo < n && cand_pos[lo] == e && recs[lo].status == 0) nx = lo;
     }
   }
   jump[i] = nx;
@@ -325,16 +326,19 @@ __global__ void __launch_bounds__(256) jump_kernel(const uint32_t* __restrict__ 
 }
 
 // one thread: the length of the chain from candidate 0 by binary lifting over the jump levels
-__global__ void chain_kernel(const uint64_t* __restrict__ cand_pos, const uint32_t* __restrict__ jump,
-                             uint32_t levels, uint32_t* __restrict__ counters, uint32_t capacity, uint64_t n_bytes,
-                             uint64_t max_frames, uint64_t* __restrict__ n_frames) {
+__global__ void chain_kernel(const uint64_t* __restrict__ cand_pos, const FrameRec* __restrict__ recs,
+                             const uint32_t* __restrict__ jump, uint32_t levels, uint32_t* __restrict__ counters,
+                             uint32_t capacity, uint64_t n_bytes, uint64_t max_frames,
+                             uint64_t* __restrict__ n_frames) {
   const uint32_t total = counters[0], n = min(total, capacity);
+  // candidates past `capacity` (the highest positions) were dropped: what the chain reaches is still a verified
+  // prefix, but it may stop early, so the caller is told to come back with a larger max_frames
   uint64_t err = total > capacity ? kIndexError : 0;
   uint64_t count = 0;
   if (n_bytes == 0) {
     // an empty buffer holds no frame and no error
-  } else if (n == 0 || cand_pos[0] != 0) {
-    err = kIndexError;
+  } else if (n == 0 || cand_pos[0] != 0 || recs[0].status != 0) {
+    err = kIndexError;  // no verified frame at byte 0
   } else {
     uint32_t cur = 0;
     count = 1;
@@ -444,8 +448,8 @@ hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t 
       hipLaunchKernelGGL(jump_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream,
                          jump + static_cast<size_t>(k - 1) * cap, jump + static_cast<size_t>(k) * cap, counters, cap);
   }
-  hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1), 0, stream, cand_pos, jump, levels, counters, cap, n_bytes,
-                     static_cast<uint64_t>(max_frames), n_frames);
+  hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1), 0, stream, cand_pos, recs, jump, levels, counters, cap,
+                     n_bytes, static_cast<uint64_t>(max_frames), n_frames);
   if (max_frames)
     hipLaunchKernelGGL(enumerate_kernel, dim3(ceil_div(max_frames < cap ? max_frames : cap, 256)), dim3(256), 0,
                        stream, cand_pos, recs, jump, levels, counters, cap, offsets, lengths);

@@ -756,7 +756,12 @@ int flacenc_hip_set_host_threads(flacenc_hip_handle* h, int threads);
  * parsed for its length and CRC-16, and the frames are exactly those reachable from byte 0 by "the next frame starts
  * where this one ends" (resolved on the device by pointer jumping), so a header planted inside a frame is never one.
  * offsets / lengths receive at most max_frames frames in stream order; n_frames[0] = the number written, with
- * FLACENC_HIP_INDEX_ERROR set when that chain does not end exactly at n_bytes or holds more than max_frames frames.
+ * FLACENC_HIP_INDEX_ERROR set when that chain does not end exactly at n_bytes or holds more than max_frames frames, and
+ * also when the buffer holds more candidate headers (planted ones included) than max_frames + max_frames / 4 + 4096, the
+ * room of the candidate table: the candidates at the highest positions are then dropped and the chain may stop early.
+ * A caller clears that by passing a larger max_frames.  With or without the flag the frames written are a verified prefix
+ * of the chain: each passed its header checks and CRC-16 and starts where the one before it ends, the first at byte 0
+ * (so a stream cut inside its last frame gives the frames before it), and nothing is written past that count.
  * Scratch (the per-frame skim records, the candidates) comes from the handle.
  */
 #define FLACENC_HIP_DECODE_BAD_HEADER 1u       /* no sync code, a reserved code or a malformed coded number */

@@ -80,14 +80,23 @@ def _residual(br, n, order):
     return out
 
 
-def _subframe(br, n, bps):
+def _subframe(br, n, bps, wasted_ok=False):
     assert br.u(1) == 0
     typ = br.u(6)
-    assert br.u(1) == 0, "wasted bits are not produced by this encoder"
+    if br.u(1):
+        assert wasted_ok, "wasted bits are not produced by this encoder"
+        k = br.unary() + 1
+        assert k < bps
+        x, kind, order = _subframe_body(br, n, bps - k, typ)
+        return x << k, kind, order
+    return _subframe_body(br, n, bps, typ)
+
+
+def _subframe_body(br, n, bps, typ):
     if typ == 0:
-        return np.full(n, br.s(bps), np.int64), "constant"
+        return np.full(n, br.s(bps), np.int64), "constant", 0
     if typ == 1:
-        return np.array([br.s(bps) for _ in range(n)], np.int64), "verbatim"
+        return np.array([br.s(bps) for _ in range(n)], np.int64), "verbatim", 0
     if 8 <= typ <= 12:
         order = typ - 8
         coefs, shift, kind = FIXED_COEFS[order], 0, "fixed"
@@ -106,12 +115,13 @@ def _subframe(br, n, bps):
     for t in range(order, n):
         pred = sum(int(c) * int(out[t - 1 - j]) for j, c in enumerate(coefs))
         out[t] += pred >> shift
-    return out, kind
+    return out, kind, order
 
 
-def parse_frame(data, stream_bps=None, stream_rate=None):
+def parse_frame(data, stream_bps=None, stream_rate=None, wasted_ok=False):
     """-> dict(header fields, channels = int64 [nch, n] after undoing the stereo decorrelation,
-    kinds, length = bytes consumed).  Asserts the sync code, reserved bits and both CRCs."""
+    kinds, orders, length = bytes consumed).  Asserts the sync code, reserved bits and both CRCs, and -- unless
+    wasted_ok -- that no subframe carries wasted bits."""
     data = bytes(data)
     br = Bits(data)
     assert br.u(14) == 0x3FFE, "sync code"
@@ -149,12 +159,13 @@ def parse_frame(data, stream_bps=None, stream_rate=None):
     assert bps is not None
     nch = ch_tag + 1 if ch_tag < 8 else 2
     assert ch_tag <= 10
-    subs, kinds = [], []
+    subs, kinds, orders = [], [], []
     for c in range(nch):
         side = (ch_tag == 8 and c == 1) or (ch_tag == 9 and c == 0) or (ch_tag == 10 and c == 1)
-        x, kind = _subframe(br, n, bps + (1 if side else 0))
+        x, kind, order = _subframe(br, n, bps + (1 if side else 0), wasted_ok)
         subs.append(x)
         kinds.append(kind)
+        orders.append(order)
     br.pos = (br.pos + 7) // 8 * 8
     body_len = br.pos // 8
     assert br.u(16) == crc16(data[:body_len]), "frame CRC-16"
@@ -167,4 +178,5 @@ def parse_frame(data, stream_bps=None, stream_rate=None):
         mid = (mid << 1) | (side & 1)
         subs = [(mid + side) >> 1, (mid - side) >> 1]
     return {"variable": variable, "number": number, "block_size": n, "sample_rate": rate, "bps": bps,
-            "channel_tag": ch_tag, "channels": np.stack(subs), "kinds": kinds, "length": br.pos // 8}
+            "channel_tag": ch_tag, "channels": np.stack(subs), "kinds": kinds, "orders": orders,
+            "length": br.pos // 8}
