@@ -669,6 +669,16 @@ class Handle:
         self._check(rc)
         return params, residual, keys
 
+    def fixed_lpc_batch_device(self, cfg: FrameConfig, samples_ptr: int, n_units: int, block_size: int, stride: int,
+                               bps_ptr: int | None, bits_per_sample: int, layout: int, params_ptr: int,
+                               residual_ptr: int, residual_stride: int, selector_keys_ptr: int | None,
+                               stream: int | None = None):
+        """flacenc_hip_fixed_lpc_batch_async: device pointers (bps_ptr None: bits_per_sample for every subframe)."""
+        rc = self._lib.flacenc_hip_fixed_lpc_batch_async(
+            self._h, C.byref(cfg), samples_ptr, n_units, block_size, stride, bps_ptr or None, bits_per_sample, layout,
+            params_ptr, residual_ptr, residual_stride, selector_keys_ptr or None, stream or None)
+        self._check(rc)
+
     def pack_stereo_frames(self, frames, results, residual, bits_per_sample: int, sample_rate: int,
                            first_frame_number: int = 0, frame_number_step: int = 1):
         """Frame::write (src/component/bitrepr.rs:289-319) for the frames encode_stereo_frames decided:
@@ -780,6 +790,13 @@ class Handle:
                                                  block_size, out.ctypes.data, block_size, MEM_HOST)
         self._check(rc)
         return out
+
+    def fill_le_bytes_device(self, bytes_ptr: int, total_samples: int, channels: int, bytes_per_sample: int,
+                             n_frames: int, block_size: int, frames_ptr: int, stride: int, stream: int | None = None):
+        """flacenc_hip_fill_le_bytes_async: packed interleaved PCM in HBM -> FrameBuf rows in HBM."""
+        rc = self._lib.flacenc_hip_fill_le_bytes_async(self._h, bytes_ptr, total_samples, channels, bytes_per_sample,
+                                                       n_frames, block_size, frames_ptr, stride, stream or None)
+        self._check(rc)
 
     def encode_pack_stereo_frames_device(self, cfg: FrameConfig, frames_ptr: int, n_frames: int, block_size: int,
                                          stride: int, bits_per_sample: int, sample_rate: int,
