@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_verify_config",
     "flacenc_hip_window_weights",
     "flacenc_hip_set_lpc_windows",
+    "flacenc_hip_set_order_guesses",
     "flacenc_hip_lpc_window_weights",
     "flacenc_hip_qlpc_batch",
     "flacenc_hip_qlpc_batch_async",
@@ -270,6 +271,8 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_window_weights.restype = C.c_int
     L.flacenc_hip_set_lpc_windows.argtypes = [vp, vp, vp, vp, vp, C.c_uint32]
     L.flacenc_hip_set_lpc_windows.restype = C.c_int
+    L.flacenc_hip_set_order_guesses.argtypes = [vp, C.c_uint32]
+    L.flacenc_hip_set_order_guesses.restype = C.c_int
     L.flacenc_hip_lpc_window_weights.argtypes = [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.flacenc_hip_lpc_window_weights.restype = C.c_int
     L.flacenc_hip_synchronize.argtypes = [vp]
@@ -424,6 +427,7 @@ FLAG_INTEGER_PARITY_ONLY = 256  # with FLAG_REFERENCE_SUM_ORDER: certified shape
 FLAG_WASTED_BITS = 512  # frame-level calls code subframes whose low bits are all zero as x >> k at w - k bits
 FLAG_ORDER_SEARCH = 1024  # every LPC candidate's order chosen by an exhaustive search over 1..lpc_order
 FLAG_WINDOW_SEARCH = 2048  # every LPC candidate analysed under the config's window and the handle's extra windows
+FLAG_ORDER_GUESS = 4096  # the LPC order guessed from the Levinson error: (0, P) and K guesses per window are coded
 
 
 def wasted_bits(results) -> np.ndarray:
@@ -559,6 +563,11 @@ class Handle:
         n = len(t)
         ptr = (lambda x: x.ctypes.data) if n else (lambda x: None)
         self._check(self._lib.flacenc_hip_set_lpc_windows(self._h, ptr(t), ptr(a), ptr(s), ptr(e), n))
+
+    def set_order_guesses(self, k: int):
+        """flacenc_hip_set_order_guesses: K of FLAG_ORDER_GUESS, the guessed orders coded per window, 1..32 (a fresh
+        handle holds 1); applies to the calls made after it."""
+        self._check(self._lib.flacenc_hip_set_order_guesses(self._h, int(k)))
 
     def _hook(self, name):
         if not hasattr(self._lib, name):

@@ -40,12 +40,12 @@ __global__ void bitcount_pick_kernel(const unsigned long long* keys, uint32_t n,
 namespace flacenc_hip {
 
 // FLACENC_HIP_FLAG_WINDOW_SEARCH with no extra window is exactly the call with the summation-order flag in its place
-// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call).  Callers of the flagged entry points run their config
-// through this once, after flacenc_hip_verify_config.
+// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call; with FLACENC_HIP_FLAG_ORDER_GUESS: the ORDER_GUESS call).
+// Callers of the flagged entry points run their config through this once, after flacenc_hip_verify_config.
 uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags) {
   if (!(flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) || !h->lpc_windows.empty()) return flags;
   flags &= ~FLACENC_HIP_FLAG_WINDOW_SEARCH;
-  if (flags & FLACENC_HIP_FLAG_ORDER_SEARCH) return flags;
+  if (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS)) return flags;
   flags &= ~(FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY);
   if (!(flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER)) flags |= FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER;
   return flags;
@@ -54,7 +54,7 @@ uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags) {
 // The LPC candidate of a (normalised) config comes from the search over windows and orders (order_search.h): the frame
 // -level calls then take the candidate batches and the stand-alone deciding kernels for every shape.
 bool lpc_search(uint32_t flags) {
-  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH)) != 0;
+  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS)) != 0;
 }
 
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
@@ -365,16 +365,18 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
     a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
   }
   if (order_search) {
-    // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: R[] of every window in the stable build's
-    // order (nightly's with its flag; the certificate and INTEGER_PARITY_ONLY do not apply), every candidate (window,
-    // order) searched, the records written by stage 3
+    // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS: R[] of every window in
+    // the stable build's order (nightly's with its flag; the certificate and INTEGER_PARITY_ONLY do not apply), every
+    // candidate (window, order) searched -- under ORDER_GUESS (0, P) and every window's K guesses, K as the handle holds
+    // it now --, the records written by stage 3
     a.certify = 0;
     a.integer_parity_only = 0;
     a.cert_stats = nullptr;
     flacenc_hip::SearchShape shape{};
     shape.windows[0] = win_dev;
     shape.n_windows = 1;
-    shape.search_orders = (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) ? 1u : 0u;
+    shape.guess_orders = (cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) ? h->order_guesses : 0u;
+    shape.search_orders = ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) || shape.guess_orders) ? 1u : 0u;
     if (cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) {
       for (const LpcWindow& w : h->lpc_windows) {
         const WindowEntry* e = nullptr;

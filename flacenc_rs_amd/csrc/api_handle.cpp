@@ -143,6 +143,19 @@ int flacenc_hip_verify_config(const flacenc_hip_qlpc_config* cfg) {
   // the order search runs on the autocorrelation's R[]; the covariance-method estimator has none
   if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
   if ((cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
+  // the guessed search is a subset of the exhaustive one: one of the two at a time
+  if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) && (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH)) return FLACENC_HIP_ERR_BAD_CONFIG;
+  if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_set_order_guesses(flacenc_hip_handle* h, uint32_t k) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (k < 1 || k > 32) {
+    h->last_error = "flacenc_hip_set_order_guesses: k must be in 1..=32";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->order_guesses = k;
   return FLACENC_HIP_OK;
 }
 

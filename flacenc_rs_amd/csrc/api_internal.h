@@ -169,6 +169,7 @@ struct flacenc_hip_handle {
   flacenc_hip::DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
   // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
   flacenc_hip::DeviceBuffer d_order;
+  uint32_t order_guesses = 1;  // FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window (flacenc_hip_set_order_guesses)
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into

@@ -3,10 +3,13 @@
 // of window j comes from the one R_j[0..P] the reference-order pass produces under that window: levinson_quantize at order
 // o reads lags 0..o only, so candidate (j, o) is bit for bit the order-o run under window j, and candidate (0, P) is the
 // unflagged FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER record.  ORDER_SEARCH alone is the W = 1 case.
+// FLACENC_HIP_FLAG_ORDER_GUESS (section 4.13) runs the same grid of predictors, then order_guess_kernel strikes every
+// candidate that is neither (0, P) nor one of its window's K guesses (order_guess_core.h) before the search codes the rest.
 #include "order_search.h"
 
 #include "acorr_reference.h"
 #include "lds_opt_in.h"
+#include "order_guess_core.h"
 #include "qlpc_kernel_impl.h"
 
 namespace flacenc_hip {
@@ -17,6 +20,7 @@ constexpr int kTabStride = 31;                    // Rice parameters 0..30 per p
 constexpr uint32_t kMaxBits = (1u << 27) - 1u;    // MAX_P_TO_BITS, rice.rs:51
 constexpr uint32_t kWideU = 1u << 27;             // zig-zag codes from here on can wrap a 16-sample chunk's u32 sum
 constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, 0 (levinson_batch_kernel's record)
+constexpr int32_t kNotCandidate = 0x40000000;     // order_guess_kernel's status word of a candidate the search skips
 constexpr size_t kSmallBytes = 1024 + 16 * 8 + 2 * 8 + 16 * 4 + 256 + 256;  // psum, level bits, sums, misc, two ps rows
 
 enum { kMaxAbs = 0, kUMax, kSat, kLo, kHi, kRice2, kClamp };
@@ -71,10 +75,11 @@ __device__ __forceinline__ void candidate_of(uint32_t c, uint32_t P, uint32_t Pc
 }
 
 // candidate c of subframe sf at [(sf * C + c) * 36]: levinson_quantize on R_j[0..o] (lpc.rs:633-705, 273-302)
-template <int MAXP>
+// REFL (the order guess): k_o, the candidate's unquantised coefficient number o - 1, at refl[sf * C + c] as well
+template <int MAXP, bool REFL>
 __global__ void __launch_bounds__(64) order_levinson_kernel(const double* __restrict__ racc, uint32_t n_subframes,
                                                              uint32_t W, uint32_t P, uint32_t Pc, uint32_t precision,
-                                                             int32_t* __restrict__ cand) {
+                                                             int32_t* __restrict__ cand, double* __restrict__ refl) {
   const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
   const uint32_t C = W * Pc;
   if (i >= (size_t)n_subframes * C) return;
@@ -94,6 +99,40 @@ __global__ void __launch_bounds__(64) order_levinson_kernel(const double* __rest
   pr[33] = shift;
   pr[34] = status;
   pr[35] = 0;
+  if (REFL) {
+    double k = 0.0;
+#pragma unroll
+    for (int t = 0; t < MAXP; ++t) k = (t == o - 1) ? coef[t] : k;
+    refl[i] = k;
+  }
+}
+
+struct DevLog2f {
+  __device__ float operator()(float x) const { return dev_log2f(x); }
+};
+
+// The order guess, one lane per (subframe, window): the error chain over the window's P candidates, the K guesses
+// (order_guess_core.h), and kNotCandidate into the status word of every candidate that is neither a guess nor (0, P) --
+// order_search_kernel skips a record whose status is not 0, and order_pick_kernel runs the chosen (j, o) again.
+__global__ void __launch_bounds__(64) order_guess_kernel(const double* __restrict__ racc, const double* __restrict__ refl,
+                                                          int32_t* __restrict__ cand, uint32_t n_subframes, uint32_t W,
+                                                          uint32_t P, uint32_t precision, uint32_t block_size,
+                                                          const uint8_t* __restrict__ bps, uint32_t bps_uniform,
+                                                          uint32_t stereo, uint32_t K) {
+  const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
+  if (i >= (size_t)n_subframes * W) return;
+  const size_t sf = i / W;
+  const uint32_t j = (uint32_t)(i % W);
+  const uint32_t w = bps ? (uint32_t)bps[sf] : bps_uniform + ((stereo && (sf & 3u) == 3u) ? 1u : 0u);
+  const size_t c0 = i * P;  // candidate (j, 1) of the subframe: sf * W * P + j * P
+  int32_t* st = cand + c0 * kCandWords + 34;
+  order_guess::Guess g;
+  order_guess::guess_orders(racc[i * 33], refl + c0, 1u, st, (uint32_t)kCandWords, P, block_size, w, precision, K,
+                            DevLog2f(), &g);
+  for (uint32_t o = 1; o <= P; ++o) {
+    const bool keep = ((g.mask >> (o - 1)) & 1u) != 0u || (j == 0u && o == P);
+    if (!keep) st[(size_t)(o - 1) * kCandWords] = kNotCandidate;
+  }
 }
 
 // the chosen candidate's predictor record for the stage-3 kernels, its unquantised coefficients (zeros from o on) and
@@ -417,6 +456,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
 // autocorr already offset to the slice's first subframe.
 struct SliceArgs {
   const double* racc;
+  double* refl;  // the order guess: k_o of every candidate [n][C], else nullptr
   int32_t* cand;
   uint32_t* best;
   int32_t* pred;
@@ -430,8 +470,12 @@ template <int MAXP>
 hipError_t launch_levinson_and_pick(bool pick, const SliceArgs& s, hipStream_t stream) {
   if (!pick) {
     const size_t items = (size_t)s.n_subframes * s.W * s.Pc;
-    hipLaunchKernelGGL(order_levinson_kernel<MAXP>, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, s.racc,
-                       s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand);
+    if (s.refl)
+      hipLaunchKernelGGL((order_levinson_kernel<MAXP, true>), dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream,
+                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand, s.refl);
+    else
+      hipLaunchKernelGGL((order_levinson_kernel<MAXP, false>), dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream,
+                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand, s.refl);
   } else {
     hipLaunchKernelGGL(order_pick_kernel<MAXP>, dim3((s.n_subframes + 63) / 64), dim3(64), 0, stream, s.racc, s.n_subframes,
                        s.W, s.P, s.Pc, s.precision, s.best, s.pred, s.lpc_coefs, s.autocorr);
@@ -450,7 +494,7 @@ hipError_t levinson_bucket(bool pick, const SliceArgs& s, hipStream_t stream) {
 
 size_t bytes_per_subframe(uint32_t lpc_order, const SearchShape& shape) {
   const size_t W = shape.n_windows, C = W * (shape.search_orders ? lpc_order : 1u);
-  return W * 33 * sizeof(double) + C * kCandWords * 4 + 4;
+  return W * 33 * sizeof(double) + (shape.guess_orders ? C * sizeof(double) : 0) + C * kCandWords * 4 + 4;
 }
 
 // subframes per slice: as many as kSearchScratchCap holds, whole stereo frames (a multiple of 4), at least 4
@@ -470,7 +514,8 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
                                const SearchShape& shape, void* scratch, hipStream_t stream) {
   if (a.n_subframes == 0) return hipSuccess;
   if (a.split_scratch == nullptr || scratch == nullptr || a.lpc_order < 1 || a.lpc_order > 32 || a.block_size < 64 ||
-      a.block_size > 32767 || shape.n_windows < 1 || shape.n_windows > kMaxSearchWindows)
+      a.block_size > 32767 || shape.n_windows < 1 || shape.n_windows > kMaxSearchWindows || shape.guess_orders > 32 ||
+      (shape.guess_orders && !shape.search_orders))
     return hipErrorInvalidValue;
   const size_t n = a.n_subframes;
   const uint32_t W = shape.n_windows;
@@ -479,7 +524,8 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
   const size_t slice = slice_subframes(n, a.lpc_order, shape);
   int32_t* pred = reinterpret_cast<int32_t*>(reinterpret_cast<double*>(a.split_scratch) + n * 33);
   double* racc = static_cast<double*>(scratch);
-  int32_t* cand = reinterpret_cast<int32_t*>(racc + slice * W * 33);
+  double* refl = shape.guess_orders ? racc + slice * W * 33 : nullptr;
+  int32_t* cand = reinterpret_cast<int32_t*>(racc + slice * W * 33 + (refl ? slice * C : 0));
   uint32_t* best = reinterpret_cast<uint32_t*>(cand + slice * C * kCandWords);
 
   const bool lds_u = search_lds_bytes(a.block_size, true) <= 160 * 1024;
@@ -515,6 +561,7 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
     }
     SliceArgs sl{};
     sl.racc = racc;
+    sl.refl = refl;
     sl.cand = cand;
     sl.best = best;
     sl.pred = pred + sf0 * kCandWords;
@@ -527,6 +574,13 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
     sl.precision = a.precision;
     // 2. every candidate's predictor
     if ((err = levinson_bucket(false, sl, stream)) != hipSuccess) return err;
+    if (refl) {  // 2b. the order guess: all but (0, P) and every window's guesses struck from the search
+      const size_t items = (size_t)ns * W;
+      hipLaunchKernelGGL(order_guess_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, racc, refl, cand,
+                         ns, W, a.lpc_order, a.precision, a.block_size, a.bps ? a.bps + sf0 : nullptr, a.bps_uniform,
+                         a.stereo, shape.guess_orders);
+      if ((err = hipGetLastError()) != hipSuccess) return err;
+    }
     // 3. the search
     OrderSearchArgs s{};
     s.samples = samples;

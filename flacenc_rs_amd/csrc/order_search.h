@@ -23,18 +23,23 @@ struct SearchShape {
   const float* windows[kMaxSearchWindows];  // device weight tables (32 leading pad floats), nullptr = all ones
   uint32_t n_windows;                       // W, 1..8
   uint32_t search_orders;                   // 1: orders 1..P per window; 0: order P only
+  // FLACENC_HIP_FLAG_ORDER_GUESS: K in 1..32 -- of the orders 1..P (search_orders = 1) the search codes only (0, P) and
+  // every window's K guesses (order_guess_core.h); 0: every candidate
+  uint32_t guess_orders;
 };
 
 // Handle scratch of a flagged candidate batch of n subframes at lpc_order P: per subframe R[0..32] of every window
 // ([W][33] f64, 264 B each), the C = W x (P or 1) candidate predictor records ([C][36] int32: qc[32], order, shift,
-// status, 0; 144 B each) and the chosen candidate (uint32) -- for the largest slice the call runs, so never above
-// kSearchScratchCap.
+// status, 0; 144 B each) and the chosen candidate (uint32), with the order guess also every candidate's k_o ([C] f64) --
+// for the largest slice the call runs, so never above kSearchScratchCap.
 size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order, const SearchShape& shape);
 
 // The whole flagged pipeline of a candidate batch `a` (split scratch attached; autocorr / lpc_coefs as the caller asked),
 // steps 1..4 per slice of subframes:
 //   1. R[0..P] of every window in the stable build's order (nightly's with `nightly`);
 //   2. order_levinson_kernel: levinson_quantize at every candidate (j, o), one lane per (subframe, candidate);
+//      with the order guess then order_guess_kernel, one lane per (subframe, window): every candidate but (0, P) and the
+//      window's K guesses gets a status the search skips;
 //   3. order_search_kernel: one workgroup per subframe, every candidate's residual and exact Rice search -> the
 //      candidate whose Lpc::count_bits is smallest (ties: the lower window, then the lower order; no candidate with
 //      status 0: (0, P));

@@ -488,7 +488,8 @@ class HipContext {
   HipContext(const HipContext&) = delete;
   HipContext& operator=(const HipContext&) = delete;
   HipContext(HipContext&& o) noexcept  // std::vector<HipContext>: one per GPU
-      : h_(o.h_), sum_order_(o.sum_order_), order_search_(o.order_search_), window_search_(o.window_search_) {
+      : h_(o.h_), sum_order_(o.sum_order_), order_search_(o.order_search_), window_search_(o.window_search_),
+        order_guess_(o.order_guess_) {
     o.h_ = nullptr;
   }
   HipContext& operator=(HipContext&& o) noexcept {
@@ -498,6 +499,7 @@ class HipContext {
       sum_order_ = o.sum_order_;
       order_search_ = o.order_search_;
       window_search_ = o.window_search_;
+      order_guess_ = o.order_guess_;
       o.h_ = nullptr;
     }
     return *this;
@@ -532,8 +534,18 @@ class HipContext {
     if (flacenc_hip_set_lpc_windows(h_, types, alphas, starts, ends, n_extra) != FLACENC_HIP_OK)
       throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
   }
+  // FLACENC_HIP_FLAG_ORDER_GUESS: every LPC subframe's order guessed from the Levinson error and only (0, lpc_order) and
+  // the guesses coded (set_order_guesses: how many per window, 1 on a fresh handle); off by default, and not to be
+  // combined with set_order_search (the library answers FLACENC_HIP_ERR_BAD_CONFIG)
+  void set_order_guess(bool on) { order_guess_ = on; }
+  bool order_guess() const { return order_guess_; }
+  void set_order_guesses(uint32_t k) {
+    if (flacenc_hip_set_order_guesses(h_, k) != FLACENC_HIP_OK)
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+  }
   uint32_t sum_order_flags(size_t lpc_order) const {
-    const uint32_t os = (order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u) | (window_search_ ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u);
+    const uint32_t os = (order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u) | (window_search_ ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u) |
+                        (order_guess_ ? FLACENC_HIP_FLAG_ORDER_GUESS : 0u);
     // (the mirror consumes integers only: certified shapes keep their own order, INTEGER_PARITY_ONLY)
     if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY | os;
     if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER | os;
@@ -574,6 +586,7 @@ class HipContext {
   SumOrder sum_order_ = SumOrder::Canonical;
   bool order_search_ = false;
   bool window_search_ = false;
+  bool order_guess_ = false;
 };
 
 // Staging memory for the host-pointer entry points: page-locked (flacenc_hip_host_alloc), so that the

@@ -233,6 +233,40 @@ extern "C" {
  * the handle's window cache until flacenc_hip_destroy. */
 #define FLACENC_HIP_FLAG_WINDOW_SEARCH 2048u
 
+/* Guided LPC order search (libFLAC's default mode; only its -e codes every order as FLACENC_HIP_FLAG_ORDER_SEARCH does):
+ * the order of every LPC candidate subframe is guessed from the prediction error the Levinson recursion leaves at each
+ * order, and only the guesses are coded.  Inputs per subframe with lpc_order = P: n, the block size; w, the row's bits per
+ * sample as the key uses it (bits_per_sample + 1 for the side role, w - k for a shifted row under WASTED_BITS); q,
+ * quant_precision; K, the handle's guesses per window (flacenc_hip_set_order_guesses; a fresh handle holds 1).  For every
+ * window j, R = R_j[0..P] exactly as WINDOW_SEARCH defines it (without WINDOW_SEARCH j = 0 is the only window): the stable
+ * build's order, or nightly's under NIGHTLY_SUM_ORDER; CANONICAL_SUM_ORDER and INTEGER_PARITY_ONLY have no effect.
+ *   1. k_o, o = 1..P: unquantised coefficient number o - 1 of ORDER_SEARCH's candidate o on R[0..o] (all coefficients are
+ *      zero when R[0] = 0).
+ *   2. e_0 = R[0]; e_o = e_(o-1) * (1.0 - k_o * k_o) in binary64, the multiply, the subtraction and the multiply each
+ *      rounded on their own (no fma).
+ *   3. Order o is eligible iff for every i <= o candidate i has status 0 and e_i >= 0 (a NaN fails); the first failure
+ *      ends the chain.
+ *   4. x_o = (float)(e_o * (0.5 / (double)n)); b_o = 0.5f * log2f(x_o) if x_o > 0 and that value is > 0, else +0.0f
+ *      (libm's log2f).
+ *   5. cost_o = (double)b_o * (double)(n - o) + (double)(o * (q + w)), multiply and add each rounded on their own.
+ *   6. The guesses of window j are the K eligible orders with the smallest (cost_o, o); fewer when fewer are eligible.
+ *   7. The candidates are (0, P) and every guess (j, o), each built and keyed exactly as ORDER_SEARCH / WINDOW_SEARCH build
+ *      and key a candidate; the one with status 0 and the smallest exact Lpc::count_bits is coded, ties to the lower
+ *      window, then the lower order; with no such candidate (0, P), status included.
+ * The record and residual row are the winner's, `autocorr` its window's R[0..P], `lpc_coefs` its unquantised coefficients
+ * with zeros from o on.  The candidates are a subset of the exhaustive search's and contain the REFERENCE_SUM_ORDER
+ * record (NIGHTLY_SUM_ORDER's under that flag): no flagged record or frame is longer than that call's, none shorter than
+ * the same call with ORDER_SEARCH in this flag's place; when every order with status 0 is eligible and K covers them every
+ * output is that ORDER_SEARCH call's; at lpc_order 1 without extra windows no byte differs from the REFERENCE_SUM_ORDER
+ * call.  With ORDER_SEARCH the flag answers FLACENC_HIP_ERR_BAD_CONFIG, with use_direct_mse FLACENC_HIP_ERR_UNSUPPORTED
+ * (flacenc_hip_verify_config and every call).  WINDOW_SEARCH with an empty extra-window list plus this flag is this flag's
+ * call.  Honoured where ORDER_SEARCH is (candidate batches, every frame-level call; composes with WASTED_BITS; FUSED_PACK
+ * ignored; flacenc_hip_fixed_lpc_batch accepts and ignores it).  No host synchronisation: a flagged call is capturable
+ * wherever the ORDER_SEARCH call is.
+ * Scratch: ORDER_SEARCH's (264 B per (subframe, window), 144 B per (subframe, window, order)) and 8 B more per (subframe,
+ * window, order) for k_o, inside the same 768 MiB slice bound. */
+#define FLACENC_HIP_FLAG_ORDER_GUESS 4096u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1
@@ -313,6 +347,10 @@ int flacenc_hip_window_weights(const flacenc_hip_qlpc_config* cfg, uint32_t bloc
  * TUKEY.  Takes effect for the calls enqueued after it; the list travels with no call that lacks the flag. */
 int flacenc_hip_set_lpc_windows(flacenc_hip_handle* h, const uint32_t* types, const float* alphas,
                                 const uint32_t* starts, const uint32_t* ends, uint32_t n_extra);
+/* FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window, 1..=32 (else FLACENC_HIP_ERR_BAD_ARGUMENT, the value kept); a
+ * fresh handle holds 1.  Read when a call is enqueued: it applies to the calls made after it, and has no effect without
+ * the flag. */
+int flacenc_hip_set_order_guesses(flacenc_hip_handle* h, uint32_t k);
 /* The weights of one extra-window entry over a block of block_size (<= 32767) samples, on the host: no handle, no GPU.
  * The same validation as flacenc_hip_set_lpc_windows (FLACENC_HIP_ERR_BAD_CONFIG). */
 int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,

@@ -59,6 +59,10 @@ pub const FLAG_ORDER_SEARCH: u32 = 1024;
 /// `FLACENC_HIP_FLAG_WINDOW_SEARCH`: every LPC candidate is analysed under the config's window and the handle's extra
 /// windows (`flacenc_hip_set_lpc_windows`) and the shortest is coded.  The drop-in never sets it.
 pub const FLAG_WINDOW_SEARCH: u32 = 2048;
+/// `FLACENC_HIP_FLAG_ORDER_GUESS`: every LPC candidate's order is guessed from the Levinson error, and only
+/// `(0, lpc_order)` and the handle's K guesses per window (`flacenc_hip_set_order_guesses`) are coded.  Not with
+/// `FLAG_ORDER_SEARCH`.  The records stay ordinary `SubFrame::Lpc`.  The drop-in never sets it.
+pub const FLAG_ORDER_GUESS: u32 = 4096;
 /// Extra-window types of `FLAG_WINDOW_SEARCH` (the config's `window_type` keeps rejecting them), the most windows per
 /// subframe, and the unit of an extra window's `start` / `end`.
 pub const WINDOW_PARTIAL_TUKEY: u32 = 2;
@@ -282,6 +286,8 @@ extern "C" {
     pub fn flacenc_hip_set_lpc_windows(
         h: *mut Handle, types: *const u32, alphas: *const f32, starts: *const u32, ends: *const u32, n_extra: u32,
     ) -> c_int;
+    /// `FLAG_ORDER_GUESS`'s guesses per window of a handle, `1..=32` (a fresh handle holds 1).
+    pub fn flacenc_hip_set_order_guesses(h: *mut Handle, k: u32) -> c_int;
     /// One extra-window entry's weights over a block, on the host.
     pub fn flacenc_hip_lpc_window_weights(
         window_type: u32, alpha: f32, start: u32, end: u32, block_size: u32, out: *mut f32,

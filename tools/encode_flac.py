@@ -8,7 +8,7 @@ MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-f
 frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
-                                  [--window-search]
+                                  [--window-search] [--order-guess [K]]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -20,6 +20,9 @@ With --order-search (FLACENC_HIP_FLAG_ORDER_SEARCH) every LPC subframe's order i
 bit count is smallest; the histogram of the chosen orders is printed.
 With --window-search (FLACENC_HIP_FLAG_WINDOW_SEARCH) every LPC subframe is also analysed under the default extra windows
 (partial and punch-out Tukey windows, _capi.DEFAULT_LPC_WINDOWS) and the shortest result is coded.
+With --order-guess [K] (FLACENC_HIP_FLAG_ORDER_GUESS, libFLAC's default mode) the order of every LPC subframe is guessed
+from the Levinson prediction error: --lpc-order and the K guesses (default 1) per window are coded and the shortest kept;
+the histogram of the chosen orders is printed.  Not together with --order-search.
 """
 import argparse
 import hashlib
@@ -119,10 +122,22 @@ def main():
     ap.add_argument("--window-search", action="store_true",
                     help="analyse every LPC subframe under the config's window and the default extra windows, keep the "
                          "shortest (FLACENC_HIP_FLAG_WINDOW_SEARCH); composes with --order-search")
+    ap.add_argument("--order-guess", type=int, nargs="?", const=1, default=0, metavar="K",
+                    help="guess the LPC order of every subframe from the Levinson error and code --lpc-order and the K "
+                         "guesses per window, K in 1..32, default 1 (FLACENC_HIP_FLAG_ORDER_GUESS); composes with "
+                         "--window-search, not with --order-search")
     ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
+    if args.order_guess and args.order_search:
+        ap.error("--order-guess and --order-search exclude each other")
+    if args.order_guess < 0 or args.order_guess > 32:
+        ap.error("--order-guess K must be in 1..32")
     flags = (_capi.FLAG_WASTED_BITS if args.wasted_bits else 0) | (_capi.FLAG_ORDER_SEARCH if args.order_search else 0)
     flags |= _capi.FLAG_WINDOW_SEARCH if args.window_search else 0  # (a fresh handle holds DEFAULT_LPC_WINDOWS)
+    flags |= _capi.FLAG_ORDER_GUESS if args.order_guess else 0
+    handle = _capi.Handle(0)
+    if args.order_guess:
+        handle.set_order_guesses(args.order_guess)
     n = 4096
     if len(args.paths) == 2:
         with wave.open(args.paths[0], "rb") as w:
@@ -138,7 +153,7 @@ def main():
         pcm = np.ascontiguousarray(_capi.sigen_frames(nf, 2, n, bps, rate / 440.0, 0.8, 0.2, seed=1)
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
     if args.levels:
-        data, v = encode_pcm_variable(pcm, bps, rate, _capi.Handle(0), block_size=n, levels=args.levels,
+        data, v = encode_pcm_variable(pcm, bps, rate, handle, block_size=n, levels=args.levels,
                                       lpc_order=args.lpc_order, flags=flags)
         with open(args.paths[-1], "wb") as f:
             f.write(data)
@@ -146,7 +161,7 @@ def main():
         print(f"{v['frames']} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM "
               f"size; block sizes {dict((int(b), int((v['block_sizes'] == b).sum())) for b in sizes)}")
         return
-    data, res = encode_pcm(pcm, bps, rate, _capi.Handle(0), block_size=n, lpc_order=args.lpc_order, flags=flags)
+    data, res = encode_pcm(pcm, bps, rate, handle, block_size=n, lpc_order=args.lpc_order, flags=flags)
     nf = len(res)
     with open(args.paths[-1], "wb") as f:
         f.write(data)
@@ -154,7 +169,7 @@ def main():
     wasted = int((res["pad"] != 0).sum())
     print(f"{nf} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM size; "
           f"subframes constant/verbatim/fixed/lpc = {kinds.tolist()}, with wasted bits {wasted}")
-    if args.order_search:
+    if args.order_search or args.order_guess:
         orders = res["lpc"]["order"][res["kind"] == 3]
         hist = np.bincount(orders, minlength=args.lpc_order + 1)
         print("chosen LPC orders: " + ", ".join(f"{o}: {int(c)}" for o, c in enumerate(hist) if c))
