@@ -62,7 +62,8 @@ VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flace
 # every symbol include/flacenc_hip.h declares
 ABI_VERSION = 6  # FLACENC_HIP_ABI_VERSION of include/flacenc_hip.h
 DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_keys", "flacenc_hip_debug_set_cert_stats",
-                 "flacenc_hip_debug_set_adaptive_order", "flacenc_hip_debug_adaptive_state")
+                 "flacenc_hip_debug_set_adaptive_order", "flacenc_hip_debug_adaptive_state",
+                 "flacenc_hip_debug_set_order_guess_trace")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -195,6 +196,11 @@ def make_frame_config(qlpc: QlpcConfig | None = None, use_constant=True, use_fix
 
 
 # flacenc_hip_channel_result (368 bytes): one channel of an Independent(n) frame
+# the record of flacenc_hip_debug_set_order_guess_trace (csrc/flacenc_hip_debug.h), 264 bytes: orders 1..eligible are
+# eligible, bit o - 1 of mask says order o is a guess, cost[o - 1] for o <= eligible and +0.0 above
+ORDER_GUESS_TRACE_DTYPE = np.dtype([("eligible", "<u4"), ("mask", "<u4"), ("cost", "<f8", 32)])
+assert ORDER_GUESS_TRACE_DTYPE.itemsize == 264
+
 CHANNEL_RESULT_DTYPE = np.dtype(
     [("kind", np.uint8), ("analysis_status", np.uint8), ("pad", np.uint8, (2,)), ("dc_offset", np.int32), ("bits", np.uint64),
      ("params", PARAMS_DTYPE)], align=False)
@@ -576,6 +582,12 @@ class Handle:
 
     def debug_set_fixed_keys(self, device_ptr: int):
         self._check(self._hook("flacenc_hip_debug_set_fixed_keys")(self._h, device_ptr or None))
+
+    def debug_set_order_guess_trace(self, device_ptr: int):
+        """Calls under FLAG_ORDER_GUESS store every (subframe, window)'s guess as one ORDER_GUESS_TRACE_DTYPE record at
+        [subframe of the call * W + window] of this device buffer, which the caller sizes (flacenc_hip_debug.h); 0
+        switches it off."""
+        self._check(self._hook("flacenc_hip_debug_set_order_guess_trace")(self._h, device_ptr or None))
 
     def debug_set_stamps(self, device_ptr: int):
         self._check(self._hook("flacenc_hip_debug_set_stamps")(self._h, device_ptr or None))

@@ -377,6 +377,7 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
     shape.n_windows = 1;
     shape.guess_orders = (cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) ? h->order_guesses : 0u;
     shape.search_orders = ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) || shape.guess_orders) ? 1u : 0u;
+    shape.guess_trace = shape.guess_orders ? h->order_guess_trace : nullptr;
     if (cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) {
       for (const LpcWindow& w : h->lpc_windows) {
         const WindowEntry* e = nullptr;

@@ -32,6 +32,12 @@ int flacenc_hip_debug_adaptive_state(flacenc_hip_handle* h, int* span, int* left
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_set_order_guess_trace(flacenc_hip_handle* h, void* device_trace) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->order_guess_trace = device_trace;
+  return FLACENC_HIP_OK;
+}
+
 int flacenc_hip_debug_set_cert_stats(flacenc_hip_handle* h, uint32_t* device_counters) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   h->cert_stats = device_counters;

@@ -186,6 +186,7 @@ struct flacenc_hip_handle {
   unsigned long long* stamps = nullptr;  // profiling hook, see flacenc_hip_debug_set_stamps
   unsigned long long* fixed_keys = nullptr;  // test hook, see flacenc_hip_debug_set_fixed_keys
   uint32_t* cert_stats = nullptr;  // statistics hook, see flacenc_hip_debug_set_cert_stats
+  void* order_guess_trace = nullptr;  // test hook, see flacenc_hip_debug_set_order_guess_trace
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch

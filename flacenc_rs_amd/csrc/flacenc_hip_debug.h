@@ -16,6 +16,20 @@ extern "C" {
  * the BitCount bits; src/coding.rs:249, :271) at device_keys[subframe*8 + order]. */
 int flacenc_hip_debug_set_fixed_keys(flacenc_hip_handle* h, unsigned long long* device_keys);
 
+/* Test hook (no reference counterpart): when `device_trace` is non-NULL, every launch of the search under
+ * FLACENC_HIP_FLAG_ORDER_GUESS stores what order_guess_kernel computed for each (subframe, window) -- the guess itself,
+ * which otherwise never leaves the handle's scratch -- as one record of 264 bytes,
+ *   uint32 eligible;   orders 1..eligible are eligible
+ *   uint32 mask;       bit o - 1: order o is one of the window's guesses
+ *   double cost[32];   cost[o - 1] of order o <= eligible, +0.0 in every entry above
+ * at record index sf * W + j: sf the subframe of the call (not of a slice of it; stereo calls: 4 * frame + role), j the
+ * window, W the number of windows the call searches (1 without FLACENC_HIP_FLAG_WINDOW_SEARCH or with an empty
+ * extra-window list, else 1 + the handle's extra windows).  The caller sizes the buffer: subframes * W records.  A call
+ * that launches the search more than once (flacenc_hip_encode_variable; with FLACENC_HIP_FLAG_WASTED_BITS the pass
+ * over every frame, left out when every frame has wasted bits, and then the fix-up of the marked frames' shifted rows)
+ * overwrites the buffer: every launch counts its own subframes from 0.  Calls without the flag store nothing.  Pass NULL to switch it off again. */
+int flacenc_hip_debug_set_order_guess_trace(flacenc_hip_handle* h, void* device_trace);
+
 /* Profiling hook (no reference counterpart): when `device_stamps` is non-NULL every
  * following launch makes each workgroup leader store 8 shader-clock timestamps
  * (phase boundaries of the fused kernel) at device_stamps[subframe*8 + phase].

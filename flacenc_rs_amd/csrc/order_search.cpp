@@ -21,6 +21,7 @@ constexpr uint32_t kMaxBits = (1u << 27) - 1u;    // MAX_P_TO_BITS, rice.rs:51
 constexpr uint32_t kWideU = 1u << 27;             // zig-zag codes from here on can wrap a 16-sample chunk's u32 sum
 constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, 0 (levinson_batch_kernel's record)
 constexpr int32_t kNotCandidate = 0x40000000;     // order_guess_kernel's status word of a candidate the search skips
+static_assert(sizeof(order_guess::Guess) == 264, "the trace record of flacenc_hip_debug_set_order_guess_trace");
 constexpr size_t kSmallBytes = 1024 + 16 * 8 + 2 * 8 + 16 * 4 + 256 + 256;  // psum, level bits, sums, misc, two ps rows
 
 enum { kMaxAbs = 0, kUMax, kSat, kLo, kHi, kRice2, kClamp };
@@ -118,7 +119,8 @@ __global__ void __launch_bounds__(64) order_guess_kernel(const double* __restric
                                                           int32_t* __restrict__ cand, uint32_t n_subframes, uint32_t W,
                                                           uint32_t P, uint32_t precision, uint32_t block_size,
                                                           const uint8_t* __restrict__ bps, uint32_t bps_uniform,
-                                                          uint32_t stereo, uint32_t K) {
+                                                          uint32_t stereo, uint32_t K,
+                                                          order_guess::Guess* __restrict__ trace) {
   const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
   if (i >= (size_t)n_subframes * W) return;
   const size_t sf = i / W;
@@ -132,6 +134,12 @@ __global__ void __launch_bounds__(64) order_guess_kernel(const double* __restric
   for (uint32_t o = 1; o <= P; ++o) {
     const bool keep = ((g.mask >> (o - 1)) & 1u) != 0u || (j == 0u && o == P);
     if (!keep) st[(size_t)(o - 1) * kCandWords] = kNotCandidate;
+  }
+  if (trace) {  // test hook (flacenc_hip_debug.h): the lane's record, +0.0 above `eligible`; `trace` is lane 0's
+    order_guess::Guess* t = trace + i;
+    t->eligible = g.eligible;
+    t->mask = g.mask;
+    for (uint32_t o = 0; o < order_guess::kMaxOrder; ++o) t->cost[o] = o < g.eligible ? g.cost[o] : 0.0;
   }
 }
 
@@ -578,7 +586,8 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
       const size_t items = (size_t)ns * W;
       hipLaunchKernelGGL(order_guess_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, racc, refl, cand,
                          ns, W, a.lpc_order, a.precision, a.block_size, a.bps ? a.bps + sf0 : nullptr, a.bps_uniform,
-                         a.stereo, shape.guess_orders);
+                         a.stereo, shape.guess_orders,
+                         shape.guess_trace ? static_cast<order_guess::Guess*>(shape.guess_trace) + sf0 * W : nullptr);
       if ((err = hipGetLastError()) != hipSuccess) return err;
     }
     // 3. the search

@@ -26,6 +26,9 @@ struct SearchShape {
   // FLACENC_HIP_FLAG_ORDER_GUESS: K in 1..32 -- of the orders 1..P (search_orders = 1) the search codes only (0, P) and
   // every window's K guesses (order_guess_core.h); 0: every candidate
   uint32_t guess_orders;
+  // flacenc_hip_debug_set_order_guess_trace (tests): device, nullable -- every order_guess_kernel lane's record, 264
+  // bytes each, at [(subframe of the call) * W + window]
+  void* guess_trace;
 };
 
 // Handle scratch of a flagged candidate batch of n subframes at lpc_order P: per subframe R[0..32] of every window

@@ -1,7 +1,8 @@
 """FLACENC_HIP_FLAG_ORDER_GUESS without a GPU: the corpus reaches every regime of the rule (tests/guess_cases.py), the
 rule's consequences hold in the model (tests/guess_model.py) on the corpus and the golden fixtures, the host build of
 flacenc_rs_amd/csrc/order_guess_core.h (g++, plain and under ASan + UBSan) gives the model's eligibility, costs and
-guesses bit for bit, and the C ABI's config rules and constants are the header's."""
+guesses bit for bit, the calls of the trace suite (tests/guess_trace_cases.py, run on the GPU by
+tests/test_gpu_order_guess_trace.py) reach what they name, and the C ABI's config rules and constants are the header's."""
 import os
 import re
 import shutil
@@ -12,6 +13,7 @@ import pytest
 
 import guess_cases as gc
 import guess_model as gm
+import guess_trace_cases as tc
 import order_model as om
 import util
 import window_model as wm
@@ -119,6 +121,56 @@ def test_golden_fixtures_at_order_32_are_strictly_shorter():
                 ref += r["subframe_bits"]
     print("order 32, K = 1: %d against %d bits (%+.3f %%)" % (guess, ref, 100.0 * (guess - ref) / ref))
     assert guess < ref
+
+
+# ---- 2b. the trace suite's calls reach what they name ----
+TRACE_CALLS = tc.all_calls()
+ALL_REACHED = {"full", "early", "none", "width", "clip_low", "clip_one", "clip_high", "large", "dead", "k_at", "k_below",
+               "k_above", "all32", "windows"}
+
+
+@pytest.mark.parametrize("c", TRACE_CALLS, ids=tc.ids(TRACE_CALLS))
+def test_trace_calls_reach_what_they_name(c):
+    tc.claims(c)
+
+
+def test_trace_calls_cover_every_property_entry_and_log2f_table_index():
+    assert set().union(*(c.reach for c in TRACE_CALLS)) == ALL_REACHED
+    assert {c.entry for c in TRACE_CALLS} == set(tc.ENTRIES)
+    assert tc.log2f_indices(TRACE_CALLS) == set(range(16))
+    # K = 1 and K = P at every edge of an order bucket, and the ends of the block-size range
+    names = {c.name for c in TRACE_CALLS}
+    assert all({"bucket_%d_K1" % o, "bucket_%d_K%d" % (o, o)} <= names for o in (1, 2, 8, 9, 12, 13, 16, 17, 24, 25, 32))
+    assert {"size_64", "size_65", "size_4096", "size_32767"} <= names
+
+
+def test_the_side_role_and_the_shifted_rows_cost_what_their_own_width_costs():
+    # role 3 of a stereo frame is searched at bits + 1 and a row with k wasted bits at w - k: the model's costs at the
+    # frame's own width differ from them in every eligible entry, so a kernel that takes that width shows in the trace
+    for c in TRACE_CALLS:
+        if c.entry == "batch":
+            continue
+        cfg = tc.config(c)
+        for (x, w), per_window in zip(tc.subframes(c), tc.model(c)):
+            if w == c.bps:
+                continue
+            at_frame_width = gm.search(x, c.bps, cfg, c.K, c.extras)[2]
+            for g, f in zip(per_window, at_frame_width):
+                assert g["eligible"] == f["eligible"], c.name
+                assert all(a != b for a, b in zip(g["cost"], f["cost"])), c.name
+
+
+def test_the_clip_search_is_reproducible_on_its_first_trials():
+    # the two seeds the corpus keeps are trials of clip_noise; a window of the search around them finds them again
+    one, eps = np.float32(1.0), np.float32(2.0 ** -10)
+    hits = {}
+    for seed in (tc.CLIP_BOTH, tc.CLIP_ONE):
+        x = tc.clip_noise(seed)
+        c = tc.call("trial", "batch", [x], 16, 8)
+        xs = tc.xs_of(tc.model(c)[0][0], len(x))
+        hits[seed] = [("low" if one - eps < v < one else "one" if v == one else "high" if one < v < one + eps else "")
+                      for v in xs]
+    assert {"low", "high"} <= set(hits[tc.CLIP_BOTH]) and "one" in hits[tc.CLIP_ONE], hits
 
 
 # ---- 3. the core header against the model ----
