@@ -30,6 +30,7 @@
 
 #include "frame_bits.h"
 #include "qlpc_kernel_impl.h"
+#include "solver_lanes_core.h"
 #include "sumabs_chain.h"
 
 namespace flacenc_hip {
@@ -1003,6 +1004,135 @@ __device__ __forceinline__ int levinson_phase_full(const double* rsrc, int preci
   return (certified ? 1 : 0) | (tier2 ? 2 : 0) | (redo ? 4 : 0);
 }
 
+// ---- levinson_phase_full with the per-coefficient work issued once: one lane per coefficient --------------------------
+// Behind the recursion, levinson_quantize_full walks each system's MAXP coefficients one after the other on the lane that
+// solved it: the class tests, the maximum, the quantiser and the certificate's boundary test are each issued MAXP times
+// for four active lanes.  Here lanes 0..3 run the recursion (levinson_core_full, untouched) and the two sequential sums
+// the certificate's bound is made of (lanes_cert_bound), hand a[] to lanes G s + i through LDS -- G = 8 lanes per system
+// at MAXP 8, a DPP row of 16 above -- and every lane does its one coefficient with the operations of
+// solver_lanes_core.h: the very operations of levinson_quantize_full / quant_certified on the very operands.  Per system:
+// max |a| by an exact butterfly maximum inside the group (every lane of the group then derives shift, scale factor and
+// the find_shift gaps for itself: the same instructions the leader would issue), `order` from a ballot of q != 0, the
+// certificate's verdict from a ballot of the lanes that failed.  The whole wave calls this (exec full); the return
+// value is levinson_phase_full's and means something on lanes 0..3 only; `redo` is wave-uniform (any system left the
+// straight line: the caller solves all four again through the generic code, as before).
+// `tr`: 16-byte aligned LDS scratch of this wave's alone, 4 (G + 2) doubles -- the head of the certificate's fallback
+// area, which nothing uses before the fallback itself.  Writes and reads of it are one wave's: no workgroup barrier.
+#ifndef FLACENC_SOLVER_LANES
+#define FLACENC_SOLVER_LANES 1  // 0: levinson_phase_full everywhere (diagnostic build, and the A/B's other side)
+#endif
+// which instances take it: the order-8 bucket of the 4096-sample kernel -- the ones whose own A/B has been run
+constexpr bool solver_lanes_instance(int maxp, int spl) { return FLACENC_SOLVER_LANES != 0 && maxp == 8 && spl == 64; }
+constexpr int solver_lanes_group(int maxp) { return maxp <= 8 ? 8 : 16; }
+
+// exact maximum over the G-lane group of the lane, in every lane of it: xor 1, xor 2 (quad_perm), then row_half_mirror
+// (the quads are uniform by then: lane j and lane 7 - j hold the two quads' maxima) and row_mirror for 16.
+// (The instruction itself: behind fmax() the compiler first canonicalises either operand with a v_max_f64 of its own --
+// three a step.  The maximum of two numbers is exact either way, and next to a NaN the instruction returns the number,
+// as fmax does; a group that holds a NaN is solved again anyway.  The s_nop belongs to it: a DPP instruction may read a
+// VGPR two wait states after a VALU instruction wrote it, and the compiler does not look into inline assembly for the
+// writer when it places its own.)
+template <int G>
+__device__ __forceinline__ double group_max_dpp(double v) {
+#define FLACENC_F64_MAX_STEP(CTRL)                                                                        \
+  {                                                                                                       \
+    const unsigned long long b_ = (unsigned long long)__double_as_longlong(v);                           \
+    const uint32_t lo_ = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)b_, CTRL, 0xF, 0xF, true);    \
+    const uint32_t hi_ = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(b_ >> 32), CTRL, 0xF, 0xF, true); \
+    const double o_ = __longlong_as_double((long long)(((unsigned long long)hi_ << 32) | lo_));          \
+    asm("v_max_f64 %0, %1, %2\n\ts_nop 1" : "=v"(v) : "v"(v), "v"(o_));                                   \
+  }
+  FLACENC_F64_MAX_STEP(0xB1)   // quad_perm:[1,0,3,2]
+  FLACENC_F64_MAX_STEP(0x4E)   // quad_perm:[2,3,0,1]
+  FLACENC_F64_MAX_STEP(0x141)  // row_half_mirror
+  if (G == 16) FLACENC_F64_MAX_STEP(0x140)  // row_mirror
+#undef FLACENC_F64_MAX_STEP
+  return v;
+}
+
+template <int MAXP, bool CERT>
+__device__ __forceinline__ int levinson_phase_lanes(const double* xr, int precision, int32_t* xq, double* lpc_coefs,
+                                                    uint32_t sf_first, uint32_t n_subframes, const uint32_t* xm, int n_sum,
+                                                    bool do_cert, double* tr, int lane) {
+  constexpr int G = solver_lanes_group(MAXP);
+  static_assert(MAXP % 2 == 0 && MAXP <= G && 4 * G <= 64, "a[] travels in pairs; a system's coefficients fit its group");
+  double* const ta = tr;          // [4][G]: a[] of system s at ta[G s ..]
+  double* const ts = tr + 4 * G;  // [4][2]: {num, f0} of system s
+#ifdef FLACENC_CERT_NOBLOCK
+  do_cert = false;
+#endif
+  bool lead_redo = false, nonpd = false;
+  if (lane < 4) {
+    double R[MAXP + 1], a[MAXP], fwd[MAXP];
+#pragma unroll
+    for (int i = 0; i <= MAXP; ++i) R[i] = xr[lane * (MAXP + 1) + i];
+    bool skipped = false;
+    levinson_core_full<MAXP>(R, a, fwd, &skipped, &nonpd);
+    lead_redo = skipped || !__builtin_amdgcn_class(R[0], 0x180);  // as levinson_quantize_full
+#pragma unroll
+    for (int i = 0; i < MAXP; i += 2) *reinterpret_cast<double2*>(&ta[lane * G + i]) = make_double2(a[i], a[i + 1]);
+    if (CERT && do_cert) {  // (uniform over the launch)
+      const double num = lanes_cert_bound<MAXP>(a, fwd, R[0], xm[lane], n_sum);
+      *reinterpret_cast<double2*>(&ts[2 * lane]) = make_double2(num, fabs(fwd[0]));
+    }
+  }
+  // (one wave's LDS operations execute in order; the fence keeps the compiler from moving the reads above the writes)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+  const int s = lane / G, i = lane & (G - 1);  // (s >= 4 on the upper lanes of G = 8: they read scratch nobody wrote,
+  const bool valid = lane < 4 * G && i < MAXP;  // compute on it and are left out of every ballot and every store)
+  double av = ta[lane];
+  av = valid ? av : 0.0;
+  const bool redo_lane = lead_redo || __builtin_amdgcn_class(av, 0x207);  // NaN or +-inf (lpc.rs:797-799)
+  bool redo = __builtin_amdgcn_ballot_w64(redo_lane) != 0ull;
+#ifdef FLACENC_SOLVER_FORCE_REDO
+  redo = true;
+#endif
+  // quantize_parameters, as in levinson_quantize_full
+  const double amax = group_max_dpp<G>(fabs(av));
+  int e;
+  const int shift = lanes_find_shift(amax, precision, &e);
+  const double scalefac = (double)(1 << shift);
+  const int lo = -(1 << (precision - 1)), hi = (1 << (precision - 1)) - 1;
+  const int q = lanes_quantize_one(av, scalefac, lo, hi);
+  const unsigned long long nz = __builtin_amdgcn_ballot_w64(valid && q != 0);
+  const uint32_t nz_mine = (uint32_t)(nz >> (G * (s & 3))) & ((1u << G) - 1u);
+  const int order = nz_mine != 0u ? 32 - __builtin_clz(nz_mine) : 1;  // the last non-zero coefficient, at least 1
+  if (valid) xq[s * 16 + i] = q;
+  if (lane < 4 * G && i == 0) {
+    xq[s * 16 + 12] = order;
+    xq[s * 16 + 13] = shift;
+    xq[s * 16 + 14] = FLACENC_HIP_SUBFRAME_OK;
+  }
+  if (lpc_coefs) {
+    // the four rows of 32: entry f of the 128 by lanes f and f - 64
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int f = lane + 64 * h, s2 = f >> 5, i2 = f & 31;
+      uint32_t sfl = sf_first + (uint32_t)s2;
+      if (sfl >= n_subframes) sfl = n_subframes - 1u;
+      double v = 0.0;
+      if (i2 < MAXP) v = ta[s2 * G + i2];
+      lpc_coefs[(size_t)sfl * 32 + i2] = v;
+    }
+  }
+  bool certified = true, tier2 = false;
+  if (CERT && do_cert) {
+    const double2 nf = *reinterpret_cast<const double2*>(&ts[2 * (s & 3)]);
+    const double num = nf.x, f0 = nf.y;
+    bool ok = lanes_certify_system(amax, e, num, f0);
+    ok = lanes_certify_one(av, scalefac, f0, num * scalefac) && ok;
+    const unsigned long long bad = __builtin_amdgcn_ballot_w64(valid && !ok);
+    // lane l < 4 reads the verdict of system l (a denominator that was not positive: no certificate, no second tier)
+    const bool sys_ok = ((uint32_t)(bad >> (G * (lane & 3))) & ((1u << G) - 1u)) == 0u;
+    certified = !nonpd && sys_ok;
+    tier2 = !nonpd && !sys_ok;
+  }
+  return (certified ? 1 : 0) | (tier2 ? 2 : 0) | (redo ? 4 : 0);
+}
+
 // DECIDE (stereo only): run encode_subframe's candidate choice and try_stereo_coding's channel
 // assignment (coding.rs:384-418 without the fixed-LPC candidate, :493-522) on the device and
 // write one flacenc_hip_stereo_frame_result + the TWO chosen residual rows per frame.
@@ -1035,6 +1165,12 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
   // workgroups resident on a CU on one SIMD in 7 % of the pairs; rotating the roles by the workgroup index changes nothing.)
   const int wave = uni(tid >> 6);  // wave-uniform by construction; tell the compiler
   const int P = (int)a.lpc_order;
+#ifndef FLACENC_NO_ORDER_FACT
+  // launch_qlpc (qlpc_dispatch.cpp) picks the instance as the smallest bucket that holds lpc_order, and
+  // wave_kernel_eligible admits orders 1 .. 12 only: with it, the t >= P mask of the block's first chunk folds away from
+  // the second 8-sample step on (t >= 8 >= P at MAXP 8)
+  __builtin_assume(P >= 1 && P <= MAXP);
+#endif
   const int n = kWaveN;
 
   // ---- which subframe does this wave own ----
@@ -1454,8 +1590,19 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
       bool certified = true, need_rows = false;
       uint32_t sfl = blk * 4u + (uint32_t)(lane & 3);
       if (sfl >= a.n_subframes) sfl = a.n_subframes - 1u;
+      // The instances of solver_lanes_instance at their own MAXP: the recursion on lanes 0..3, quantiser and certificate
+      // one coefficient per lane (levinson_phase_lanes) -- the whole wave goes in, lanes 0..3 come back with the flags.
+      constexpr bool kLanes = FLACENC_SOLVER_FULL_ORDER != 0 && kCertSupported && solver_lanes_instance(MAXP, SPL);
+      int fl_lanes = 4;
+      const bool by_lanes = kLanes && P == MAXP && !from_in;
+      if (kLanes) {
+        __builtin_amdgcn_s_setprio(3);
+        if (by_lanes)
+          fl_lanes = levinson_phase_lanes<MAXP, kCertSupported>(xr, (int)a.precision, xq, a.lpc_coefs, blk * 4u, a.n_subframes, xm,
+                                                                kWaveN, certify, reinterpret_cast<double*>(cert_rows), lane);
+      }
       if (lane < 4) {
-        __builtin_amdgcn_s_setprio(3);  // the other three waves of the workgroup wait for this one
+        if (!kLanes) __builtin_amdgcn_s_setprio(3);  // the other three waves of the workgroup wait for this one
         // lpc_order is uniform over the launch: at the instance's own MAXP the straight-line form of the solver
         // (levinson_phase_full); at every other order, and on R[] that was handed in (which keeps the generic code's
         // tests), today's generic one.  A workgroup in which a lane's system left the straight line -- a zero denominator,
@@ -1466,7 +1613,9 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
         double* const coefs_dst = a.lpc_coefs ? a.lpc_coefs + (size_t)sfl * 32 : nullptr;
         const uint32_t mabs = kCertSupported ? xm[lane] : 0u;
         int fl = 4;
-        if (FLACENC_SOLVER_FULL_ORDER != 0 && P == MAXP && !from_in)
+        if (kLanes && by_lanes)
+          fl = fl_lanes;
+        else if (FLACENC_SOLVER_FULL_ORDER != 0 && P == MAXP && !from_in)
           fl = levinson_phase_full<MAXP, kCertSupported>(xr + lane * XR, (int)a.precision, xq + lane * 16, coefs_dst, mabs,
                                                          kWaveN, certify);
         if (__builtin_amdgcn_ballot_w64((fl & 4) != 0) != 0ull)
