@@ -63,7 +63,8 @@ VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flace
 ABI_VERSION = 6  # FLACENC_HIP_ABI_VERSION of include/flacenc_hip.h
 DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_keys", "flacenc_hip_debug_set_cert_stats",
                  "flacenc_hip_debug_set_adaptive_order", "flacenc_hip_debug_adaptive_state",
-                 "flacenc_hip_debug_set_order_guess_trace")
+                 "flacenc_hip_debug_set_order_guess_trace", "flacenc_hip_debug_set_stream_chunk",
+                 "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -291,6 +292,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     if hasattr(L, "flacenc_hip_debug_set_adaptive_order"):
         L.flacenc_hip_debug_set_adaptive_order.argtypes = [vp, C.c_int]
         L.flacenc_hip_debug_adaptive_state.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "flacenc_hip_debug_set_stream_chunk"):
+        L.flacenc_hip_debug_set_stream_chunk.argtypes = [vp, C.c_size_t]
+        L.flacenc_hip_debug_last_stream_plan.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.flacenc_hip_debug_last_stream_buffers.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     batch_args = [vp, C.POINTER(QlpcConfig), i32p, C.c_size_t, C.c_uint32, C.c_size_t, u8p, vp, i32p,
                   C.c_size_t, f64p, f64p]
     L.flacenc_hip_qlpc_batch.argtypes = batch_args + [C.c_int]
@@ -608,6 +613,25 @@ class Handle:
         self._check(self._hook("flacenc_hip_debug_adaptive_state")(self._h, C.byref(span), C.byref(left)))
         return span.value, left.value
 
+    def debug_set_stream_chunk(self, frames: int):
+        """encode_pcm* cuts its full blocks into chunks of `frames` frames in place of its rule (flacenc_hip_debug.h);
+        0: the rule again.  More than 8192 is refused."""
+        self._check(self._hook("flacenc_hip_debug_set_stream_chunk")(self._h, int(frames)))
+
+    def debug_last_stream_plan(self):
+        """(frames per chunk, chunks -- the short last block's included) of the last encode_pcm* call on this handle;
+        (0, 0) when it ran none."""
+        chunk, n = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._hook("flacenc_hip_debug_last_stream_plan")(self._h, C.byref(chunk), C.byref(n)))
+        return chunk.value, n.value
+
+    def debug_last_stream_buffers(self):
+        """(pcm, out) of the last encode_pcm* call that reached its plan: True where the call found the buffer page-locked
+        and transferred it directly, False where it staged it through the handle's pinned slots."""
+        a, b = C.c_int(0), C.c_int(0)
+        self._check(self._hook("flacenc_hip_debug_last_stream_buffers")(self._h, C.byref(a), C.byref(b)))
+        return bool(a.value), bool(b.value)
+
     def synchronize(self):
         self._check(self._lib.flacenc_hip_synchronize(self._h))
 
@@ -766,40 +790,54 @@ class Handle:
         self._check(rc)
 
     def encode_pcm(self, pcm: np.ndarray, channels: int, cfg: FrameConfig, bytes_per_sample: int, bits_per_sample: int,
-                   block_size: int, sample_rate: int, first_frame_number: int = 0, frame_number_step: int = 1):
-        """flacenc_hip_encode_pcm: interleaved LE PCM of 1..8 channels -> (frame bytes, lengths)."""
+                   block_size: int, sample_rate: int, first_frame_number: int = 0, frame_number_step: int = 1,
+                   out: np.ndarray | None = None, out_len: np.ndarray | None = None):
+        """flacenc_hip_encode_pcm: interleaved LE PCM of 1..8 channels -> (frame bytes, lengths).  `pcm` / `out` may be
+        pinned_array()s or views into one; `out` (uint8, its size is the capacity the call is told) and `out_len`
+        (uint32, one entry per frame or more) are the caller's own buffers, and what comes back are views of them."""
         assert pcm.dtype == np.uint8 and pcm.flags["C_CONTIGUOUS"]
         total = pcm.size // (channels * bytes_per_sample)
         n_frames = (total + block_size - 1) // block_size
-        bound = int(self._lib.flacenc_hip_frame_bytes_bound(channels, block_size, bits_per_sample))
-        out = np.empty(n_frames * (bound + 16), np.uint8)
-        lens = np.zeros(n_frames, np.uint32)
+        if out is None:
+            bound = int(self._lib.flacenc_hip_frame_bytes_bound(channels, block_size, bits_per_sample))
+            out = np.empty(n_frames * (bound + 16), np.uint8)
+        lens = self._own_lengths(out_len, n_frames)
         written = C.c_uint64(0)
         rc = self._lib.flacenc_hip_encode_pcm(self._h, C.byref(cfg), pcm.ctypes.data, total, channels, bytes_per_sample,
                                               bits_per_sample, block_size, sample_rate, first_frame_number,
                                               frame_number_step, out.ctypes.data, out.size, lens.ctypes.data,
                                               C.byref(written))
         self._check(rc)
-        return out[: written.value], lens
+        return out[: written.value], lens[:n_frames]
+
+    @staticmethod
+    def _own_lengths(out_len, n_frames):
+        """The lengths' buffer of encode_pcm*: the caller's, checked, or a fresh one."""
+        if out_len is None:
+            return np.zeros(n_frames, np.uint32)
+        assert out_len.dtype == np.uint32 and out_len.ndim == 1 and out_len.flags["C_CONTIGUOUS"]
+        assert out_len.flags["WRITEABLE"] and out_len.size >= n_frames
+        return out_len
 
     def encode_pcm_stereo(self, pcm: np.ndarray, cfg: FrameConfig, bytes_per_sample: int, bits_per_sample: int,
                           block_size: int, sample_rate: int, out: np.ndarray | None = None,
-                          first_frame_number: int = 0, frame_number_step: int = 1):
+                          first_frame_number: int = 0, frame_number_step: int = 1, out_len: np.ndarray | None = None):
         """Packed interleaved LE stereo PCM (uint8 array) -> (frame bytes uint8 [total], lengths uint32 [n_frames]),
-        the streaming host path (flacenc_hip_encode_pcm_stereo).  `pcm` / `out` may be pinned_array()s."""
+        the streaming host path (flacenc_hip_encode_pcm_stereo).  `pcm` / `out` may be pinned_array()s; `out_len` as
+        in encode_pcm."""
         assert pcm.dtype == np.uint8 and pcm.flags["C_CONTIGUOUS"]
         total = pcm.size // (2 * bytes_per_sample)
         n_frames = (total + block_size - 1) // block_size
         if out is None:
             out = np.empty(n_frames * (self.frame_bytes_bound(block_size, bits_per_sample) + 16), np.uint8)
-        lens = np.zeros(n_frames, np.uint32)
+        lens = self._own_lengths(out_len, n_frames)
         written = C.c_uint64(0)
         rc = self._lib.flacenc_hip_encode_pcm_stereo(self._h, C.byref(cfg), pcm.ctypes.data, total, bytes_per_sample,
                                                      bits_per_sample, block_size, sample_rate, first_frame_number,
                                                      frame_number_step, out.ctypes.data, out.size, lens.ctypes.data,
                                                      C.byref(written))
         self._check(rc)
-        return out[: written.value], lens
+        return out[: written.value], lens[:n_frames]
 
     def fill_le_bytes(self, data: bytes, channels: int, bytes_per_sample: int, block_size: int):
         """FrameBuf::fill_le_bytes for a whole stream: packed interleaved PCM -> int32 [n_frames, channels, n]."""

@@ -44,4 +44,28 @@ int flacenc_hip_debug_set_cert_stats(flacenc_hip_handle* h, uint32_t* device_cou
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_set_stream_chunk(flacenc_hip_handle* h, size_t frames) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (frames > 8192) {  // the rule's own upper end; flacenc_hip_fill_le_bytes_async takes at most 65535 frames
+    h->last_error = "debug_set_stream_chunk: more than 8192 frames per chunk";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->stream_chunk_override = frames;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_last_stream_plan(flacenc_hip_handle* h, size_t* chunk_frames, size_t* n_chunks) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (chunk_frames) *chunk_frames = h->last_stream_chunk;
+  if (n_chunks) *n_chunks = h->last_stream_chunks;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_last_stream_buffers(flacenc_hip_handle* h, int* in_pinned, int* out_pinned) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (in_pinned) *in_pinned = h->last_stream_in_pinned ? 1 : 0;
+  if (out_pinned) *out_pinned = h->last_stream_out_pinned ? 1 : 0;
+  return FLACENC_HIP_OK;
+}
+
 }  // extern "C"

@@ -187,6 +187,11 @@ struct flacenc_hip_handle {
   unsigned long long* fixed_keys = nullptr;  // test hook, see flacenc_hip_debug_set_fixed_keys
   uint32_t* cert_stats = nullptr;  // statistics hook, see flacenc_hip_debug_set_cert_stats
   void* order_guess_trace = nullptr;  // test hook, see flacenc_hip_debug_set_order_guess_trace
+  // test hook, see flacenc_hip_debug_set_stream_chunk: frames per chunk of the streaming path in place of its rule (0:
+  // the rule; nothing in the product library sets it), and the plan of the last flacenc_hip_encode_pcm* call
+  size_t stream_chunk_override = 0;
+  size_t last_stream_chunk = 0, last_stream_chunks = 0;
+  bool last_stream_in_pinned = false, last_stream_out_pinned = false;  // how that call took the caller's buffers
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch

@@ -94,6 +94,7 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
                            uint32_t* out_len, uint64_t* out_total) {
   if (!h || !cfg || !out_total) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   *out_total = 0;
+  h->last_stream_chunk = h->last_stream_chunks = 0;  // flacenc_hip_debug_last_stream_plan: no chunk has run yet
   if (total_samples == 0) return FLACENC_HIP_OK;
   if (!pcm || !out || !out_len || channels < 1 || channels > 8 || bytes_per_sample < 1 || bytes_per_sample > 4 ||
       block_size < FLACENC_HIP_MIN_BLOCK_SIZE || block_size > FLACENC_HIP_MAX_BLOCK_SIZE) {
@@ -122,6 +123,8 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   const size_t frame_in_bytes = static_cast<size_t>(block_size) * channels * bytes_per_sample;
   size_t chunk = (48u << 20) / frame_in_bytes;
   chunk = chunk < 768 ? 768 : (chunk > 8192 ? 8192 : chunk);
+  // (test hook flacenc_hip_debug_set_stream_chunk, hooks library only: seams after a handful of frames)
+  if (h->stream_chunk_override) chunk = h->stream_chunk_override;
   // never more than the call has: staging, device buffers and the candidates' scratch are all sized from it
   // (a one-frame call of 8 channels x 32767 samples would otherwise pin gigabytes)
   if (chunk > n_full) chunk = n_full ? static_cast<size_t>(n_full) : 1;
@@ -129,6 +132,8 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
                               : flacenc_hip_frame_bytes_bound(channels, block_size, bits_per_sample);
   const size_t ostride = (bound + 15) & ~static_cast<size_t>(15);
   const bool in_pinned = is_pinned(pcm), out_pinned = is_pinned(out);
+  h->last_stream_in_pinned = in_pinned;  // flacenc_hip_debug_last_stream_buffers
+  h->last_stream_out_pinned = out_pinned;
   int rc;
   const size_t dstride = padded_stride(block_size);
   if (!in_pinned && (rc = ensure_pinned(h, h->pin_in, &h->pin_in_cap, chunk * frame_in_bytes)) != FLACENC_HIP_OK) return rc;
@@ -155,6 +160,8 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   for (uint64_t f = 0; f < n_full; f += chunk)
     chunks.push_back({f, static_cast<size_t>(n_full - f < chunk ? n_full - f : chunk), block_size});
   if (tail) chunks.push_back({n_full, 1, tail});
+  h->last_stream_chunk = chunk;
+  h->last_stream_chunks = chunks.size();
 
   // staging copies for pageable caller memory run on the caller's thread + the handle's helper threads
   if ((!in_pinned || !out_pinned) && !h->copy_pool) {

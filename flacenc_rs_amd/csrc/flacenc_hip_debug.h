@@ -48,6 +48,22 @@ int flacenc_hip_debug_set_adaptive_order(flacenc_hip_handle* h, int on);
 /* the current span of two-pass launches (0: the material last seen was easy) and how many of it are left */
 int flacenc_hip_debug_adaptive_state(flacenc_hip_handle* h, int* span, int* left);
 
+/* Test hook (no reference counterpart): the chunk plan of the streaming host path.  `frames` != 0: the calls of
+ * flacenc_hip_encode_pcm / _stereo that follow cut their full blocks into chunks of `frames` frames in place of the rule
+ * clamp(48 MiB / frame bytes, 768, 8192); a call with fewer full blocks than that still runs them as one chunk, and the
+ * short last block stays a chunk of its own.  The bytes a call returns do not depend on the plan; the hook brings chunk
+ * seams and the reuse of the two staging slots down to a handful of frames.  0 (a fresh handle): the rule.  More than
+ * 8192 is FLACENC_HIP_ERR_BAD_ARGUMENT. */
+int flacenc_hip_debug_set_stream_chunk(flacenc_hip_handle* h, size_t frames);
+/* The plan the last flacenc_hip_encode_pcm / _stereo call on the handle ran: frames per chunk of full blocks (after the
+ * cut to the call's own full blocks; 1 when it had none) and the number of chunks, the short last block's included.
+ * A call that ran no chunk (total_samples == 0, rejected arguments) leaves 0 and 0.  Either pointer may be NULL. */
+int flacenc_hip_debug_last_stream_plan(flacenc_hip_handle* h, size_t* chunk_frames, size_t* n_chunks);
+/* How the last flacenc_hip_encode_pcm / _stereo call that got as far as its plan took the caller's buffers: 1 when it
+ * found `pcm` (`out`) page-locked and transferred it directly -- a pointer into the interior of such an allocation
+ * included --, 0 when it staged it through the handle's pinned slots.  Either pointer may be NULL. */
+int flacenc_hip_debug_last_stream_buffers(flacenc_hip_handle* h, int* in_pinned, int* out_pinned);
+
 #ifdef __cplusplus
 }
 #endif

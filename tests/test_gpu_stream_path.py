@@ -31,6 +31,22 @@ def reference_bytes(handle, frames, bps, cfg, rate, first=0, step=1):
     return handle.pack_stereo_frames(frames, res, resid, bps, rate, first, step)
 
 
+@pytest.fixture(scope="module")
+def one_call_cache():
+    """References that several cases of this module share; released when the module is done."""
+    cache = {}
+    yield cache
+    cache.clear()
+
+
+def one_call_stream(handle, cache, key, frames, bps, cfg, rate):
+    """The one-call path's (lengths uint32 [F], all bytes) for a whole stream, stated once per `key` and shared."""
+    if key not in cache:
+        want = reference_bytes(handle, frames, bps, cfg, rate)
+        cache[key] = (np.fromiter(map(len, want), np.uint32, len(want)), b"".join(want))
+    return cache[key]
+
+
 @pytest.mark.parametrize("bps,bytes_ps,n,F,use_fixed", [(16, 2, 4096, 9, True), (16, 2, 4096, 1700, False),
                                                         (24, 3, 4096, 5, True), (16, 2, 1152, 40, True),
                                                         (24, 3, 8192, 6, False)])
@@ -39,12 +55,9 @@ def test_stream_bytes_equal_the_one_call_path(handle, bps, bytes_ps, n, F, use_f
     cfg = _capi.make_frame_config(_capi.make_config(lpc_order=8 if n == 4096 else 12), use_fixed=use_fixed)
     pcm = pack_pcm(frames, bytes_ps)
     out, lens = handle.encode_pcm_stereo(pcm, cfg, bytes_ps, bps, n, 44100)
-    want = reference_bytes(handle, frames[: min(F, 64)], bps, cfg, 44100)
-    assert lens[: len(want)].tolist() == [len(b) for b in want]
-    pos = 0
-    for f, b in enumerate(want):
-        assert out[pos:pos + len(b)].tobytes() == b, f
-        pos += len(b)
+    want = reference_bytes(handle, frames, bps, cfg, 44100)   # every frame: the chunk seams included
+    assert lens.size == F and np.array_equal(lens, np.array([len(b) for b in want], np.uint32))
+    assert out.tobytes() == b"".join(want)
     assert int(lens.astype(np.int64).sum()) == out.size
     # every frame of the stream parses (sync, both CRCs) with its number, and decodes to the input
     pos = 0
@@ -104,10 +117,11 @@ def test_pinned_buffers_give_identical_bytes(handle):
 
 
 @pytest.mark.parametrize("threads", [0, 1, 3, 8])
-def test_staging_thread_counts_give_identical_bytes(handle, threads):
+def test_staging_thread_counts_give_identical_bytes(handle, one_call_cache, threads):
     """flacenc_hip_set_host_threads: the staging copies of pageable buffers are cut into slices for helper
-    threads; three chunks in flight (the two-step way out: a chunk's transfer runs during the next chunk's
-    staging copy in), a last chunk that is not full."""
+    threads; six chunks of 3072 frames (the 48 MiB regime of the chunk rule; the two-step way out: a chunk's transfer
+    runs during the next chunk's staging copy in), a last chunk that is not full.  The run at the default thread count is
+    held to the one-call path on every one of its 16684 frames."""
     n, bps, F = 4096, 16, 8192 * 2 + 300
     frames = _capi.sigen_frames(F, 2, n, bps, 90.0, 0.3, 0.2, seed=99, nthreads=4)
     cfg = _capi.make_frame_config(_capi.make_config(lpc_order=8), use_fixed=False)
@@ -120,6 +134,8 @@ def test_staging_thread_counts_give_identical_bytes(handle, threads):
     finally:
         handle.set_host_threads(4)
     assert np.array_equal(lens, want_lens) and out.tobytes() == want.tobytes()
+    one_lens, one_bytes = one_call_stream(handle, one_call_cache, "staging threads", frames, bps, cfg, 44100)
+    assert np.array_equal(want_lens, one_lens) and want.tobytes() == one_bytes
     first = reference_bytes(handle, frames[:8], bps, cfg, 44100)
     assert out[: sum(len(b) for b in first)].tobytes() == b"".join(first)
     last = reference_bytes(handle, frames[F - 4:], bps, cfg, 44100, F - 4, 1)
@@ -155,10 +171,10 @@ def test_stream_path_for_independent_channel_frames(handle, channels, F):
     pcm = np.ascontiguousarray(inter.astype("<i4").view(np.uint8).reshape(-1, channels, 4)[:, :, :2]).reshape(-1)
     out, lens = handle.encode_pcm(pcm, channels, cfg, 2, bps, n, 48000)
     assert lens.size == F
-    k = min(F - 1, 40)
+    k = F - 1   # every full frame: the chunk seams of the 8-channel case included
     res, resid = handle.encode_frames(frames[:k], bps, cfg)
     want = handle.pack_frames(frames[:k], res, resid, bps, 48000)
-    assert lens[:k].tolist() == [len(b) for b in want]
+    assert np.array_equal(lens[:k], np.array([len(b) for b in want], np.uint32))
     assert out[: int(lens[:k].astype(np.int64).sum())].tobytes() == b"".join(want)
     tres, tresid = handle.encode_frames(np.ascontiguousarray(tail[None]), bps, cfg)
     twant = handle.pack_frames(np.ascontiguousarray(tail[None]), tres, tresid, bps, 48000, first_frame_number=F - 1)
