@@ -133,6 +133,7 @@ QlpcKernelArgs base_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q
   a.stereo = stereo ? 1u : 0u;
   if (win) {
     a.window = win->dev;
+    a.window_lanes = win->dev_lanes;
     a.flat_lo = win->flat_lo;
     a.flat_hi = win->flat_hi;
   }

@@ -117,6 +117,7 @@ int subwave_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, c
     x.residual = fixed.rows;
     x.selector_keys = fixed.keys;
     x.window = nullptr;
+    x.window_lanes = nullptr;
     x.flat_lo = x.flat_hi = 0;
     x.lpc_order = 4;
     x.precision = 0;

@@ -41,6 +41,7 @@ struct WindowEntry {
   uint32_t alpha_bits;
   uint32_t start, end;  // FLACENC_HIP_WINDOW_PARTIAL_TUKEY / _PUNCHOUT_TUKEY: the piece, in FLACENC_HIP_WINDOW_UNIT; else 0
   float* dev;  // 32 pad + rows*16 floats
+  float* dev_lanes;  // n == 4096: the lane-major copy (window_lanes_core.h), behind `dev` in the same allocation; else nullptr
   int32_t flat_lo, flat_hi;
 };
 

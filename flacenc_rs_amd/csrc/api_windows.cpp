@@ -3,6 +3,7 @@
 #include <cmath>
 
 #include "api_internal.h"
+#include "window_lanes_core.h"
 
 namespace flacenc_hip {
 namespace {
@@ -102,12 +103,16 @@ int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t
   e.start = start;
   e.end = end;
   e.dev = nullptr;
+  e.dev_lanes = nullptr;
   e.flat_lo = -64;
   e.flat_hi = 0x7FFFFFFF;
   if (type != FLACENC_HIP_WINDOW_RECTANGLE) {
     const size_t rows = (n + 15) / 16;
     const size_t total = 32 + rows * 16 + 16;
-    std::vector<float> host(total, 0.0f);
+    // blocks of 4096: the lane-major copy the fused kernel reads (window_lanes_core.h) follows in the same allocation and
+    // the same upload, 256-byte aligned
+    const size_t lanes_at = n == window_lanes::kBlock ? ((total + 63) & ~static_cast<size_t>(63)) : 0;
+    std::vector<float> host(lanes_at ? lanes_at + window_lanes::kFloats : total, 0.0f);
     lpc_window_weights(type, alpha, start, end, n, host.data() + 32);
     // longest run of exactly-1.0 weights: chunks inside it skip the table
     int best_lo = 0, best_hi = 0, run_lo = -1;
@@ -124,8 +129,10 @@ int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t
     }
     e.flat_lo = best_lo;
     e.flat_hi = best_hi;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&e.dev), total * sizeof(float)));
-    HIP_TRY(h, hipMemcpy(e.dev, host.data(), total * sizeof(float), hipMemcpyHostToDevice));
+    if (lanes_at) window_lanes::build(host.data() + 32, host.data() + lanes_at);
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&e.dev), host.size() * sizeof(float)));
+    HIP_TRY(h, hipMemcpy(e.dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (lanes_at) e.dev_lanes = e.dev + lanes_at;
   }
   h->windows.push_back(e);
   *out = &h->windows.back();

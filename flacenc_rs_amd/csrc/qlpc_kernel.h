@@ -25,6 +25,8 @@ struct QlpcKernelArgs {
   uint32_t bps_uniform = 0;
   uint32_t stereo = 0;          // 1: workgroups 4f..4f+3 = L, R, M, S of 2-channel frame f
   const float* window = nullptr;      // device table with 32 leading pad floats, nullptr = all ones
+  // blocks of 4096 with a window: the same weights in the fused kernel's lane order (window_lanes_core.h), else nullptr
+  const float* window_lanes = nullptr;
   int32_t flat_lo = 0;          // window[t] == 1.0f for flat_lo <= t < flat_hi
   int32_t flat_hi = 0;
   uint32_t lpc_order = 0;

@@ -32,6 +32,7 @@
 #include "qlpc_kernel_impl.h"
 #include "solver_lanes_core.h"
 #include "sumabs_chain.h"
+#include "window_lanes_core.h"
 
 namespace flacenc_hip {
 namespace {
@@ -81,9 +82,27 @@ namespace {
 // The stereo 4096-sample instances at three workgroups per CU keep the window table as a third LDS image; at FOUR
 // (round 5: 128 registers, possible since the lane order needs one accumulator set where the chunk tree needed three) the
 // 40 KB a workgroup may take hold the two channel images, the exchange area and the certificate's scratch, and the weights
-// come from the L2-resident table, loaded unconditionally (it holds exactly 1.0f inside the flat part) one step ahead.
+// come from a table in global memory, loaded unconditionally (it holds exactly 1.0f inside the flat part) one step ahead.
+// That table is the lane-major copy of window_lanes_core.h (QlpcKernelArgs::window_lanes): lane l reads quads at 64 l + a
+// compile-time offset, which in the time-major table puts the 64 lanes of one load 256 bytes apart -- 64 cache lines per
+// load, 1280 per wave and phase 1 at order 8, ten times the lines of the workgroup's samples and residual; lane-major,
+// one load is 1 KB contiguous (8 lines) at scalar base + immediate + 16 lane.  -DFLACENC_WINDOW_LANES=0 keeps the
+// time-major loads (the A/B's other side, profiles/window_lanes_ab.txt: the L1 accesses per wave fall from 1548 to 588,
+// the deciding kernels gain 1.1 % / 3.2 % / 4.8 % at orders 8 / 10 / 12).  The instances with the fixed-LPC candidate
+// (variants 3 and 6) keep the time-major loads: +1.5 % on the synthetic A/B at order 10, but -1 % on the real-audio row
+// of the default configuration.
+#ifndef FLACENC_WINDOW_LANES
+#if defined(FLACENC_STEREO) && (FLACENC_STEREO == 3 || FLACENC_STEREO == 6)
+#define FLACENC_WINDOW_LANES 0
+#else
+#define FLACENC_WINDOW_LANES 1
+#endif
+#endif
 constexpr bool kWindowImageBuild = FLACENC_WAVE_OCC < 4;
 constexpr bool window_image(bool stereo, int spl) { return kWindowImageBuild && stereo && spl == 64; }
+constexpr bool window_from_lanes(bool stereo, int spl) {
+  return FLACENC_WINDOW_LANES != 0 && FLACENC_WAVE_OCC >= 4 && spl == 64 && !window_image(stereo, spl);
+}
 constexpr int kWaveN = 4096;        // block size handled by this kernel
 constexpr int kSeg = 68;            // dwords per lane segment: 64 samples + 4 pad (conflict-free b128)
 constexpr int kBufDwords = 65 * kSeg + 8;  // one leading all-zero segment (halo of lane 0) + look-ahead slack
@@ -1232,10 +1251,34 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
   const int flat_lo = a.flat_lo, flat_hi = a.flat_hi;
   int tl = lane << 6;         // first sample of this lane
   int lb = (lane + 1) * kSeg;  // its place in an image: widx(tl) (made opaque again at the top of the candidate loop)
+  // the lane-major table (window_lanes_core.h): this lane's quad of slot j sits 1024 j + 16 lane bytes into it -- a
+  // scalar base, an immediate and one lane-dependent 32-bit offset
+  constexpr bool WINDOW_FROM_LANES = window_from_lanes(STEREO, SPL);
+  const char* __restrict__ const wlanes = reinterpret_cast<const char*>(a.window_lanes);
+  const uint32_t wlane_off = (uint32_t)lane << 4;
+  // The chunk loop of phase 1 sets wchunk to its counter: the loop-dependent part of the address, 4096 bytes per chunk,
+  // goes into the scalar base together with the slot's multiple of four, and what is left of the slot is a compile-time
+  // immediate of -3072 .. 0 bytes.  The base is handed on through an empty asm: seeing through it, the compiler turns
+  // every offset beyond the 13-bit field into a 64-bit VGPR address of its own, four pairs alive across the step loop.
+  int wchunk = 0;
   // four window weights at sample tl + off (off a multiple of 4)
-  auto window4_at = [&](int ix, int t) -> float4 {  // ix: LDS index (window in LDS), t: sample number (else)
+  // ix: LDS index (window in LDS), t: sample number, off: t relative to the lane's first sample (lane-major table)
+  auto window4_at = [&](int ix, int t, int off) -> float4 {
     if (!has_window) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     if (WINDOW_IN_LDS) return *reinterpret_cast<const float4*>(&wlds[ix]);
+    if (WINDOW_FROM_LANES)  // (exactly 1.0f inside the flat part, 0.0f outside the block)
+    {
+      constexpr int kSlotBytes = window_lanes::kSlotFloats * 4;
+      const int slot = window_lanes::slot_of(off - 16 * wchunk);  // (a compile-time constant at every call)
+      const int group = (slot + 3) >> 2;
+      const char* base = wlanes + (uint32_t)(wchunk + group) * (uint32_t)(4 * kSlotBytes);
+      asm("" : "+s"(base));
+      // (behind the asm the pointer's address space is no longer inferred: say it, or the loads become flat_load)
+      typedef float v4f_t __attribute__((ext_vector_type(4)));
+      typedef const v4f_t __attribute__((address_space(1))) gv4f_t;
+      const v4f_t w4 = *(gv4f_t*)(base + (slot - 4 * group) * kSlotBytes + wlane_off);
+      return make_float4(w4.x, w4.y, w4.z, w4.w);
+    }
     if (FLACENC_WAVE_OCC >= 4) return *reinterpret_cast<const float4*>(wtab + t);  // (exactly 1.0f inside the flat part)
     float4 wv = make_float4(1.0f, 1.0f, 1.0f, 1.0f);  // exactly 1.0f inside the flat part
     if (!(t >= flat_lo && t + 4 <= flat_hi)) wv = *reinterpret_cast<const float4*>(wtab + t);
@@ -1424,14 +1467,14 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
       for (int q = 0; q < 2; ++q) {
         const int ix = p1ix(t0 + 4 * q, fwd_tag);
         rv[q] = ld4_at(kind, ix);
-        if (PREFETCH_W) rw[q] = window4_at(ix, p1t + t0 + 4 * q);
+        if (PREFETCH_W) rw[q] = window4_at(ix, p1t + t0 + 4 * q, t0 + 4 * q);
       }
     };
     // x_w[t] = (f32)s[t] * w[t]: one f32 rounding, then widen (lpc.rs:751-754)
     auto convert = [&](int base, auto fwd_tag) {
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
-        if (!PREFETCH_W) rw[q] = window4_at(p1ix(t_conv + 4 * q, fwd_tag), p1t + t_conv + 4 * q);
+        if (!PREFETCH_W) rw[q] = window4_at(p1ix(t_conv + 4 * q, fwd_tag), p1t + t_conv + 4 * q, t_conv + 4 * q);
         dw[base + 4 * q + 0] = (double)((float)rv[q].x * rw[q].x);
         dw[base + 4 * q + 1] = (double)((float)rv[q].y * rw[q].y);
         dw[base + 4 * q + 2] = (double)((float)rv[q].z * rw[q].z);
@@ -1445,7 +1488,7 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
       if (HP > 8) {
         const int ix = p1ix(-12, std::false_type{});
         const int4 v = ld4_at(kind, ix);
-        const float4 wv = window4_at(ix, p1t - 12);
+        const float4 wv = window4_at(ix, p1t - 12, -12);
         dw[HP - 4 + 0] = (double)((float)v.x * wv.x);
         dw[HP - 4 + 1] = (double)((float)v.y * wv.y);
         dw[HP - 4 + 2] = (double)((float)v.z * wv.z);
@@ -1463,6 +1506,7 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
     auto chunk = [&](auto masked_tag, auto start_tag, int i) {
       constexpr bool MASKED = decltype(masked_tag)::value;
       constexpr bool START = decltype(start_tag)::value;  // the lane's chains start here (literal +0.0), else they go on
+      wchunk = i;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int t0 = 16 * i + 8 * h;  // relative to tl
@@ -1503,6 +1547,7 @@ __global__ void __launch_bounds__(256, FLACENC_WAVE_OCC) qlpc_wave4096_kernel(Ql
     // ... and the 64 lane sums meet by a reduce-scatter (lane_order_reduce): slot q of row r = lane >> 4 ends up with lag
     // 4 q + 2 (r & 1) + (r >> 1), complete in the row's lane 15
     lane_order_reduce<NLAG>(acc, Rq);
+    wchunk = 0;
     if (SPL != 64) {
       // Blocks of 4608: the last 512 samples, 16 per lane on lanes 0..31 (the upper lanes shadow them and contribute
       // +0.0), a chain of their own per lag, reduced the same way and added to the main part's sums
@@ -2673,6 +2718,8 @@ hipError_t launch_wave4096(const QlpcKernelArgs& a, hipStream_t stream) {
   constexpr size_t smem = (size_t)(STEREO ? (window_image(STEREO, SPL) ? 3 : 2) : 4) * WaveGeom<SPL>::Buf * 4 +
                           ((MAXP > 10 && !PACK && window_image(STEREO, SPL)) ? 4 * (MAXP + 1) * 8 : 4 * ((MAXP + 1) * 8 + 64)) +
                           (cert ? 16 : 0) + ((cert && !window_image(STEREO, SPL)) ? cert_scratch_bytes(STEREO, SPL) : 0);
+  // (a window without its lane-major copy: the record was not filled by base_args)
+  if (window_from_lanes(STEREO, SPL) && a.window != nullptr && a.window_lanes == nullptr) return hipErrorInvalidValue;
   static DynamicLdsOptIn opt_in;  // per instantiation, per device inside
   if (hipError_t err = opt_in.ensure(reinterpret_cast<const void*>(kern), smem); err != hipSuccess) return err;
   const uint32_t blocks = STEREO ? a.n_subframes / 4u : (a.n_subframes + 3u) / 4u;
