@@ -365,8 +365,14 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
         for (uint32_t q = tid; q < nparts; q += kPackThreads) rice2 |= rice_p[q] > 14 ? 1u : 0u;
         rice2 = __syncthreads_or((int)rice2) ? 1u : 0u;
         const uint32_t pbits = rice2 ? 5u : 4u;
-        if (tid == 192) put_bits(words, sb + head_bits, (rice2 << 4) | porder, 6u);
-        const uint32_t res_base = sb + head_bits + 6u;
+        // A first partition without samples (order == part_len) still has its parameter (bitrepr.rs:567-571), and the
+        // walk below meets no sample that could carry it: it goes out with the header, the slices start behind it.
+        const uint32_t lead0 = (order != 0u && order == part_len) ? pbits : 0u;
+        if (tid == 192) {
+          put_bits(words, sb + head_bits, (rice2 << 4) | porder, 6u);
+          put_bits(words, sb + head_bits + 6u, rice_p[0], lead0);
+        }
+        const uint32_t res_base = sb + head_bits + 6u + lead0;
         // contiguous slice of samples per thread; pass 1 counts its bits, pass 2 writes them.
         // Up to 16 samples per thread (blocks <= 4096) are held in registers as zig-zag codes.
         const int per = (n + kPackThreads - 1) / kPackThreads;

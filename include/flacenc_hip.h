@@ -558,6 +558,20 @@ int flacenc_hip_fixed_lpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_f
  * 150 KiB -- e.g. 8 channels x 16384 samples x 24 bits -- are FLACENC_HIP_ERR_UNSUPPORTED.
  * sample_rate / bits_per_sample go into the header specs exactly as encode_frame_impl chooses them
  * (src/coding.rs:431-436); a rate or size without a code becomes "Unspecified".
+ *
+ * The packers' domain, for callers that build or move records themselves (flacenc_hip_pack_frames alike).  Nothing
+ * of it is checked on the device:
+ *   - a record describes a subframe the project's decoder reads (flacenc_hip_decode_frames);
+ *   - order <= block_size >> rice_order: the first Rice partition may be empty (its parameter is still written),
+ *     never negative;
+ *   - rice_params[0 .. 2^rice_order) are 0..30 -- the record cannot express an escaped partition; the residual is
+ *     written with 5-bit parameters exactly when one of them exceeds 14;
+ *   - shift 0..15 and precision 1..15 (LPC); a Fixed record holds FIXED_LPC_COEFS[order], shift 0, precision 0;
+ *   - every sample fits its width (bits_per_sample, + 1 for the side role, - pad[c] wasted bits) and every residual
+ *     an int32; the residual row is that of the shifted signal, its first `order` slots are not read;
+ *   - bits[] are the exact SubFrame::count_bits (+ pad[c]), and over a frame they sum to at most
+ *     channels * (8 + block_size * bits_per_sample): the LDS image is sized from flacenc_hip_*_frame_bytes_bound plus a
+ *     few words, and a frame beyond it would be written outside the image.
  */
 size_t flacenc_hip_stereo_frame_bytes_bound(uint32_t block_size, uint32_t bits_per_sample);
 int flacenc_hip_pack_stereo_frames(flacenc_hip_handle* h, const int32_t* frames, size_t n_frames,

@@ -80,10 +80,16 @@ def header(block_size, ch_tag, bps, number, variable=False, bs_code=None, sr_cod
 def residuals(x, coefs, shift, order):
     """e[t] = x[t] - (sum c_j x[t-1-j] >> shift) in the decoder's arithmetic (inverse of the reconstruction)."""
     x = np.asarray(x, np.int64)
-    e = np.zeros(len(x), np.int64)
-    for t in range(order, len(x)):
-        pred = sum(int(c) * int(x[t - 1 - j]) for j, c in enumerate(coefs))
-        e[t] = x[t] - (pred >> max(shift, 0))
+    n = len(x)
+    e = np.zeros(n, np.int64)
+    if order >= n:
+        return e
+    # one int64 pass per coefficient: |c| < 2^15, |x| < 2^25 and at most 32 terms stay far below 2^63
+    assert len(coefs) <= order
+    pred = np.zeros(n - order, np.int64)
+    for j, c in enumerate(coefs):
+        pred += int(c) * x[order - 1 - j:n - 1 - j]
+    e[order:] = x[order:] - (pred >> max(shift, 0))
     return e
 
 
