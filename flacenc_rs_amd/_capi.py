@@ -56,6 +56,7 @@ COMM_ID_BYTES = 128  # FLACENC_HIP_COMM_ID_BYTES
 # FLACENC_HIP_DECODE_* status bits of the frame decoder, FLACENC_HIP_INDEX_ERROR
 DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 8
 DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
+DECODE_NO_ROOM, DECODE_CHAIN = 256, 512  # totals[3] of flacenc_hip_decode_pcm: why the call stopped
 INDEX_ERROR = 1 << 63
 VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flacenc_hip_encode_variable*
 
@@ -64,7 +65,8 @@ ABI_VERSION = 6  # FLACENC_HIP_ABI_VERSION of include/flacenc_hip.h
 DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_keys", "flacenc_hip_debug_set_cert_stats",
                  "flacenc_hip_debug_set_adaptive_order", "flacenc_hip_debug_adaptive_state",
                  "flacenc_hip_debug_set_order_guess_trace", "flacenc_hip_debug_set_stream_chunk",
-                 "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers")
+                 "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers",
+                 "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -116,6 +118,8 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_frames",
     "flacenc_hip_verify_frames_async",
     "flacenc_hip_index_frames_async",
+    "flacenc_hip_pack_le_bytes",
+    "flacenc_hip_decode_pcm",
     "flacenc_hip_variable_bytes_bound",
     "flacenc_hip_variable_max_frames",
     "flacenc_hip_encode_variable_async",
@@ -296,6 +300,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
         L.flacenc_hip_debug_set_stream_chunk.argtypes = [vp, C.c_size_t]
         L.flacenc_hip_debug_last_stream_plan.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.flacenc_hip_debug_last_stream_buffers.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "flacenc_hip_debug_set_decode_plan"):
+        L.flacenc_hip_debug_set_decode_plan.argtypes = [vp, C.c_size_t, C.c_size_t]
+        L.flacenc_hip_debug_last_decode_plan.argtypes = [vp] + [C.POINTER(C.c_size_t)] * 4
     batch_args = [vp, C.POINTER(QlpcConfig), i32p, C.c_size_t, C.c_uint32, C.c_size_t, u8p, vp, i32p,
                   C.c_size_t, f64p, f64p]
     L.flacenc_hip_qlpc_batch.argtypes = batch_args + [C.c_int]
@@ -393,6 +400,12 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_index_frames_async.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp,
                                                  vp]
     L.flacenc_hip_index_frames_async.restype = C.c_int
+    pack_le_args = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, vp]
+    L.flacenc_hip_pack_le_bytes.argtypes = pack_le_args + [C.c_int]
+    L.flacenc_hip_pack_le_bytes.restype = C.c_int
+    L.flacenc_hip_decode_pcm.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
+                                         C.c_uint64, vp]
+    L.flacenc_hip_decode_pcm.restype = C.c_int
     L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -631,6 +644,18 @@ class Handle:
         a, b = C.c_int(0), C.c_int(0)
         self._check(self._hook("flacenc_hip_debug_last_stream_buffers")(self._h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
+
+    def debug_set_decode_plan(self, window_bytes: int = 0, group_frames: int = 0):
+        """decode_pcm cuts its input into windows of `window_bytes` (raised to 2B by the call) and decodes groups of
+        `group_frames` frames in place of its rules (flacenc_hip_debug.h); 0: the rule again."""
+        self._check(self._hook("flacenc_hip_debug_set_decode_plan")(self._h, int(window_bytes), int(group_frames)))
+
+    def debug_last_decode_plan(self):
+        """(window bytes, windows indexed, frames per group, groups decoded) of the last decode_pcm call on this handle;
+        zeros when it ran none."""
+        v = [C.c_size_t(0) for _ in range(4)]
+        self._check(self._hook("flacenc_hip_debug_last_decode_plan")(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def synchronize(self):
         self._check(self._lib.flacenc_hip_synchronize(self._h))
@@ -963,6 +988,67 @@ class Handle:
                                                       max_frames, offsets_ptr, lengths_ptr, n_frames_ptr,
                                                       stream or None)
         self._check(rc)
+
+    def pack_le_bytes(self, frames, block_sizes, bytes_per_sample: int, out_capacity: int | None = None,
+                      out: np.ndarray | None = None):
+        """flacenc_hip_pack_le_bytes on host arrays: rows int32 [n_frames, channels, stride] + one block size per frame ->
+        (packed interleaved little-endian PCM uint8, sample offsets uint64 [n_frames + 1], total samples, fits).  `out`
+        (uint8; its size is the capacity unless out_capacity says less) defaults to exactly the room the block sizes need;
+        fits is False (FLACENC_HIP_ERR_BAD_ARGUMENT from the call: nothing was written) when the output needs more."""
+        x = np.ascontiguousarray(frames, np.int32)
+        n, channels, stride = x.shape
+        bs = np.ascontiguousarray(block_sizes, np.uint32)
+        assert bs.shape == (n,)
+        need = int(np.minimum(bs.astype(np.uint64), stride).sum()) * channels * bytes_per_sample
+        if out is None:
+            out = np.zeros(max(1, need if out_capacity is None else out_capacity), np.uint8)
+        cap = (need if out.size >= need else out.size) if out_capacity is None else out_capacity
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and cap <= out.size
+        off = np.zeros(n + 1, np.uint64)
+        total = np.zeros(1, np.uint64)
+        rc = self._lib.flacenc_hip_pack_le_bytes(self._h, x.ctypes.data if n else None, stride,
+                                                 bs.ctypes.data if n else None, n, channels, bytes_per_sample,
+                                                 out.ctypes.data, cap, off.ctypes.data, total.ctypes.data, MEM_HOST)
+        fits = int(total[0]) * channels * bytes_per_sample <= cap
+        if not (rc == ERR_BAD_ARGUMENT and not fits):
+            self._check(rc)
+        return out[: int(total[0]) * channels * bytes_per_sample if fits else 0], off, int(total[0]), fits
+
+    def pack_le_bytes_device(self, frames_ptr: int, stride: int, block_sizes_ptr: int, n_frames: int, channels: int,
+                             bytes_per_sample: int, out_ptr: int, out_capacity: int, sample_offsets_ptr: int | None,
+                             total_ptr: int, check: bool = True) -> int:
+        """flacenc_hip_pack_le_bytes on device pointers: decoded rows in HBM -> packed interleaved PCM in HBM, on the
+        handle's stream; returns when the launches have run (work the caller queued on other streams must be complete).
+        -> the call's code; with check=False a failure is returned instead of raised (ERR_BAD_ARGUMENT is also what an
+        output that needs more than out_capacity gives: `total` and the offsets are then written, `out` is not)."""
+        rc = self._lib.flacenc_hip_pack_le_bytes(self._h, frames_ptr or None, stride, block_sizes_ptr or None, n_frames,
+                                                 channels, bytes_per_sample, out_ptr or None, out_capacity,
+                                                 sample_offsets_ptr or None, total_ptr, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return rc
+
+    def decode_pcm(self, data, channels: int, bits_per_sample: int, max_block_size: int,
+                   bytes_per_sample: int | None = None, out: np.ndarray | None = None, out_capacity: int | None = None):
+        """flacenc_hip_decode_pcm: a buffer of frames (bytes, or a uint8 array -- a pinned_array() or a view into one is
+        transferred directly) -> (packed interleaved little-endian PCM, a view of `out`; totals = [frames, samples, bytes
+        consumed, stop reason]).  `out` (uint8; pinned or not) is the caller's buffer, its size the capacity unless
+        out_capacity says less; without one the call gets room for len(data) // 9 + 1 frames of max_block_size, which
+        always suffices but is only sensible for small inputs."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        width = bytes_per_sample or (bits_per_sample + 7) // 8
+        if out is None:
+            room = (buf.size // 9 + 1) * max_block_size * channels * width if out_capacity is None else out_capacity
+            out = np.zeros(max(1, room), np.uint8)
+        cap = out.size if out_capacity is None else out_capacity
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and cap <= out.size
+        totals = np.zeros(4, np.uint64)
+        rc = self._lib.flacenc_hip_decode_pcm(self._h, buf.ctypes.data if buf.size else None, buf.size, channels,
+                                              bits_per_sample, max_block_size, width, out.ctypes.data, cap,
+                                              totals.ctypes.data)
+        self._check(rc)
+        return out[: int(totals[1]) * channels * width], [int(t) for t in totals]
 
     # -- block-size search: variable-blocking streams ---------------------------------------------------------
     def encode_variable(self, frames, bits_per_sample: int, cfg: FrameConfig, levels: int, total_samples: int | None = None,

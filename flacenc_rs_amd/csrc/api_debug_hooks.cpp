@@ -68,4 +68,25 @@ int flacenc_hip_debug_last_stream_buffers(flacenc_hip_handle* h, int* in_pinned,
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_set_decode_plan(flacenc_hip_handle* h, size_t window_bytes, size_t group_frames) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (group_frames > 8192) {  // the rule's own upper end
+    h->last_error = "debug_set_decode_plan: more than 8192 frames per group";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->decode_window_override = window_bytes;
+  h->decode_group_override = group_frames;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_bytes, size_t* n_windows,
+                                       size_t* group_frames, size_t* n_groups) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (window_bytes) *window_bytes = h->last_decode_window;
+  if (n_windows) *n_windows = h->last_decode_windows;
+  if (group_frames) *group_frames = h->last_decode_group;
+  if (n_groups) *n_groups = h->last_decode_groups;
+  return FLACENC_HIP_OK;
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@
 //   api_pack.cpp         Frame::write, frame lengths, the wire format, stream offsets
 //   api_stream.cpp       the streaming host path (flacenc_hip_encode_pcm)
 //   api_decode.cpp       decode / verify / index
+//   api_decode_stream.cpp  rows to packed PCM (flacenc_hip_pack_le_bytes), the streaming way back (flacenc_hip_decode_pcm)
 //   api_variable.cpp     the block-size search
 //   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
 #ifndef FLACENC_HIP_API_INTERNAL_H_
@@ -164,6 +165,8 @@ struct flacenc_hip_handle {
   std::vector<flacenc_hip::LpcWindow> lpc_windows{std::begin(flacenc_hip::kDefaultLpcWindows), std::end(flacenc_hip::kDefaultLpcWindows)};
   flacenc_hip::DeviceBuffer d_samples, d_residual, d_params, d_bps, d_autocorr, d_lpc, d_tables, d_keys, d_sel, d_results, d_out, d_outlen, d_cparams, d_cresid, d_fparams, d_fresid, d_fkeys, d_split, d_presid, d_sumabs, d_minmax, d_marked, d_irlsw, d_gram;
   flacenc_hip::DeviceBuffer d_dec, d_dec_io, d_idx;  // frame decoder: skim records, host-pointer staging, index candidates
+  // pack_le_bytes: the offsets when the caller wants none, host-pointer staging; decode_pcm: a window's index
+  flacenc_hip::DeviceBuffer d_ppk_off, d_ppk_io, d_dpcm_idx;
   // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
   flacenc_hip::DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
   // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
@@ -193,6 +196,10 @@ struct flacenc_hip_handle {
   size_t stream_chunk_override = 0;
   size_t last_stream_chunk = 0, last_stream_chunks = 0;
   bool last_stream_in_pinned = false, last_stream_out_pinned = false;  // how that call took the caller's buffers
+  // test hook, see flacenc_hip_debug_set_decode_plan: window bytes and frames per group of flacenc_hip_decode_pcm in
+  // place of its rules (0: the rule), and the plan the last call ran
+  size_t decode_window_override = 0, decode_group_override = 0;
+  size_t last_decode_window = 0, last_decode_windows = 0, last_decode_group = 0, last_decode_groups = 0;
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch
@@ -279,6 +286,14 @@ int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
                   size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps, uint32_t bps_uniform,
                   bool stereo, flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
                   unsigned long long* selector_keys, hipStream_t stream, uint32_t residual_mode = 0);
+
+// ---- api_stream.cpp ----
+// what the streaming host paths (encode_pcm, decode_pcm) share: is the caller's buffer page-locked, the two pinned
+// slots of a staging buffer, the copy streams and events, the helper threads of the staging copies
+bool is_pinned(const void* p);
+int ensure_pinned(flacenc_hip_handle* h, void** slot, size_t* cap_field, size_t bytes);
+int ensure_stream_objects(flacenc_hip_handle* h);
+int ensure_copy_pool(flacenc_hip_handle* h, const char* what);
 
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);

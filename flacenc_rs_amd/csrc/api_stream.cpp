@@ -4,7 +4,7 @@
 
 using namespace flacenc_hip;
 
-namespace {
+namespace flacenc_hip {
 bool is_pinned(const void* p) {
   hipPointerAttribute_t attr{};
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
@@ -26,7 +26,41 @@ int ensure_pinned(flacenc_hip_handle* h, void** slot, size_t* cap_field, size_t 
   *cap_field = want;
   return FLACENC_HIP_OK;
 }
-}  // namespace
+
+int ensure_stream_objects(flacenc_hip_handle* h) {
+  if (h->s_in) return FLACENC_HIP_OK;
+  HIP_TRY(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
+  HIP_TRY(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_h2d[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fill[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pack[i], hipEventDisableTiming));
+    HIP_TRY(h, hipEventCreateWithFlags(&h->ev_d2h[i], hipEventDisableTiming));
+  }
+  return FLACENC_HIP_OK;
+}
+
+// staging copies for pageable caller memory run on the caller's thread + the handle's helper threads
+int ensure_copy_pool(flacenc_hip_handle* h, const char* what) {
+  if (h->copy_pool) return FLACENC_HIP_OK;
+  const int want = h->host_threads < 0 ? 4 : h->host_threads;  // total, the caller's thread included
+  // (thread creation can throw std::system_error, vector growth std::bad_alloc: nothing unwinds across the ABI)
+  try {
+    h->copy_pool.reset(new CopyPool(want > 1 ? static_cast<unsigned>(want - 1) : 0u));
+  } catch (...) {
+    h->copy_pool.reset();
+  }
+  if (!h->copy_pool) {
+    try {
+      h->copy_pool.reset(new CopyPool(0u));  // no helper threads: plain memcpy on the caller's thread
+    } catch (...) {
+      h->last_error = std::string(what) + ": out of host memory";
+      return FLACENC_HIP_ERR_DEVICE;
+    }
+  }
+  return FLACENC_HIP_OK;
+}
+}  // namespace flacenc_hip
 
 extern "C" {
 
@@ -108,16 +142,8 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   // (a last block shorter than MIN_BLOCK_SIZE_FOR_PREDICTION is a frame like any other: encode_subframe skips
   // its predictors, coding.rs:396, and the frame-level calls below do the same)
   HIP_TRY(h, hipSetDevice(h->device));
-  if (!h->s_in) {
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->s_in, hipStreamNonBlocking));
-    HIP_TRY(h, hipStreamCreateWithFlags(&h->s_out, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-      HIP_TRY(h, hipEventCreateWithFlags(&h->ev_h2d[i], hipEventDisableTiming));
-      HIP_TRY(h, hipEventCreateWithFlags(&h->ev_fill[i], hipEventDisableTiming));
-      HIP_TRY(h, hipEventCreateWithFlags(&h->ev_pack[i], hipEventDisableTiming));
-      HIP_TRY(h, hipEventCreateWithFlags(&h->ev_d2h[i], hipEventDisableTiming));
-    }
-  }
+  int rc;
+  if ((rc = ensure_stream_objects(h)) != FLACENC_HIP_OK) return rc;
   // chunks of whole frames: big enough to run the kernels at full occupancy (>= 768 workgroups),
   // small enough that two slots of staging stay modest and the pipeline has several stages in flight
   const size_t frame_in_bytes = static_cast<size_t>(block_size) * channels * bytes_per_sample;
@@ -134,7 +160,6 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   const bool in_pinned = is_pinned(pcm), out_pinned = is_pinned(out);
   h->last_stream_in_pinned = in_pinned;  // flacenc_hip_debug_last_stream_buffers
   h->last_stream_out_pinned = out_pinned;
-  int rc;
   const size_t dstride = padded_stride(block_size);
   if (!in_pinned && (rc = ensure_pinned(h, h->pin_in, &h->pin_in_cap, chunk * frame_in_bytes)) != FLACENC_HIP_OK) return rc;
   if (!out_pinned && (rc = ensure_pinned(h, h->pin_out, &h->pin_out_cap, chunk * ostride)) != FLACENC_HIP_OK) return rc;
@@ -163,24 +188,7 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   h->last_stream_chunk = chunk;
   h->last_stream_chunks = chunks.size();
 
-  // staging copies for pageable caller memory run on the caller's thread + the handle's helper threads
-  if ((!in_pinned || !out_pinned) && !h->copy_pool) {
-    const int want = h->host_threads < 0 ? 4 : h->host_threads;  // total, the caller's thread included
-    // (thread creation can throw std::system_error, vector growth std::bad_alloc: nothing unwinds across the ABI)
-    try {
-      h->copy_pool.reset(new CopyPool(want > 1 ? static_cast<unsigned>(want - 1) : 0u));
-    } catch (...) {
-      h->copy_pool.reset();
-    }
-    if (!h->copy_pool) {
-      try {
-        h->copy_pool.reset(new CopyPool(0u));  // no helper threads: plain memcpy on the caller's thread
-      } catch (...) {
-        h->last_error = "encode_pcm: out of host memory";
-        return FLACENC_HIP_ERR_DEVICE;
-      }
-    }
-  }
+  if ((!in_pinned || !out_pinned) && (rc = ensure_copy_pool(h, "encode_pcm")) != FLACENC_HIP_OK) return rc;
   uint64_t written = 0;
   // A chunk's way out has two steps so that the host never idles on a transfer: start_out waits for the
   // chunk's lengths and starts the device -> host copy of exactly its bytes (contiguous on the device

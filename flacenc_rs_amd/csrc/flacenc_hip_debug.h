@@ -64,6 +64,21 @@ int flacenc_hip_debug_last_stream_plan(flacenc_hip_handle* h, size_t* chunk_fram
  * included --, 0 when it staged it through the handle's pinned slots.  Either pointer may be NULL. */
 int flacenc_hip_debug_last_stream_buffers(flacenc_hip_handle* h, int* in_pinned, int* out_pinned);
 
+/* Test hook (no reference counterpart): the plan of flacenc_hip_decode_pcm.  window_bytes != 0: the calls that follow
+ * cut their input into windows of that many bytes in place of the rule (128 MiB); a value below 2B, B =
+ * flacenc_hip_frame_bytes_bound(channels, max_block_size, bits_per_sample) (for 2 channels the larger of that and
+ * flacenc_hip_stereo_frame_bytes_bound), is raised to 2B by the call.  group_frames != 0: they decode and pack groups of
+ * that many frames in place of the rule clamp(128 MiB / (max_block_size*channels*bytes_per_sample), 64, 8192).  The bytes a
+ * call returns and its totals do not depend on the plan; the hook brings window edges, group seams and the reuse of the
+ * two slots down to a handful of frames.  0 (a fresh handle): the rule.  More than 8192 frames is
+ * FLACENC_HIP_ERR_BAD_ARGUMENT. */
+int flacenc_hip_debug_set_decode_plan(flacenc_hip_handle* h, size_t window_bytes, size_t group_frames);
+/* The plan the last flacenc_hip_decode_pcm call on the handle ran: the window size in bytes and the windows it indexed,
+ * the frames per group (after the cut to what the call's bytes can hold) and the groups it decoded.  A call that ran
+ * no window (n_bytes == 0, rejected arguments) leaves zeros.  Any pointer may be NULL. */
+int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_bytes, size_t* n_windows,
+                                       size_t* group_frames, size_t* n_groups);
+
 #ifdef __cplusplus
 }
 #endif

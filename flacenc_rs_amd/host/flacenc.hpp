@@ -1163,5 +1163,31 @@ inline std::vector<DecodedFrame> decode_frames(HipContext& gpu, const uint8_t* b
   return out;
 }
 
+// `flacenc decode` for a whole stream: the verified chain of frames from bytes[0] (host memory, frames only) to packed
+// interleaved little-endian PCM of ceil(bits_per_sample / 8) bytes per sample -- the bytes the STREAMINFO MD5 is defined
+// over (src/source.rs:406-428) -- through flacenc_hip_decode_pcm.  out[0 .. samples * channels * width) is written and
+// nothing behind it; after FLACENC_HIP_DECODE_NO_ROOM a second call on bytes + consumed continues the stream.
+struct DecodedPcm {
+  uint64_t frames = 0;
+  uint64_t samples = 0;   // inter-channel samples written
+  uint64_t consumed = 0;  // bytes of input: the start of the frame the call stopped at, or n_bytes
+  uint32_t stop = 0;      // 0, FLACENC_HIP_DECODE_NO_ROOM, FLACENC_HIP_DECODE_CHAIN or a frame's FLACENC_HIP_DECODE_* bits
+};
+
+inline DecodedPcm decode_pcm(HipContext& gpu, const uint8_t* bytes, size_t n_bytes, size_t channels,
+                             size_t bits_per_sample, size_t max_block_size, uint8_t* out, size_t out_capacity) {
+  uint64_t totals[4] = {0, 0, 0, 0};
+  const int rc = flacenc_hip_decode_pcm(gpu.get(), bytes, n_bytes, static_cast<uint32_t>(channels),
+                                        static_cast<uint32_t>(bits_per_sample), static_cast<uint32_t>(max_block_size),
+                                        static_cast<uint32_t>((bits_per_sample + 7) / 8), out, out_capacity, totals);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  DecodedPcm r;
+  r.frames = totals[0];
+  r.samples = totals[1];
+  r.consumed = totals[2];
+  r.stop = static_cast<uint32_t>(totals[3]);
+  return r;
+}
+
 }  // namespace flacenc
 #endif  // FLACENC_HOST_FLACENC_HPP_

@@ -841,6 +841,65 @@ int flacenc_hip_index_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, 
                                    uint32_t bits_per_sample, size_t max_frames, uint64_t* offsets, uint32_t* lengths,
                                    uint64_t* n_frames, void* stream);
 
+/*
+ * Decoded rows to packed PCM: the inverse of flacenc_hip_fill_le_bytes (interleave + i32s_to_le_bytes), with one block
+ * size per frame so that the rows of a variable-blocking stream pack back to back.
+ *   frames          frame f, channel c is the row at frames + (f*channels + c)*stride: flacenc_hip_decode_frames' `out`
+ *   block_sizes     samples of frame f; 0 is legal and contributes nothing (what the decoder leaves for a frame with a
+ *                   status); a value above `stride` counts as `stride`, so garbage never reads outside a row
+ *   out             with off[f] the exclusive prefix sum of the block sizes, sample i of frame f, channel c goes to
+ *                   out + ((off[f] + i)*channels + c)*bytes_per_sample as the low bytes_per_sample bytes of its
+ *                   two's-complement value, little-endian; a value that does not fit the width KEEPS ITS LOW BYTES (no
+ *                   saturation, no status): the exact inverse of le_bytes_to_i32s for every value that fits
+ *   sample_offsets  n_frames + 1 entries, NULL to skip: off[f], and the total in the last
+ *   total           1 entry: the inter-channel samples of all frames
+ * For the bytes_per_sample a stream's bit depth needs (ceil(bits / 8)) the output is the byte string the STREAMINFO MD5
+ * is defined over (src/source.rs:406-428), and for 16 / 24 bits the WAV payload.
+ * Nothing is read beyond block_sizes[f] samples of a row and no byte of `out` outside [0, total*channels*
+ * bytes_per_sample) is written; when that range exceeds out_capacity NOTHING is written to `out`, `total` and
+ * `sample_offsets` still are, and the call returns FLACENC_HIP_ERR_BAD_ARGUMENT.  channels 1..8,
+ * bytes_per_sample 1..4, up to 2^31 - 1 frames (no limit of 65535 as in flacenc_hip_fill_le_bytes); `out` may be NULL
+ * when out_capacity is 0.  Host or device pointers (memory_kind); with device pointers the call enqueues two launches on
+ * the handle's stream (with sample_offsets NULL the offsets live in the handle's scratch) and returns when they have run.
+ * There is no stream-taking form yet: inside the library the same two launches run stream-ordered behind each group of
+ * flacenc_hip_decode_pcm.
+ */
+int flacenc_hip_pack_le_bytes(flacenc_hip_handle* h, const int32_t* frames, size_t stride, const uint32_t* block_sizes,
+                              size_t n_frames, uint32_t channels, uint32_t bytes_per_sample, uint8_t* out,
+                              uint64_t out_capacity, uint64_t* sample_offsets, uint64_t* total, int memory_kind);
+/*
+ * The mirror of flacenc_hip_encode_pcm: frame bytes in host memory in, packed interleaved little-endian PCM in host
+ * memory out (the flacenc_hip_pack_le_bytes layout), in one call.  `bytes` holds only frames -- a .flac file after its
+ * metadata blocks, or the output of flacenc_hip_encode_pcm / flacenc_hip_encode_variable --, `bytes` and `out` are
+ * pageable or flacenc_hip_host_alloc memory.  The call decodes the verified chain of frames that starts at byte 0
+ * (flacenc_hip_index_frames_async: header checks, CRC-8, CRC-16, each frame starting where the one before ends), writes
+ * their samples to `out` back to back and stops at the first position where it cannot go on.  It returns
+ * FLACENC_HIP_OK whenever the arguments were acceptable and the device worked; totals says how far it got:
+ *   totals[0]  frames decoded            totals[1]  inter-channel samples written
+ *   totals[2]  bytes of input consumed: the start of the frame it stopped at, or n_bytes
+ *   totals[3]  why it stopped: 0, the chain ended exactly at n_bytes;
+ *              FLACENC_HIP_DECODE_NO_ROOM, the next frame's samples do not fit in out_capacity (every frame before it is
+ *              complete in `out`; a second call on bytes + totals[2] continues the stream, and the two outputs
+ *              concatenated are the output of one call with enough room);
+ *              FLACENC_HIP_DECODE_CHAIN, no verified frame starts at totals[2] (garbage, a corrupted frame, a stream cut
+ *              inside a frame -- or a frame longer than flacenc_hip_frame_bytes_bound(channels, max_block_size,
+ *              bits_per_sample), which no frame this library writes is);
+ *              else the FLACENC_HIP_DECODE_* bits of a frame of the chain that decoded with a status.
+ * In every case `out` beyond totals[1]*channels*bytes_per_sample bytes is untouched, and garbage in never faults.
+ * channels 1..8; bits_per_sample 4..24 (else FLACENC_HIP_ERR_UNSUPPORTED); max_block_size 1..65536 (STREAMINFO's; a frame
+ * above it stops the call with UNSUPPORTED); bytes_per_sample from ceil(bits_per_sample / 8) to 4; n_bytes == 0 returns OK
+ * with all-zero totals.  Device memory and pinned staging are bounded whatever n_bytes and the decoded size are: the
+ * input moves in windows of bytes (128 MiB; the upload of the next window does not wait for the index of this one), the
+ * rows and the PCM in groups of frames (128 MiB / (max_block_size*channels*bytes_per_sample), 64..8192) over two slots
+ * and the handle's three streams, with the staging copies of pageable buffers on the handle's host threads
+ * (flacenc_hip_set_host_threads).  The bytes written and totals do not depend on that plan.
+ */
+#define FLACENC_HIP_DECODE_NO_ROOM 256u
+#define FLACENC_HIP_DECODE_CHAIN 512u
+int flacenc_hip_decode_pcm(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, uint32_t channels,
+                           uint32_t bits_per_sample, uint32_t max_block_size, uint32_t bytes_per_sample, uint8_t* out,
+                           uint64_t out_capacity, uint64_t totals[4]);
+
 /* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
 /*
  * Each region coded at the block size that compresses it best (BASELINE config 5's "beat-search block sizing"; the

@@ -381,6 +381,19 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, channels: u32, bits_per_sample: u32, max_frames: usize,
         offsets: *mut u64, lengths: *mut u32, n_frames: *mut u64, stream: *mut c_void,
     ) -> c_int;
+    /// The inverse of `flacenc_hip_fill_le_bytes`: decoded rows (one block size per frame) to packed interleaved
+    /// little-endian PCM; `total[0]` = inter-channel samples, nothing written to `out` when they do not fit.
+    pub fn flacenc_hip_pack_le_bytes(
+        h: *mut Handle, frames: *const i32, stride: usize, block_sizes: *const u32, n_frames: usize, channels: u32,
+        bytes_per_sample: u32, out: *mut u8, out_capacity: u64, sample_offsets: *mut u64, total: *mut u64,
+        memory_kind: c_int,
+    ) -> c_int;
+    /// The mirror of `flacenc_hip_encode_pcm`: frame bytes in host memory to packed PCM in host memory;
+    /// `totals` = frames, samples, bytes consumed, stop reason (0, `DECODE_NO_ROOM`, `DECODE_CHAIN` or `DECODE_*` bits).
+    pub fn flacenc_hip_decode_pcm(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, channels: u32, bits_per_sample: u32, max_block_size: u32,
+        bytes_per_sample: u32, out: *mut u8, out_capacity: u64, totals: *mut u64,
+    ) -> c_int;
     /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
     /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
     /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.
@@ -465,6 +478,9 @@ pub const DECODE_LENGTH: u32 = 16;
 pub const DECODE_STREAM_MISMATCH: u32 = 32;
 pub const DECODE_UNSUPPORTED: u32 = 64;
 pub const DECODE_MISMATCH: u32 = 128;
+/// `totals[3]` of `flacenc_hip_decode_pcm`: the next frame's samples do not fit / no verified frame starts there.
+pub const DECODE_NO_ROOM: u32 = 256;
+pub const DECODE_CHAIN: u32 = 512;
 /// Set in `n_frames` by `flacenc_hip_index_frames_async` when the chain of frames does not end at `n_bytes`.
 pub const INDEX_ERROR: u64 = 1 << 63;
 
@@ -539,6 +555,40 @@ impl Gpu {
                 Ok(inter)
             })
             .collect())
+    }
+}
+
+/// What `Gpu::decode_pcm` gives back: how far the call got and why it stopped (`flacenc_hip_decode_pcm`'s `totals`).
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub struct DecodedPcm {
+    pub frames: u64,
+    pub samples: u64,
+    /// bytes of input consumed: the start of the frame the call stopped at, or `bytes.len()`
+    pub consumed: u64,
+    /// 0: the chain ended at the end of the input; `DECODE_NO_ROOM`, `DECODE_CHAIN`, or a frame's `DECODE_*` bits
+    pub stop: u32,
+}
+
+impl Gpu {
+    /// Decodes the chain of frames that starts at `bytes[0]` into `out` as packed interleaved little-endian PCM of
+    /// `ceil(bits_per_sample / 8)` bytes per sample -- the bytes the STREAMINFO MD5 is defined over
+    /// (`src/source.rs:406-428`) -- with `flacenc_hip_decode_pcm`.  `out[..samples * channels * width]` is written,
+    /// nothing behind it; after `DECODE_NO_ROOM` a second call on `&bytes[consumed..]` continues the stream.
+    pub fn decode_pcm(
+        &mut self, bytes: &[u8], channels: usize, bits_per_sample: usize, max_block_size: usize, out: &mut [u8],
+    ) -> Result<DecodedPcm, EncodeError> {
+        let width = (bits_per_sample as u32 + 7) / 8;
+        let mut totals = [0u64; 4];
+        let rc = unsafe {
+            flacenc_hip_decode_pcm(
+                self.0, bytes.as_ptr(), bytes.len() as u64, channels as u32, bits_per_sample as u32,
+                max_block_size as u32, width, out.as_mut_ptr(), out.len() as u64, totals.as_mut_ptr(),
+            )
+        };
+        if rc != OK {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_decode_pcm failed")));
+        }
+        Ok(DecodedPcm { frames: totals[0], samples: totals[1], consumed: totals[2], stop: totals[3] as u32 })
     }
 }
 

@@ -1,9 +1,9 @@
 """The counterpart of `flacenc decode`: .flac -> .wav with the frames indexed and decoded on the GPU.
 
 The host reads the metadata blocks (it takes the stream's parameters and MD5 from STREAMINFO and skips every other
-block), flacenc_hip_index_frames_async finds the frames, flacenc_hip_decode_frames decodes them, and the host
-interleaves the samples, checks the MD5 against STREAMINFO (an all-zero digest means "not checked") and writes the
-WAV (8 / 16 / 24-bit PCM).
+block); flacenc_hip_decode_pcm finds the frames, decodes them and returns the samples as packed interleaved
+little-endian PCM -- the byte string the STREAMINFO MD5 is defined over.  The host checks that MD5 (an all-zero digest
+means "not checked") and writes the WAV (8 / 16 / 24-bit PCM).
 
     python tools/decode_flac.py in.flac out.wav
 """
@@ -43,28 +43,25 @@ def read_metadata(data: bytes):
     return info, pos
 
 
+STOP_NAMES = {_capi.DECODE_NO_ROOM: "the output has no room", _capi.DECODE_CHAIN: "no verified frame starts here"}
+
+
 def decode(data: bytes, handle):
-    """-> (interleaved int32 samples [total, channels], STREAMINFO)."""
+    """-> (packed interleaved little-endian PCM, ceil(bits / 8) bytes per sample, as a uint8 array; STREAMINFO)."""
     info, start = read_metadata(data)
-    frames = data[start:]
+    frames = np.frombuffer(data, np.uint8)[start:]
     ch, bps = info["channels"], info["bits_per_sample"]
-    max_frames = len(frames) // 9 + 1  # a frame is at least 9 bytes
-    offsets, lengths, ok = handle.index_frames(frames, ch, bps, max_frames)
-    if not ok:
-        raise ValueError("the frames do not chain from the first to the end of the file")
-    out, bs, _, st = handle.decode_frames(frames, offsets, lengths, ch, bps, info["max_block_size"])
-    if st.any():
-        f = int(np.flatnonzero(st)[0])
-        raise ValueError(f"frame {f} at byte {start + int(offsets[f])}: decode status {int(st[f]):#x}")
-    pcm = np.concatenate([out[f, :, :bs[f]].T for f in range(len(bs))]) if len(bs) else np.zeros((0, ch), np.int32)
+    width = (bps + 7) // 8
+    if info["total_samples"]:
+        room = info["total_samples"] * ch * width
+    else:   # an unknown length: a frame is at least 9 bytes
+        room = (len(frames) // 9 + 1) * info["max_block_size"] * ch * width
+    out = np.empty(max(1, room), np.uint8)
+    pcm, totals = handle.decode_pcm(frames, ch, bps, info["max_block_size"], out=out, out_capacity=room)
+    if totals[3]:
+        why = STOP_NAMES.get(totals[3], f"decode status {totals[3]:#x}")
+        raise ValueError(f"frame {totals[0]} at byte {start + totals[2]}: {why}")
     return pcm, info
-
-
-def md5_of(pcm, bps):
-    """Interleaved little-endian samples of ceil(bps / 8) bytes (src/source.rs:406-428 of the reference)."""
-    nbytes = (bps + 7) // 8
-    raw = np.ascontiguousarray(pcm, "<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :nbytes]
-    return hashlib.md5(raw.tobytes()).digest()
 
 
 def main():
@@ -76,26 +73,34 @@ def main():
     with _capi.Handle(0) as h:
         pcm, info = decode(data, h)
     bps = info["bits_per_sample"]
-    if info["total_samples"] and pcm.shape[0] != info["total_samples"]:
-        raise SystemExit(f"decoded {pcm.shape[0]} samples, STREAMINFO says {info['total_samples']}")
+    width = (bps + 7) // 8
+    samples = pcm.size // (info["channels"] * width)
+    if info["total_samples"] and samples != info["total_samples"]:
+        raise SystemExit(f"decoded {samples} samples, STREAMINFO says {info['total_samples']}")
     if info["md5"] == bytes(16):
         status = "MD5 not checked (STREAMINFO has none)"
-    elif md5_of(pcm, bps) == info["md5"]:
+    elif hashlib.md5(pcm).digest() == info["md5"]:   # the bytes the call returns are the ones the MD5 is defined over
         status = "MD5 OK"
     else:
         raise SystemExit("MD5 mismatch")
-    width = (bps + 7) // 8
-    shifted = pcm.astype(np.int64) << (8 * width - bps)
-    if width == 1:
-        raw = (shifted + 128).astype(np.uint8).tobytes()
+    if 8 * width == bps and width > 1:
+        raw = pcm.tobytes()   # 16 / 24 bits: the WAV payload as it stands
     else:
-        raw = np.ascontiguousarray(shifted, "<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :width].tobytes()
+        # a depth that does not fill its bytes sits in the high bits of the WAV sample; 8-bit WAV is offset binary
+        wide = np.zeros((pcm.size // width, 4), np.uint8)
+        wide[:, :width] = pcm.reshape(-1, width)
+        v = (wide.view("<i4").reshape(-1) << (32 - 8 * width)) >> (32 - 8 * width)   # sign-extend
+        shifted = v.astype(np.int64) << (8 * width - bps)
+        if width == 1:
+            raw = (shifted + 128).astype(np.uint8).tobytes()
+        else:
+            raw = np.ascontiguousarray(shifted, "<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :width].tobytes()
     with wave.open(args.output, "wb") as w:
         w.setnchannels(info["channels"])
         w.setsampwidth(width)
         w.setframerate(info["sample_rate"])
         w.writeframes(raw)
-    print(f"{pcm.shape[0]} samples x {info['channels']} channels, {bps} bits: {status}")
+    print(f"{samples} samples x {info['channels']} channels, {bps} bits: {status}")
 
 
 if __name__ == "__main__":

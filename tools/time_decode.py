@@ -7,7 +7,15 @@ with events (median of --reps after --warmup):
   verify   flacenc_hip_verify_frames_async of the same frames against the encoder's input
   index    flacenc_hip_index_frames_async on the frames placed back to back (flacenc_hip_place_frames_async)
   encode   the encode + pack launch the frames came from, for scale
-HBM traffic counts the compressed bytes read plus 4 bytes per sample written (decode) or read (verify), against 8 TB/s.
+  pack     flacenc_hip_pack_le_bytes on device pointers: the decoded rows -> packed interleaved 16-bit PCM (the call runs
+           on the handle's stream and returns when it is done: host wall clock, not events)
+HBM traffic counts the compressed bytes read plus 4 bytes per sample written (decode) or read (verify), against 8 TB/s;
+for pack, 4 bytes per sample read plus 2 written.
+The host boundary, wall clock and best of 3 on the first --host-frames frames (bench.py's streaming workload: 24 576),
+frame bytes in host memory to interleaved PCM in host memory:
+  decode_pcm pinned / pageable   flacenc_hip_decode_pcm with both buffers page-locked / both ordinary memory
+  pieces                         what tools/decode_flac.py did before that call existed: upload + index, decode_frames to
+                                 int32 host rows, numpy interleave per frame
 The CPU baseline runs flac_decode_cpu.cpp (the same flac_decode_core.h, g++ -O2) on --threads host threads.
 Writes profiles/decode_rates.json.
 
@@ -28,6 +36,55 @@ from flacenc_rs_amd import _capi, decode_cpu  # noqa: E402
 HBM_BYTES_PER_S = 8.0e12
 
 
+def best_of(fn, reps=3):
+    best = None
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        dt = time.perf_counter() - t0
+        best = dt if best is None or dt < best else best
+    return best
+
+
+def host_boundary(h, args, x, stream_buf, starts, lens, n, bps):
+    """Frame bytes in host memory -> interleaved PCM in host memory: flacenc_hip_decode_pcm, and the pieces without it."""
+    import torch
+    hf = min(args.host_frames, len(lens))
+    n_bytes = int(starts[hf - 1]) + int(lens[hf - 1])
+    pcm_bytes = hf * n * 2 * 2
+    want = x[:hf].transpose(1, 2).contiguous().to(torch.int16).cpu().numpy().view(np.uint8).reshape(-1)
+    src_pin, out_pin = _capi.pinned_array(n_bytes), _capi.pinned_array(pcm_bytes)
+    src_pin[:] = stream_buf[:n_bytes].cpu().numpy()
+    src_page, out_page = np.array(src_pin, copy=True), np.zeros(pcm_bytes, np.uint8)
+    rows = {}
+    for name, src, out in (("decode_pcm_pinned", src_pin, out_pin), ("decode_pcm_pageable", src_page, out_page)):
+        def call():
+            got, totals = h.decode_pcm(src, 2, bps, n, out=out)
+            assert totals == [hf, hf * n, n_bytes, 0], totals
+        call()   # warm: staging and scratch are allocated
+        dt = best_of(call)
+        assert np.array_equal(out, want)
+        rows[name] = {"s": round(dt, 4), "G_samples_per_s": round(hf * 2 * n / dt / 1e9, 3),
+                      "pcie_GB_per_s_in": round(n_bytes / dt / 1e9, 2), "pcie_GB_per_s_out": round(pcm_bytes / dt / 1e9, 2)}
+
+    got = {}
+
+    def pieces():
+        off, ln, ok = h.index_frames(src_page, 2, bps, n_bytes // 9 + 1)
+        assert ok
+        out, bs, _, st = h.decode_frames(src_page, off, ln, 2, bps, n)
+        assert not st.any()
+        got["pcm"] = np.concatenate([out[f, :, :bs[f]].T for f in range(len(bs))])
+    pieces()
+    dt = best_of(pieces)
+    assert np.array_equal(np.ascontiguousarray(got["pcm"].astype("<i2")).view(np.uint8).reshape(-1), want)
+    rows["pieces"] = {"s": round(dt, 4), "G_samples_per_s": round(hf * 2 * n / dt / 1e9, 3),
+                      "what": "index_frames + decode_frames to int32 host rows + numpy interleave per frame (the tool "
+                              "before flacenc_hip_decode_pcm); its samples are still int32"}
+    rows.update(frames=hf, compressed_bytes=n_bytes, pcm_bytes=pcm_bytes, timing="wall clock, best of 3 after one warm call")
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=98304)
@@ -37,6 +94,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--cpu-frames", type=int, default=8192, help="frames the CPU baseline decodes")
+    ap.add_argument("--host-frames", type=int, default=24576, help="frames of the host-boundary rows")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_rates.json"))
     args = ap.parse_args()
     import torch
@@ -89,25 +147,39 @@ def main():
         h.index_frames_device(stream_buf.data_ptr(), total, 2, bps, F + 8, ioff.data_ptr(), ilen.data_ptr(),
                               inf.data_ptr(), stream=s)
 
-    def timed(fn):
+    def timed(fn, blocking=False):
         for _ in range(args.warmup):
             fn()
         ms = []
-        for _ in range(args.reps):
+        for _ in range(args.reps if not blocking else 0):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             fn()
             b.record()
             b.synchronize()
             ms.append(a.elapsed_time(b))
+        for _ in range(args.reps if blocking else 0):   # the call synchronises its own stream: the host's clock
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ms.append((time.perf_counter() - t0) * 1e3)
         return float(np.median(ms)), [round(v, 4) for v in ms]
 
     samples = F * 2 * n
     res = {"workload": f"bench.py's: {F} stereo frames x {n} samples, 16-bit sigen Sine(200,0.4)+Noise(0.4), "
                        f"LPC order {args.lpc_order}, encode_pack_stereo_frames_async output",
            "compressed_bytes": total, "samples": samples}
-    for name, fn in (("encode", encode), ("decode", decode), ("verify", verify), ("index", index)):
-        med, all_ms = timed(fn)
+    pcm = torch.empty(samples * 2, dtype=torch.uint8, device=dev)
+    ptotal = torch.zeros(1, dtype=torch.int64, device=dev)
+    decode()   # rows and block sizes for pack
+    torch.cuda.synchronize()
+
+    def pack():
+        h.pack_le_bytes_device(out.data_ptr(), n, bs.data_ptr(), F, 2, 2, pcm.data_ptr(), samples * 2, None,
+                               ptotal.data_ptr())
+
+    for name, fn in (("encode", encode), ("decode", decode), ("verify", verify), ("index", index), ("pack", pack)):
+        med, all_ms = timed(fn, blocking=name == "pack")
         entry = {"ms_median": round(med, 4), "ms": all_ms, "G_samples_per_s": round(samples / med / 1e6, 2)}
         if name in ("decode", "verify"):
             traffic = total + 4 * samples
@@ -116,6 +188,11 @@ def main():
         elif name == "index":
             entry["hbm_bytes"] = total
             entry["hbm_frac"] = round(total / (med * 1e-3) / HBM_BYTES_PER_S, 4)
+        elif name == "pack":
+            traffic = 6 * samples
+            entry["hbm_bytes"] = traffic
+            entry["hbm_GB_per_s"] = round(traffic / (med * 1e-3) / 1e9, 1)
+            entry["hbm_frac"] = round(traffic / (med * 1e-3) / HBM_BYTES_PER_S, 4)
         res[name] = entry
     torch.cuda.synchronize()
     # correctness of what was timed
@@ -128,7 +205,13 @@ def main():
     index()
     torch.cuda.synchronize()
     assert int(inf.item()) == F and torch.equal(ioff[:F], soff)
-    res["checked"] = "decode == input, verify all zero, index == place_frames offsets"
+    pack()
+    torch.cuda.synchronize()
+    want_pcm = x.transpose(1, 2).contiguous().to(torch.int16).view(torch.uint8).reshape(-1)   # [F, n, 2] int16
+    assert int(ptotal.item()) == F * n and torch.equal(pcm, want_pcm)
+    del want_pcm
+    res["checked"] = "decode == input, verify all zero, index == place_frames offsets, pack == interleaved int16 input"
+    res["host_boundary"] = host_boundary(h, args, x, stream_buf, starts, lens, n, bps)
     # CPU baseline: the same core on host threads
     cf = min(args.cpu_frames, F)
     host_bytes = packed[:cf].cpu().numpy().reshape(-1)
