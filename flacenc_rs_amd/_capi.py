@@ -77,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_window_weights",
     "flacenc_hip_set_lpc_windows",
     "flacenc_hip_set_order_guesses",
+    "flacenc_hip_set_precision_floor",
     "flacenc_hip_lpc_window_weights",
     "flacenc_hip_qlpc_batch",
     "flacenc_hip_qlpc_batch_async",
@@ -284,6 +285,8 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_set_lpc_windows.restype = C.c_int
     L.flacenc_hip_set_order_guesses.argtypes = [vp, C.c_uint32]
     L.flacenc_hip_set_order_guesses.restype = C.c_int
+    L.flacenc_hip_set_precision_floor.argtypes = [vp, C.c_uint32]
+    L.flacenc_hip_set_precision_floor.restype = C.c_int
     L.flacenc_hip_lpc_window_weights.argtypes = [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.flacenc_hip_lpc_window_weights.restype = C.c_int
     L.flacenc_hip_synchronize.argtypes = [vp]
@@ -452,6 +455,8 @@ FLAG_WASTED_BITS = 512  # frame-level calls code subframes whose low bits are al
 FLAG_ORDER_SEARCH = 1024  # every LPC candidate's order chosen by an exhaustive search over 1..lpc_order
 FLAG_WINDOW_SEARCH = 2048  # every LPC candidate analysed under the config's window and the handle's extra windows
 FLAG_ORDER_GUESS = 4096  # the LPC order guessed from the Levinson error: (0, P) and K guesses per window are coded
+FLAG_PRECISION_SEARCH = 8192  # every LPC candidate coded at each precision quant_precision .. the handle's floor
+DEFAULT_PRECISION_FLOOR = 5  # a fresh handle's floor (flacenc_hip_set_precision_floor)
 
 
 def wasted_bits(results) -> np.ndarray:
@@ -592,6 +597,11 @@ class Handle:
         """flacenc_hip_set_order_guesses: K of FLAG_ORDER_GUESS, the guessed orders coded per window, 1..32 (a fresh
         handle holds 1); applies to the calls made after it."""
         self._check(self._lib.flacenc_hip_set_order_guesses(self._h, int(k)))
+
+    def set_precision_floor(self, floor: int):
+        """flacenc_hip_set_precision_floor: F of FLAG_PRECISION_SEARCH, the lowest coefficient precision searched,
+        1..15 (a fresh handle holds 5); applies to the calls made after it."""
+        self._check(self._lib.flacenc_hip_set_precision_floor(self._h, int(floor)))
 
     def _hook(self, name):
         if not hasattr(self._lib, name):

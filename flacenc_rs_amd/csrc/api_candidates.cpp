@@ -40,12 +40,17 @@ __global__ void bitcount_pick_kernel(const unsigned long long* keys, uint32_t n,
 namespace flacenc_hip {
 
 // FLACENC_HIP_FLAG_WINDOW_SEARCH with no extra window is exactly the call with the summation-order flag in its place
-// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call; with FLACENC_HIP_FLAG_ORDER_GUESS: the ORDER_GUESS call).
+// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call; with FLACENC_HIP_FLAG_ORDER_GUESS: the ORDER_GUESS call),
+// and so is FLACENC_HIP_FLAG_PRECISION_SEARCH with the handle's floor at or above the config's quant_precision.
 // Callers of the flagged entry points run their config through this once, after flacenc_hip_verify_config.
-uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags) {
-  if (!(flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) || !h->lpc_windows.empty()) return flags;
-  flags &= ~FLACENC_HIP_FLAG_WINDOW_SEARCH;
-  if (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS)) return flags;
+uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags, uint32_t quant_precision) {
+  const uint32_t dropped =
+      (((flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) && h->lpc_windows.empty()) ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u) |
+      (((flags & FLACENC_HIP_FLAG_PRECISION_SEARCH) && h->precision_floor >= quant_precision)
+           ? FLACENC_HIP_FLAG_PRECISION_SEARCH : 0u);
+  if (!dropped) return flags;
+  flags &= ~dropped;
+  if (lpc_search(flags)) return flags;
   flags &= ~(FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY);
   if (!(flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER)) flags |= FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER;
   return flags;
@@ -54,7 +59,8 @@ uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags) {
 // The LPC candidate of a (normalised) config comes from the search over windows and orders (order_search.h): the frame
 // -level calls then take the candidate batches and the stand-alone deciding kernels for every shape.
 bool lpc_search(uint32_t flags) {
-  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS)) != 0;
+  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS |
+                   FLACENC_HIP_FLAG_PRECISION_SEARCH)) != 0;
 }
 
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
@@ -315,7 +321,7 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
             uint32_t residual_mode) {
   if (placed) *placed = false;
   flacenc_hip_qlpc_config qcfg = *cfg;
-  qcfg.flags = search_flags(h, cfg->flags);
+  qcfg.flags = search_flags(h, cfg->flags, cfg->quant_precision);
   cfg = &qcfg;
   const WindowEntry* win = nullptr;
   int rc = get_window(h, cfg, block_size, &win);
@@ -366,10 +372,12 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
     a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
   }
   if (order_search) {
-    // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS: R[] of every window in
-    // the stable build's order (nightly's with its flag; the certificate and INTEGER_PARITY_ONLY do not apply), every
-    // candidate (window, order) searched -- under ORDER_GUESS (0, P) and every window's K guesses, K as the handle holds
-    // it now --, the records written by stage 3
+    // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH (DESIGN.md 4.10, 4.11, 4.13,
+    // 4.16): R[] of every window in the stable build's order (nightly's with its flag; the certificate and
+    // INTEGER_PARITY_ONLY do not apply), every candidate (window, order, precision) searched -- under ORDER_GUESS (0, P)
+    // and every window's K guesses, K as the handle holds it now; under PRECISION_SEARCH every precision from
+    // quant_precision down to the handle's floor as it is now (search_flags: below quant_precision) --, the records
+    // written by stage 3
     a.certify = 0;
     a.integer_parity_only = 0;
     a.cert_stats = nullptr;
@@ -379,6 +387,8 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
     shape.guess_orders = (cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) ? h->order_guesses : 0u;
     shape.search_orders = ((cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH) || shape.guess_orders) ? 1u : 0u;
     shape.guess_trace = shape.guess_orders ? h->order_guess_trace : nullptr;
+    shape.n_precisions =
+        (cfg->flags & FLACENC_HIP_FLAG_PRECISION_SEARCH) ? cfg->quant_precision - h->precision_floor + 1u : 1u;
     if (cfg->flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) {
       for (const LpcWindow& w : h->lpc_windows) {
         const WindowEntry* e = nullptr;

@@ -19,11 +19,12 @@ int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_frame_con
                               flacenc_hip_stereo_frame_result* results, int32_t* residual, size_t residual_stride,
                               void* stream, const PackTarget* pack, bool* packed);
 
-// The config a frame-level call runs with: the window search without windows normalised away (search_flags), and
+// The config a frame-level call runs with: the window search without windows and the precision search without a
+// precision below quant_precision normalised away (search_flags), and
 // too_short (coding.rs:396): neither fixed_lpc nor estimated_qlpc is tried; Constant or Verbatim
 flacenc_hip_frame_config frame_config(const flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, uint32_t block_size) {
   flacenc_hip_frame_config c = *cfg;
-  c.qlpc.flags = search_flags(h, cfg->qlpc.flags);
+  c.qlpc.flags = search_flags(h, cfg->qlpc.flags, cfg->qlpc.quant_precision);
   if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) c.use_fixed = c.use_lpc = 0;
   return c;
 }
@@ -169,7 +170,7 @@ int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
   if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
   // the unflagged configuration (FUSED_PACK: a kernel choice the fix-up's packer has no part in)
   flacenc_hip_frame_config plain = *cfg;
-  plain.qlpc.flags = search_flags(h, plain.qlpc.flags) & ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
+  plain.qlpc.flags = search_flags(h, plain.qlpc.flags, plain.qlpc.quant_precision) & ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = ensure(h, h->d_wk, n_frames * rows)) != FLACENC_HIP_OK) return rc;
@@ -390,8 +391,8 @@ int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_frame_con
   bool want_fused = false;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_FUSED_PACK) want_fused = true;
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_TWO_STAGE_PACK) want_fused = false;
-  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: the candidate batches + frame_decide_kernel for every shape
-  // (FUSED_PACK ignored)
+  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH: the candidate batches +
+  // frame_decide_kernel for every shape (FUSED_PACK ignored)
   const bool order_search = lpc_search(cfg->qlpc.flags) && cfg->use_lpc;
   if (pack && want_fused && !fixed_composite && !order_search && block_size == 4096 && wave_kernel_eligible(a)) {
     attach_fused_pack(a, pack, bits_per_sample);

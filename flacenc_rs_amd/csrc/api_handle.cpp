@@ -147,6 +147,8 @@ int flacenc_hip_verify_config(const flacenc_hip_qlpc_config* cfg) {
   // the guessed search is a subset of the exhaustive one: one of the two at a time
   if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) && (cfg->flags & FLACENC_HIP_FLAG_ORDER_SEARCH)) return FLACENC_HIP_ERR_BAD_CONFIG;
   if ((cfg->flags & FLACENC_HIP_FLAG_ORDER_GUESS) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
+  // the precision search requantises the recursion's coefficients: a third axis of the same search
+  if ((cfg->flags & FLACENC_HIP_FLAG_PRECISION_SEARCH) && cfg->use_direct_mse) return FLACENC_HIP_ERR_UNSUPPORTED;
   return FLACENC_HIP_OK;
 }
 
@@ -157,6 +159,16 @@ int flacenc_hip_set_order_guesses(flacenc_hip_handle* h, uint32_t k) {
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   h->order_guesses = k;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_set_precision_floor(flacenc_hip_handle* h, uint32_t floor) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (floor < 1 || floor > FLACENC_HIP_MAX_PRECISION) {
+    h->last_error = "flacenc_hip_set_precision_floor: floor must be in 1..=15";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->precision_floor = floor;
   return FLACENC_HIP_OK;
 }
 

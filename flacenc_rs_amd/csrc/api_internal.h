@@ -174,6 +174,8 @@ struct flacenc_hip_handle {
   // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
   flacenc_hip::DeviceBuffer d_order;
   uint32_t order_guesses = 1;  // FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window (flacenc_hip_set_order_guesses)
+  // FLACENC_HIP_FLAG_PRECISION_SEARCH: F, the lowest precision searched (flacenc_hip_set_precision_floor)
+  uint32_t precision_floor = 5;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into
@@ -246,7 +248,7 @@ int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t
 int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32_t n, const WindowEntry** out);
 
 // ---- api_candidates.cpp ----
-uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags);
+uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags, uint32_t quant_precision);
 bool lpc_search(uint32_t flags);
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
                      size_t n_subframes, uint32_t block_size, size_t stride, flacenc_hip_subframe_params* params,

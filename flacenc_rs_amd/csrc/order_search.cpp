@@ -5,6 +5,8 @@
 // unflagged FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER record.  ORDER_SEARCH alone is the W = 1 case.
 // FLACENC_HIP_FLAG_ORDER_GUESS (section 4.13) runs the same grid of predictors, then order_guess_kernel strikes every
 // candidate that is neither (0, P) nor one of its window's K guesses (order_guess_core.h) before the search codes the rest.
+// FLACENC_HIP_FLAG_PRECISION_SEARCH (section 4.16) is the third axis: every (j, o) is quantised at the Q precisions
+// q0, q0 - 1, .. q0 - Q + 1 from the one run of the recursion, and the key takes each record's own precision.
 #include "order_search.h"
 
 #include "acorr_reference.h"
@@ -19,7 +21,8 @@ constexpr int kOsThreads = 256;
 constexpr int kTabStride = 31;                    // Rice parameters 0..30 per partition row
 constexpr uint32_t kMaxBits = (1u << 27) - 1u;    // MAX_P_TO_BITS, rice.rs:51
 constexpr uint32_t kWideU = 1u << 27;             // zig-zag codes from here on can wrap a 16-sample chunk's u32 sum
-constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, 0 (levinson_batch_kernel's record)
+constexpr size_t kCandWords = 36;                 // qc[32], order, shift, status, precision (levinson_batch_kernel's
+                                                  // record, whose last word is 0: the launch's precision)
 constexpr int32_t kNotCandidate = 0x40000000;     // order_guess_kernel's status word of a candidate the search skips
 static_assert(sizeof(order_guess::Guess) == 264, "the trace record of flacenc_hip_debug_set_order_guess_trace");
 constexpr size_t kSmallBytes = 1024 + 16 * 8 + 2 * 8 + 16 * 4 + 256 + 256;  // psum, level bits, sums, misc, two ps rows
@@ -36,7 +39,6 @@ struct OrderSearchArgs {
   uint32_t bps_uniform;
   uint32_t lpc_order;
   uint32_t n_cand;      // C candidates per subframe
-  uint32_t precision;
   uint32_t max_rice_parameter;
   uint32_t rice_finest_only;
   const int32_t* cand;  // [n][C][36]
@@ -68,38 +70,89 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
   return v;
 }
 
-// Candidate c = j * Pc + (o - 1 - (P - Pc)) of a subframe: window j, order o (Pc = P orders per window with the order
-// search, else 1: order P only).  R_j of subframe sf at racc[(sf * W + j) * 33].
-__device__ __forceinline__ void candidate_of(uint32_t c, uint32_t P, uint32_t Pc, uint32_t* j, int* o) {
-  *j = c / Pc;
-  *o = (int)(P - Pc + 1u + c % Pc);
+// Candidate c = (j * Pc + (o - 1 - (P - Pc))) * Q + i of a subframe: window j, order o (Pc = P orders per window with the
+// order search, else 1: order P only), precision q0 - i (Q = 1 without the precision search).  R_j of subframe sf at
+// racc[(sf * W + j) * 33].
+__device__ __forceinline__ void candidate_of(uint32_t c, uint32_t P, uint32_t Pc, uint32_t Q, uint32_t* j, int* o,
+                                             uint32_t* i) {
+  const uint32_t g = c / Q;
+  *i = c % Q;
+  *j = g / Pc;
+  *o = (int)(P - Pc + 1u + g % Pc);
 }
 
-// candidate c of subframe sf at [(sf * C + c) * 36]: levinson_quantize on R_j[0..o] (lpc.rs:633-705, 273-302)
-// REFL (the order guess): k_o, the candidate's unquantised coefficient number o - 1, at refl[sf * C + c] as well
-template <int MAXP, bool REFL>
-__global__ void __launch_bounds__(64) order_levinson_kernel(const double* __restrict__ racc, uint32_t n_subframes,
-                                                             uint32_t W, uint32_t P, uint32_t Pc, uint32_t precision,
-                                                             int32_t* __restrict__ cand, double* __restrict__ refl) {
-  const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
-  const uint32_t C = W * Pc;
-  if (i >= (size_t)n_subframes * C) return;
-  const size_t sf = i / C;
-  uint32_t j;
-  int o;
-  candidate_of((uint32_t)(i % C), P, Pc, &j, &o);
-  double coef[MAXP];
-  int32_t qc[MAXP];
-  int order, shift;
-  const int status = levinson_quantize<MAXP>(racc + (sf * W + j) * 33, o, (int)precision, coef, qc, &order, &shift);
-  int32_t* pr = cand + i * kCandWords;
+// quantize_parameters (lpc.rs:273-302: find_shift :234-254, quantize_parameter :258-270, the tail-zero truncation) of the
+// coefficients a[0..P) of a levinson_quantize run with status 0, at another precision: operation for operation
+// levinson_quantize's own quantiser, which stays as it is (the fused kernel's schedule hangs on that function's shape).
+template <int MAXP>
+__device__ void quantize_at(const double (&a)[MAXP], int P, int precision, int32_t* qc_out, int* order_out,
+                            int* shift_out) {
+  double max_abs = 0.0;
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i)
+    if (i < P) max_abs = fmax(max_abs, fabs(a[i]));
+  int abs_log2 = ceil_log2_pos(max_abs);
+  if (abs_log2 < -32752) abs_log2 = -32752;
+  int shift = (precision - 1) - abs_log2;
+  shift = shift < 0 ? 0 : (shift > 15 ? 15 : shift);
+  const double scalefac = (double)(1 << shift);
+  const int lo = -(1 << (precision - 1)), hi = (1 << (precision - 1)) - 1;
+  int order = 1;
+#pragma unroll
+  for (int i = 0; i < MAXP; ++i) {
+    int q = 0;
+    if (i < P) {
+      double s = round(a[i] * scalefac);  // half away from zero
+      s = s < -32768.0 ? -32768.0 : (s > 32767.0 ? 32767.0 : s);
+      q = (int)s;
+      q = q < lo ? lo : (q > hi ? hi : q);
+      if (q != 0) order = i + 1;  // tail-zero truncation, min 1 (lpc.rs:295-299)
+    }
+    qc_out[i] = q;
+  }
+  *order_out = order;
+  *shift_out = shift;
+}
+
+// a predictor record: qc[32], order, shift, status, precision
+template <int MAXP>
+__device__ __forceinline__ void write_pred(int32_t* pr, const int32_t* qc, int order, int shift, int status,
+                                           uint32_t precision) {
 #pragma unroll
   for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
   for (int k = MAXP; k < 32; ++k) pr[k] = 0;
   pr[32] = order;
   pr[33] = shift;
   pr[34] = status;
-  pr[35] = 0;
+  pr[35] = (int32_t)precision;
+}
+
+// One lane per (subframe, window, order): the Q candidates (j, o, 0..Q-1) of subframe sf from [(sf * C + c) * 36] on:
+// levinson_quantize on R_j[0..o] (lpc.rs:633-705, 273-302) at q0, then the same coefficients quantised at q0 - 1, ..
+// (a status other than 0 is every precision's)
+// REFL (the order guess): k_o, the candidate's unquantised coefficient number o - 1, at refl[sf * W * Pc + j * Pc + oi] as well
+template <int MAXP, bool REFL>
+__global__ void __launch_bounds__(64) order_levinson_kernel(const double* __restrict__ racc, uint32_t n_subframes,
+                                                             uint32_t W, uint32_t P, uint32_t Pc, uint32_t Q,
+                                                             uint32_t precision, int32_t* __restrict__ cand,
+                                                             double* __restrict__ refl) {
+  const size_t i = (size_t)blockIdx.x * 64u + threadIdx.x;
+  const uint32_t G = W * Pc;
+  if (i >= (size_t)n_subframes * G) return;
+  const size_t sf = i / G;
+  uint32_t j, i0;
+  int o;
+  candidate_of((uint32_t)(i % G) * Q, P, Pc, Q, &j, &o, &i0);
+  double coef[MAXP];
+  int32_t qc[MAXP];
+  int order, shift;
+  const int status = levinson_quantize<MAXP>(racc + (sf * W + j) * 33, o, (int)precision, coef, qc, &order, &shift);
+  int32_t* pr = cand + i * Q * kCandWords;
+  write_pred<MAXP>(pr, qc, order, shift, status, precision);
+  for (uint32_t x = 1; x < Q; ++x) {
+    if (status == 0) quantize_at<MAXP>(coef, o, (int)(precision - x), qc, &order, &shift);
+    write_pred<MAXP>(pr + x * kCandWords, qc, order, shift, status, precision - x);
+  }
   if (REFL) {
     double k = 0.0;
 #pragma unroll
@@ -117,7 +170,7 @@ struct DevLog2f {
 // order_search_kernel skips a record whose status is not 0, and order_pick_kernel runs the chosen (j, o) again.
 __global__ void __launch_bounds__(64) order_guess_kernel(const double* __restrict__ racc, const double* __restrict__ refl,
                                                           int32_t* __restrict__ cand, uint32_t n_subframes, uint32_t W,
-                                                          uint32_t P, uint32_t precision, uint32_t block_size,
+                                                          uint32_t P, uint32_t Q, uint32_t precision, uint32_t block_size,
                                                           const uint8_t* __restrict__ bps, uint32_t bps_uniform,
                                                           uint32_t stereo, uint32_t K,
                                                           order_guess::Guess* __restrict__ trace) {
@@ -126,14 +179,15 @@ __global__ void __launch_bounds__(64) order_guess_kernel(const double* __restric
   const size_t sf = i / W;
   const uint32_t j = (uint32_t)(i % W);
   const uint32_t w = bps ? (uint32_t)bps[sf] : bps_uniform + ((stereo && (sf & 3u) == 3u) ? 1u : 0u);
-  const size_t c0 = i * P;  // candidate (j, 1) of the subframe: sf * W * P + j * P
-  int32_t* st = cand + c0 * kCandWords + 34;
+  const size_t c0 = i * P;  // (j, 1) of the subframe: sf * W * P + j * P; its Q records from c0 * Q on
+  int32_t* st = cand + c0 * Q * kCandWords + 34;  // the status words of the records at q0, Q records apart
   order_guess::Guess g;
-  order_guess::guess_orders(racc[i * 33], refl + c0, 1u, st, (uint32_t)kCandWords, P, block_size, w, precision, K,
+  order_guess::guess_orders(racc[i * 33], refl + c0, 1u, st, (uint32_t)(Q * kCandWords), P, block_size, w, precision, K,
                             DevLog2f(), &g);
   for (uint32_t o = 1; o <= P; ++o) {
     const bool keep = ((g.mask >> (o - 1)) & 1u) != 0u || (j == 0u && o == P);
-    if (!keep) st[(size_t)(o - 1) * kCandWords] = kNotCandidate;
+    if (!keep)
+      for (uint32_t x = 0; x < Q; ++x) st[((size_t)(o - 1) * Q + x) * kCandWords] = kNotCandidate;
   }
   if (trace) {  // test hook (flacenc_hip_debug.h): the lane's record, +0.0 above `eligible`; `trace` is lane 0's
     order_guess::Guess* t = trace + i;
@@ -143,34 +197,28 @@ __global__ void __launch_bounds__(64) order_guess_kernel(const double* __restric
   }
 }
 
-// the chosen candidate's predictor record for the stage-3 kernels, its unquantised coefficients (zeros from o on) and
-// its window's R[0..P] (zeros above P)
+// the chosen candidate's predictor record for the stage-3 kernels (its precision in word 35 with the precision search,
+// else 0: the launch's), its unquantised coefficients (zeros from o on) and its window's R[0..P] (zeros above P)
 template <int MAXP>
 __global__ void __launch_bounds__(64) order_pick_kernel(const double* __restrict__ racc, uint32_t n_subframes, uint32_t W,
-                                                         uint32_t P, uint32_t Pc, uint32_t precision,
+                                                         uint32_t P, uint32_t Pc, uint32_t Q, uint32_t precision,
                                                          const uint32_t* __restrict__ best, int32_t* __restrict__ pred,
                                                          double* __restrict__ lpc_coefs, double* __restrict__ autocorr) {
   const size_t sf = (size_t)blockIdx.x * 64u + threadIdx.x;
   if (sf >= n_subframes) return;
   const uint32_t b = best[sf];
-  // no candidate with status 0: candidate (0, P), status included
-  const uint32_t c = (b >= 1u && b <= W * Pc) ? b - 1u : Pc - 1u;
-  uint32_t j;
+  // no candidate with status 0: candidate (0, P, q0), status included
+  const uint32_t c = (b >= 1u && b <= W * Pc * Q) ? b - 1u : (Pc - 1u) * Q;
+  uint32_t j, x;
   int o;
-  candidate_of(c, P, Pc, &j, &o);
+  candidate_of(c, P, Pc, Q, &j, &o, &x);
   const double* rj = racc + (sf * W + j) * 33;
   double coef[MAXP];
   int32_t qc[MAXP];
   int order, shift;
   const int status = levinson_quantize<MAXP>(rj, o, (int)precision, coef, qc, &order, &shift);
-  int32_t* pr = pred + sf * kCandWords;
-#pragma unroll
-  for (int k = 0; k < MAXP; ++k) pr[k] = qc[k];
-  for (int k = MAXP; k < 32; ++k) pr[k] = 0;
-  pr[32] = order;
-  pr[33] = shift;
-  pr[34] = status;
-  pr[35] = 0;
+  if (x != 0u && status == 0) quantize_at<MAXP>(coef, o, (int)(precision - x), qc, &order, &shift);
+  write_pred<MAXP>(pred + sf * kCandWords, qc, order, shift, status, Q > 1u ? precision - x : 0u);
   if (lpc_coefs) {
 #pragma unroll
     for (int k = 0; k < MAXP; ++k) lpc_coefs[sf * 32 + k] = (k < o && status == 0) ? coef[k] : 0.0;
@@ -268,6 +316,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
     if (pr[34] != 0) continue;  // (uniform: every thread reads the same record)
     const int q = pr[32];
     const int shift = pr[33];
+    const unsigned long long prec = (unsigned long long)(uint32_t)pr[35];  // (order_levinson_kernel: never 0)
     int32_t c[32];
     int64_t sumabs = 0;
 #pragma unroll
@@ -436,7 +485,7 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
     if (!wide && !best_clamp) {
       // no entry of the chosen level saturates or wraps: code_bits is the exact sum, and the residual's bits are
       // 2 + 4 + nb * (4 or 5) + quotients + remainders = 6 + code_bits (+ nb with the 5-bit parameters)
-      key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + 6ull + best_bits + (best_r2 ? (unsigned long long)nb : 0ull);
+      key = 8ull + bps * wq + 4ull + 5ull + prec * wq + 6ull + best_bits + (best_r2 ? (unsigned long long)nb : 0ull);
     } else {
       __syncthreads();  // (psel complete)
       const int pb = psize << best_lvl;
@@ -450,9 +499,9 @@ __global__ void __launch_bounds__(kOsThreads) order_search_kernel(OrderSearchArg
       for (int i = 0; i < nb; ++i) sum_p += psel[i];
       const unsigned long long rbits = 6ull + (unsigned long long)nb * (best_r2 ? 5ull : 4ull) + sum_q +
                                        (unsigned long long)(n - q) + (sum_p * (unsigned long long)pb - wq * psel[0]);
-      key = 8ull + bps * wq + 4ull + 5ull + (unsigned long long)a.precision * wq + rbits;
+      key = 8ull + bps * wq + 4ull + 5ull + prec * wq + rbits;
     }
-    if (key < best_key) {  // strict: the lower candidate -- window, then order -- wins a tie
+    if (key < best_key) {  // strict: the lower candidate -- window, then order, then the higher precision -- wins a tie
       best_key = key;
       best_c = (uint32_t)cand + 1u;
     }
@@ -471,7 +520,7 @@ struct SliceArgs {
   double* lpc_coefs;
   double* autocorr;
   uint32_t n_subframes;
-  uint32_t W, P, Pc, precision;
+  uint32_t W, P, Pc, Q, precision;
 };
 
 template <int MAXP>
@@ -480,13 +529,13 @@ hipError_t launch_levinson_and_pick(bool pick, const SliceArgs& s, hipStream_t s
     const size_t items = (size_t)s.n_subframes * s.W * s.Pc;
     if (s.refl)
       hipLaunchKernelGGL((order_levinson_kernel<MAXP, true>), dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream,
-                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand, s.refl);
+                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.Q, s.precision, s.cand, s.refl);
     else
       hipLaunchKernelGGL((order_levinson_kernel<MAXP, false>), dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream,
-                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.precision, s.cand, s.refl);
+                         s.racc, s.n_subframes, s.W, s.P, s.Pc, s.Q, s.precision, s.cand, s.refl);
   } else {
     hipLaunchKernelGGL(order_pick_kernel<MAXP>, dim3((s.n_subframes + 63) / 64), dim3(64), 0, stream, s.racc, s.n_subframes,
-                       s.W, s.P, s.Pc, s.precision, s.best, s.pred, s.lpc_coefs, s.autocorr);
+                       s.W, s.P, s.Pc, s.Q, s.precision, s.best, s.pred, s.lpc_coefs, s.autocorr);
   }
   return hipGetLastError();
 }
@@ -501,8 +550,8 @@ hipError_t levinson_bucket(bool pick, const SliceArgs& s, hipStream_t stream) {
 }
 
 size_t bytes_per_subframe(uint32_t lpc_order, const SearchShape& shape) {
-  const size_t W = shape.n_windows, C = W * (shape.search_orders ? lpc_order : 1u);
-  return W * 33 * sizeof(double) + (shape.guess_orders ? C * sizeof(double) : 0) + C * kCandWords * 4 + 4;
+  const size_t W = shape.n_windows, G = W * (shape.search_orders ? lpc_order : 1u), C = G * shape.n_precisions;
+  return W * 33 * sizeof(double) + (shape.guess_orders ? G * sizeof(double) : 0) + C * kCandWords * 4 + 4;
 }
 
 // subframes per slice: as many as kSearchScratchCap holds, whole stereo frames (a multiple of 4), at least 4
@@ -523,17 +572,18 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
   if (a.n_subframes == 0) return hipSuccess;
   if (a.split_scratch == nullptr || scratch == nullptr || a.lpc_order < 1 || a.lpc_order > 32 || a.block_size < 64 ||
       a.block_size > 32767 || shape.n_windows < 1 || shape.n_windows > kMaxSearchWindows || shape.guess_orders > 32 ||
-      (shape.guess_orders && !shape.search_orders))
+      (shape.guess_orders && !shape.search_orders) || shape.n_precisions < 1 || shape.n_precisions > a.precision)
     return hipErrorInvalidValue;
   const size_t n = a.n_subframes;
   const uint32_t W = shape.n_windows;
   const uint32_t Pc = shape.search_orders ? a.lpc_order : 1u;
-  const uint32_t C = W * Pc;
+  const uint32_t Q = shape.n_precisions;
+  const uint32_t G = W * Pc, C = G * Q;
   const size_t slice = slice_subframes(n, a.lpc_order, shape);
   int32_t* pred = reinterpret_cast<int32_t*>(reinterpret_cast<double*>(a.split_scratch) + n * 33);
   double* racc = static_cast<double*>(scratch);
   double* refl = shape.guess_orders ? racc + slice * W * 33 : nullptr;
-  int32_t* cand = reinterpret_cast<int32_t*>(racc + slice * W * 33 + (refl ? slice * C : 0));
+  int32_t* cand = reinterpret_cast<int32_t*>(racc + slice * W * 33 + (refl ? slice * G : 0));
   uint32_t* best = reinterpret_cast<uint32_t*>(cand + slice * C * kCandWords);
 
   const bool lds_u = search_lds_bytes(a.block_size, true) <= 160 * 1024;
@@ -579,13 +629,14 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
     sl.W = W;
     sl.P = a.lpc_order;
     sl.Pc = Pc;
+    sl.Q = Q;
     sl.precision = a.precision;
     // 2. every candidate's predictor
     if ((err = levinson_bucket(false, sl, stream)) != hipSuccess) return err;
     if (refl) {  // 2b. the order guess: all but (0, P) and every window's guesses struck from the search
       const size_t items = (size_t)ns * W;
       hipLaunchKernelGGL(order_guess_kernel, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, stream, racc, refl, cand,
-                         ns, W, a.lpc_order, a.precision, a.block_size, a.bps ? a.bps + sf0 : nullptr, a.bps_uniform,
+                         ns, W, a.lpc_order, Q, a.precision, a.block_size, a.bps ? a.bps + sf0 : nullptr, a.bps_uniform,
                          a.stereo, shape.guess_orders,
                          shape.guess_trace ? static_cast<order_guess::Guess*>(shape.guess_trace) + sf0 * W : nullptr);
       if ((err = hipGetLastError()) != hipSuccess) return err;
@@ -601,7 +652,6 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
     s.bps_uniform = a.bps_uniform;
     s.lpc_order = a.lpc_order;
     s.n_cand = C;
-    s.precision = a.precision;
     s.max_rice_parameter = a.max_rice_parameter;
     s.rice_finest_only = a.rice_finest_only;
     s.cand = cand;

@@ -149,6 +149,7 @@ __global__ void __launch_bounds__(256, ((STEREO && K == 1) || MODE == FLACENC_BI
   // which row of the frame this wave filters, behind which predictor, and where its residual goes
   int role = STEREO ? wave : 0;
   int warm, shift, status;
+  uint32_t precision = a.precision;  // MODE 0 / 1: the predictor record's word 35 when not 0 (the precision search)
   const int32_t* __restrict__ pr = nullptr;                        // MODE 0 / 1: qc[32], order, shift, status
   const flacenc_hip_subframe_params* __restrict__ prec = nullptr;  // MODE 2: the chosen candidate's record
   int32_t* __restrict__ rrow = nullptr;
@@ -189,6 +190,7 @@ __global__ void __launch_bounds__(256, ((STEREO && K == 1) || MODE == FLACENC_BI
     warm = uni(pr[32]);
     shift = uni(pr[33]);
     status = uni(pr[34]);
+    if (uni(pr[35]) != 0) precision = (uint32_t)uni(pr[35]);
     rrow = a.residual + (size_t)sf * a.residual_stride;
     if (STEREO && a.residual_lr != nullptr && role < 2)  // L / R candidates in place of the output channel they can fill
       rrow = a.residual_lr + (size_t)(2u * blk + (uint32_t)role) * a.residual_lr_stride;
@@ -662,7 +664,7 @@ __global__ void __launch_bounds__(256, ((STEREO && K == 1) || MODE == FLACENC_BI
   const unsigned long long sub_bits = a.fixed_mode != 0
       ? 8ull + bps_role * (unsigned long long)warm + residual_bits
       : 8ull + bps_role * (unsigned long long)warm + 4ull + 5ull +
-            (unsigned long long)a.precision * (unsigned long long)warm + residual_bits;
+            (unsigned long long)precision * (unsigned long long)warm + residual_bits;
 
   stamp(5);  // Rice search
   if (a.minmax_out != nullptr && active && lane == 0) {
@@ -702,7 +704,7 @@ __global__ void __launch_bounds__(256, ((STEREO && K == 1) || MODE == FLACENC_BI
   if (lane == 0) {
     rec->order = (uint8_t)warm;
     rec->shift = (int8_t)shift;
-    rec->precision = (uint8_t)(a.fixed_mode != 0 ? 0u : a.precision);
+    rec->precision = (uint8_t)(a.fixed_mode != 0 ? 0u : precision);
     rec->rice_order = (uint8_t)(status == 0 ? rice_order : 0);
     rec->status = status;
     rec->code_bits = status == 0 ? best_bits : 0ull;

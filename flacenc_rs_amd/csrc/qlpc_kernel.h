@@ -134,7 +134,8 @@ struct QlpcKernelArgs {
   unsigned long long* selector_keys = nullptr;  // device, nullable, [n]: the chosen order's selector key
   // three-launch split of the generic kernel for large orders (launch_qlpc): 0 = fused,
   // 1 = window + autocorrelation only (R[] to `autocorr`), 3 = residual + Rice with the predictor
-  // levinson_batch_kernel left in `pred` ([n][36] int32: qc[32], order, shift, status, 0)
+  // levinson_batch_kernel left in `pred` ([n][36] int32: qc[32], order, shift, status, 0 -- or, from the precision
+  // search, the subframe's precision in place of `precision`)
   uint32_t lpc_stage = 0;
   const int32_t* pred = nullptr;
   int32_t* pred_out = nullptr;

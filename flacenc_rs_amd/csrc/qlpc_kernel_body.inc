@@ -893,15 +893,18 @@
     // side channel carries one extra bit (ChannelAssignment::bits_per_sample_offset, coding.rs:444)
     unsigned long long bps = a.bps ? (unsigned long long)a.bps[sf]
                                    : (unsigned long long)(a.bps_uniform + (role == 3 ? 1u : 0u));
+    // (a predictor record of the precision search carries its own precision in word 35; 0: the launch's)
+    uint32_t precision = a.precision;
+    if (a.lpc_stage == 3u && a.pred[(size_t)sf * 36 + 35] != 0) precision = (uint32_t)a.pred[(size_t)sf * 36 + 35];
     unsigned long long sub_bits = 8ull + bps * (unsigned long long)warm + 4ull + 5ull +
-                                  (unsigned long long)a.precision * (unsigned long long)warm + residual_bits;
+                                  (unsigned long long)precision * (unsigned long long)warm + residual_bits;
     // BitRepr for FixedLpc::count_bits, bitrepr.rs:473-477
     if (a.fixed_mode != 0) sub_bits = 8ull + bps * (unsigned long long)warm + residual_bits;
     // OrderSel::BitCount's key: bits_per_sample * order + code_bits (coding.rs:249)
     if (a.fixed_mode >= 2u && a.selector_keys) a.selector_keys[sf] = bps * (unsigned long long)warm + code_bits;
     rec->order = (uint8_t)warm;
     rec->shift = (int8_t)shift;
-    rec->precision = (uint8_t)(a.fixed_mode != 0 ? 0u : a.precision);
+    rec->precision = (uint8_t)(a.fixed_mode != 0 ? 0u : precision);
     rec->rice_order = (uint8_t)(status == 0 ? rice_order : 0);
     rec->status = status;
     rec->code_bits = status == 0 ? code_bits : 0ull;

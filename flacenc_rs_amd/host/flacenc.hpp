@@ -489,7 +489,7 @@ class HipContext {
   HipContext& operator=(const HipContext&) = delete;
   HipContext(HipContext&& o) noexcept  // std::vector<HipContext>: one per GPU
       : h_(o.h_), sum_order_(o.sum_order_), order_search_(o.order_search_), window_search_(o.window_search_),
-        order_guess_(o.order_guess_) {
+        order_guess_(o.order_guess_), precision_search_(o.precision_search_) {
     o.h_ = nullptr;
   }
   HipContext& operator=(HipContext&& o) noexcept {
@@ -500,6 +500,7 @@ class HipContext {
       order_search_ = o.order_search_;
       window_search_ = o.window_search_;
       order_guess_ = o.order_guess_;
+      precision_search_ = o.precision_search_;
       o.h_ = nullptr;
     }
     return *this;
@@ -543,9 +544,20 @@ class HipContext {
     if (flacenc_hip_set_order_guesses(h_, k) != FLACENC_HIP_OK)
       throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
   }
+  // FLACENC_HIP_FLAG_PRECISION_SEARCH: every LPC subframe coded at each coefficient precision from quant_precision down to
+  // the handle's floor (set_precision_floor: kDefaultPrecisionFloor on a fresh handle), the shortest kept (the records
+  // stay ordinary SubFrame::Lpc at the chosen precision); off by default
+  static constexpr uint32_t kDefaultPrecisionFloor = 5;
+  void set_precision_search(bool on) { precision_search_ = on; }
+  bool precision_search() const { return precision_search_; }
+  void set_precision_floor(uint32_t floor) {
+    if (flacenc_hip_set_precision_floor(h_, floor) != FLACENC_HIP_OK)
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+  }
   uint32_t sum_order_flags(size_t lpc_order) const {
     const uint32_t os = (order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u) | (window_search_ ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u) |
-                        (order_guess_ ? FLACENC_HIP_FLAG_ORDER_GUESS : 0u);
+                        (order_guess_ ? FLACENC_HIP_FLAG_ORDER_GUESS : 0u) |
+                        (precision_search_ ? FLACENC_HIP_FLAG_PRECISION_SEARCH : 0u);
     // (the mirror consumes integers only: certified shapes keep their own order, INTEGER_PARITY_ONLY)
     if (sum_order_ == SumOrder::Stable) return FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY | os;
     if (sum_order_ == SumOrder::SimdNightly && lpc_order <= 15) return FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER | os;
@@ -587,6 +599,7 @@ class HipContext {
   bool order_search_ = false;
   bool window_search_ = false;
   bool order_guess_ = false;
+  bool precision_search_ = false;
 };
 
 // Staging memory for the host-pointer entry points: page-locked (flacenc_hip_host_alloc), so that the

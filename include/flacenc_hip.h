@@ -267,6 +267,37 @@ extern "C" {
  * window, order) for k_o, inside the same 768 MiB slice bound. */
 #define FLACENC_HIP_FLAG_ORDER_GUESS 4096u
 
+/* LPC coefficient precision search (libFLAC's -p, do_qlp_coeff_prec_search), an extension like the three flags above: an
+ * LPC subframe pays order x precision bits for its coefficients whatever its length, so every LPC candidate subframe with
+ * lpc_order = P and quant_precision = q0 (a role, a channel, a row of a candidate batch, a shifted row under WASTED_BITS)
+ * is coded at the precisions q_i = q0 - i, i = 0 .. Q-1, and the shortest result is kept.  F is the handle's floor
+ * (flacenc_hip_set_precision_floor; a fresh handle holds 5, libFLAC's FLAC__MIN_QLP_COEFF_PRECISION): Q = q0 - F + 1 when
+ * F < q0, else 1.
+ *   - the candidates are (j, o, i): (j, o) ranges exactly over what the other flags define -- (0, P) alone; every order
+ *     under ORDER_SEARCH; every window under WINDOW_SEARCH; (0, P) and each window's K guesses under ORDER_GUESS, whose
+ *     guesses are computed as without this flag (its cost formula keeps q = q0) -- and each kept (j, o) is coded at every
+ *     q_i;
+ *   - candidate (j, o, i) is the recursion on R_j[0..o] with the status checks, as under those flags (R_j in the stable
+ *     build's order, nightly's under NIGHTLY_SUM_ORDER; CANONICAL_SUM_ORDER and INTEGER_PARITY_ONLY have no effect), then
+ *     quantize_parameters(a, q_i) on the unquantised coefficients -- which do not depend on i --, the residual and the
+ *     exhaustive Rice search (max_rice_parameter and FINEST_RICE_ORDER honoured), keyed by the exact Lpc::count_bits with
+ *     q_i in the precision term;
+ *   - the candidate with status 0 and the smallest key is coded, ties to the lower window, then the lower order, then the
+ *     higher precision; if none has status 0, candidate (0, P, q0), status included.
+ * The record and residual row are the winner's and record.precision is its q_i; `autocorr` and `lpc_coefs` are as the other
+ * search flags define them.  Candidate (0, P, q0) is the REFERENCE_SUM_ORDER record (NIGHTLY_SUM_ORDER's under that flag),
+ * so no flagged record or frame is longer than that call's, nor than the same call without this flag when other search
+ * flags are set.  Unlike the order search, bytes do change at lpc_order 1.  With F >= q0 every output and launch is that of
+ * the same call without this flag: of the call with REFERENCE_SUM_ORDER (or NIGHTLY_SUM_ORDER) in its place when no other
+ * search flag remains.  The floor has no effect without the flag.  Honoured where ORDER_SEARCH is (candidate batches,
+ * every frame-level call; composes with WASTED_BITS, ORDER_SEARCH, WINDOW_SEARCH and ORDER_GUESS; FUSED_PACK ignored;
+ * flacenc_hip_fixed_lpc_batch accepts and ignores it); use_direct_mse with this flag answers FLACENC_HIP_ERR_UNSUPPORTED
+ * (flacenc_hip_verify_config and every call).  No host synchronisation: a flagged call is capturable wherever the
+ * ORDER_SEARCH call is.
+ * Scratch: 144 B per (subframe, window, order, precision) in place of ORDER_SEARCH's 144 B per (subframe, window, order),
+ * inside the same 768 MiB slice bound; k_o stays 8 B per (subframe, window, order). */
+#define FLACENC_HIP_FLAG_PRECISION_SEARCH 8192u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1
@@ -351,6 +382,10 @@ int flacenc_hip_set_lpc_windows(flacenc_hip_handle* h, const uint32_t* types, co
  * fresh handle holds 1.  Read when a call is enqueued: it applies to the calls made after it, and has no effect without
  * the flag. */
 int flacenc_hip_set_order_guesses(flacenc_hip_handle* h, uint32_t k);
+/* FLACENC_HIP_FLAG_PRECISION_SEARCH: F, the lowest precision searched, 1..=15 (else FLACENC_HIP_ERR_BAD_ARGUMENT, the
+ * value kept); a fresh handle holds 5.  Read when a call is enqueued: it applies to the calls made after it, and has no
+ * effect without the flag. */
+int flacenc_hip_set_precision_floor(flacenc_hip_handle* h, uint32_t floor);
 /* The weights of one extra-window entry over a block of block_size (<= 32767) samples, on the host: no handle, no GPU.
  * The same validation as flacenc_hip_set_lpc_windows (FLACENC_HIP_ERR_BAD_CONFIG). */
 int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,

@@ -63,6 +63,11 @@ pub const FLAG_WINDOW_SEARCH: u32 = 2048;
 /// `(0, lpc_order)` and the handle's K guesses per window (`flacenc_hip_set_order_guesses`) are coded.  Not with
 /// `FLAG_ORDER_SEARCH`.  The records stay ordinary `SubFrame::Lpc`.  The drop-in never sets it.
 pub const FLAG_ORDER_GUESS: u32 = 4096;
+/// `FLACENC_HIP_FLAG_PRECISION_SEARCH`: every LPC candidate is coded at each coefficient precision from the config's
+/// `quant_precision` down to the handle's floor (`flacenc_hip_set_precision_floor`, 5 on a fresh handle) and the
+/// shortest is kept.  The records stay ordinary `SubFrame::Lpc` at the chosen precision.  The drop-in never sets it.
+pub const FLAG_PRECISION_SEARCH: u32 = 8192;
+pub const DEFAULT_PRECISION_FLOOR: u32 = 5;
 /// Extra-window types of `FLAG_WINDOW_SEARCH` (the config's `window_type` keeps rejecting them), the most windows per
 /// subframe, and the unit of an extra window's `start` / `end`.
 pub const WINDOW_PARTIAL_TUKEY: u32 = 2;
@@ -288,6 +293,8 @@ extern "C" {
     ) -> c_int;
     /// `FLAG_ORDER_GUESS`'s guesses per window of a handle, `1..=32` (a fresh handle holds 1).
     pub fn flacenc_hip_set_order_guesses(h: *mut Handle, k: u32) -> c_int;
+    /// `FLAG_PRECISION_SEARCH`'s lowest precision of a handle, `1..=15` (a fresh handle holds 5).
+    pub fn flacenc_hip_set_precision_floor(h: *mut Handle, floor: u32) -> c_int;
     /// One extra-window entry's weights over a block, on the host.
     pub fn flacenc_hip_lpc_window_weights(
         window_type: u32, alpha: f32, start: u32, end: u32, block_size: u32, out: *mut f32,
@@ -509,6 +516,15 @@ impl Gpu {
         match unsafe { flacenc_hip_create(&mut h, device_id) } {
             OK => Ok(Self(h, order)),
             _ => Err(EncodeError::Config(VerifyError::new("gpu", "no usable HIP device"))),
+        }
+    }
+
+    /// The lowest coefficient precision `FLAG_PRECISION_SEARCH` tries on this handle, `1..=15`; it has no effect on a
+    /// call without the flag.
+    pub fn set_precision_floor(&self, floor: u32) -> Result<(), EncodeError> {
+        match unsafe { flacenc_hip_set_precision_floor(self.0, floor) } {
+            OK => Ok(()),
+            _ => Err(EncodeError::Config(VerifyError::new("precision_floor", "must be in range 1..=15"))),
         }
     }
 }

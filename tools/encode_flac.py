@@ -8,7 +8,7 @@ MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-f
 frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
-                                  [--window-search] [--order-guess [K]]
+                                  [--window-search] [--order-guess [K]] [--precision-search [FLOOR]]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -23,6 +23,9 @@ With --window-search (FLACENC_HIP_FLAG_WINDOW_SEARCH) every LPC subframe is also
 With --order-guess [K] (FLACENC_HIP_FLAG_ORDER_GUESS, libFLAC's default mode) the order of every LPC subframe is guessed
 from the Levinson prediction error: --lpc-order and the K guesses (default 1) per window are coded and the shortest kept;
 the histogram of the chosen orders is printed.  Not together with --order-search.
+With --precision-search [FLOOR] (FLACENC_HIP_FLAG_PRECISION_SEARCH, libFLAC's -p) every LPC subframe is coded at each
+coefficient precision from 15 down to FLOOR (default 5) and the shortest kept; the histogram of the chosen precisions is
+printed.  Composes with the three searches above.
 """
 import argparse
 import hashlib
@@ -126,6 +129,10 @@ def main():
                     help="guess the LPC order of every subframe from the Levinson error and code --lpc-order and the K "
                          "guesses per window, K in 1..32, default 1 (FLACENC_HIP_FLAG_ORDER_GUESS); composes with "
                          "--window-search, not with --order-search")
+    ap.add_argument("--precision-search", type=int, nargs="?", const=_capi.DEFAULT_PRECISION_FLOOR, default=0,
+                    metavar="FLOOR",
+                    help="code every LPC subframe at each coefficient precision from 15 down to FLOOR, 1..15, default 5, "
+                         "and keep the shortest (FLACENC_HIP_FLAG_PRECISION_SEARCH); composes with the other searches")
     ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
     if args.order_guess and args.order_search:
@@ -135,7 +142,12 @@ def main():
     flags = (_capi.FLAG_WASTED_BITS if args.wasted_bits else 0) | (_capi.FLAG_ORDER_SEARCH if args.order_search else 0)
     flags |= _capi.FLAG_WINDOW_SEARCH if args.window_search else 0  # (a fresh handle holds DEFAULT_LPC_WINDOWS)
     flags |= _capi.FLAG_ORDER_GUESS if args.order_guess else 0
+    if args.precision_search < 0 or args.precision_search > 15:
+        ap.error("--precision-search FLOOR must be in 1..15")
+    flags |= _capi.FLAG_PRECISION_SEARCH if args.precision_search else 0
     handle = _capi.Handle(0)
+    if args.precision_search:
+        handle.set_precision_floor(args.precision_search)
     if args.order_guess:
         handle.set_order_guesses(args.order_guess)
     n = 4096
@@ -173,6 +185,9 @@ def main():
         orders = res["lpc"]["order"][res["kind"] == 3]
         hist = np.bincount(orders, minlength=args.lpc_order + 1)
         print("chosen LPC orders: " + ", ".join(f"{o}: {int(c)}" for o, c in enumerate(hist) if c))
+    if args.precision_search:
+        hist = np.bincount(res["lpc"]["precision"][res["kind"] == 3], minlength=16)
+        print("chosen LPC precisions: " + ", ".join(f"{q}: {int(c)}" for q, c in enumerate(hist) if c))
 
 
 if __name__ == "__main__":
