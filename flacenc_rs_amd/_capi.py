@@ -456,6 +456,7 @@ FLAG_ORDER_SEARCH = 1024  # every LPC candidate's order chosen by an exhaustive 
 FLAG_WINDOW_SEARCH = 2048  # every LPC candidate analysed under the config's window and the handle's extra windows
 FLAG_ORDER_GUESS = 4096  # the LPC order guessed from the Levinson error: (0, P) and K guesses per window are coded
 FLAG_PRECISION_SEARCH = 8192  # every LPC candidate coded at each precision quant_precision .. the handle's floor
+FLAG_RICE_ESCAPE = 16384  # Rice partitions may be stored escaped (raw, rice_params[q] = 0x80 | width): the general path
 DEFAULT_PRECISION_FLOOR = 5  # a fresh handle's floor (flacenc_hip_set_precision_floor)
 
 

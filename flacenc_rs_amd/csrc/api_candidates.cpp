@@ -6,6 +6,7 @@
 #include "api_internal.h"
 #include "direct_mse.h"
 #include "order_search.h"
+#include "rice_escape.h"
 
 namespace {  // (the two kernels of this unit, outside flacenc_hip: their names in a kernel trace stay what they were)
 
@@ -313,12 +314,30 @@ int launch_adaptive(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, const
   return FLACENC_HIP_OK;
 }
 
-int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
-            size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
-            flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
-            double* autocorr, double* lpc_coefs, hipStream_t stream, bool stereo, uint32_t bps_uniform,
-            int32_t* residual_lr, size_t residual_lr_stride, int32_t* minmax_out, bool* placed,
-            uint32_t residual_mode) {
+// FLACENC_HIP_FLAG_RICE_ESCAPE: the post-pass over the records and rows a candidate batch has just enqueued
+// (rice_escape.cpp)
+int enqueue_rice_escape(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, flacenc_hip_subframe_params* params,
+                        const int32_t* residual, size_t residual_stride, size_t n_subframes, uint32_t block_size,
+                        hipStream_t stream) {
+  flacenc_hip::RiceEscapeArgs e{};
+  e.params = params;
+  e.residual = residual;
+  e.residual_stride = residual_stride;
+  e.block_size = block_size;
+  e.n_rows = static_cast<uint32_t>(n_subframes);
+  e.max_rice_parameter = q.max_rice_parameter;
+  e.finest_only = (q.flags & FLACENC_HIP_FLAG_FINEST_RICE_ORDER) ? 1u : 0u;
+  HIP_TRY(h, flacenc_hip::launch_rice_escape(e, stream));
+  return FLACENC_HIP_OK;
+}
+
+namespace {
+int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
+                size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
+                flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
+                double* autocorr, double* lpc_coefs, hipStream_t stream, bool stereo, uint32_t bps_uniform,
+                int32_t* residual_lr, size_t residual_lr_stride, int32_t* minmax_out, bool* placed,
+                uint32_t residual_mode) {
   if (placed) *placed = false;
   flacenc_hip_qlpc_config qcfg = *cfg;
   qcfg.flags = search_flags(h, cfg->flags, cfg->quant_precision);
@@ -422,6 +441,30 @@ int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int
   }
   return launch_adaptive(h, a, plan, stream);
 }
+}  // namespace
+
+// The one exit of the LPC candidates.  Under FLACENC_HIP_FLAG_RICE_ESCAPE every record and row goes to `params` /
+// `residual` (no rows placed in the caller's frame, no analyse-only launch) and the escape pass runs behind them -- on
+// the winner's record where a search flag chose one.
+int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
+            size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
+            flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
+            double* autocorr, double* lpc_coefs, hipStream_t stream, bool stereo, uint32_t bps_uniform,
+            int32_t* residual_lr, size_t residual_lr_stride, int32_t* minmax_out, bool* placed,
+            uint32_t residual_mode) {
+  if (!(cfg->flags & FLACENC_HIP_FLAG_RICE_ESCAPE))
+    return enqueue_lpc(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual, residual_stride, autocorr,
+                       lpc_coefs, stream, stereo, bps_uniform, residual_lr, residual_lr_stride, minmax_out, placed,
+                       residual_mode);
+  if (residual_mode != 0u) {
+    h->last_error = "internal: analyse-only QLPC batch under FLACENC_HIP_FLAG_RICE_ESCAPE";
+    return FLACENC_HIP_ERR_UNSUPPORTED;
+  }
+  int rc = enqueue_lpc(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual, residual_stride, autocorr,
+                       lpc_coefs, stream, stereo, bps_uniform, nullptr, 0, nullptr, placed, 0u);
+  if (rc != FLACENC_HIP_OK) return rc;
+  return enqueue_rice_escape(h, *cfg, params, residual, residual_stride, n_subframes, block_size, stream);
+}
 
 // config::Fixed::verify (config.rs:246-255) + OrderSel::verify (:419-431)
 int verify_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg) {
@@ -444,6 +487,16 @@ int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
                   uint32_t residual_mode) {
   int rc = verify_fixed(h, cfg);
   if (rc != FLACENC_HIP_OK) return rc;
+  // FLACENC_HIP_FLAG_RICE_ESCAPE: the pass runs on the selected order's record; the selector's keys (and BitCount's
+  // comparison of unescaped code_bits) are what they are without the flag
+  auto escape = [&](int done) -> int {
+    if (done != FLACENC_HIP_OK || !(cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE)) return done;
+    return enqueue_rice_escape(h, cfg->qlpc, params, residual, residual_stride, n_subframes, block_size, stream);
+  };
+  if ((cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE) && residual_mode != 0u) {
+    h->last_error = "internal: analyse-only fixed_lpc batch under FLACENC_HIP_FLAG_RICE_ESCAPE";
+    return FLACENC_HIP_ERR_UNSUPPORTED;
+  }
   flacenc_hip::QlpcLaunchPlan plan = flacenc_hip::plan_qlpc_launch(block_size, 4);
   if (plan.smem_bytes > 160 * 1024) {
     h->last_error = "internal: LDS plan exceeds 160 KiB";
@@ -481,7 +534,7 @@ int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
       a.residual_mode = 1u;
     }
     HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-    return FLACENC_HIP_OK;
+    return escape(FLACENC_HIP_OK);
   }
   // BitCount: code every order, keep the first minimum of bps*order + code_bits, code it again
   const uint32_t n_orders = cfg->fixed_max_order + 1;
@@ -506,7 +559,7 @@ int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
   a.forced_orders = static_cast<const uint8_t*>(h->d_sel.ptr);
   a.selector_keys = nullptr;
   HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-  return FLACENC_HIP_OK;
+  return escape(FLACENC_HIP_OK);
 }
 
 }  // namespace flacenc_hip

@@ -393,7 +393,8 @@ int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_frame_con
   if (cfg->qlpc.flags & FLACENC_HIP_FLAG_TWO_STAGE_PACK) want_fused = false;
   // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH: the candidate batches +
   // frame_decide_kernel for every shape (FUSED_PACK ignored)
-  const bool order_search = lpc_search(cfg->qlpc.flags) && cfg->use_lpc;
+  // FLACENC_HIP_FLAG_RICE_ESCAPE: the same, whatever the candidates -- the pass sits between the batches and the decision
+  const bool order_search = (lpc_search(cfg->qlpc.flags) && cfg->use_lpc) || (cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE);
   if (pack && want_fused && !fixed_composite && !order_search && block_size == 4096 && wave_kernel_eligible(a)) {
     attach_fused_pack(a, pack, bits_per_sample);
     if (packed) *packed = a.pack_out != nullptr;
@@ -469,7 +470,8 @@ int flacenc_hip_encode_frames_async(flacenc_hip_handle* h, const flacenc_hip_fra
   d.residual = residual;
   d.residual_stride = residual_stride;
   // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: the candidate batches + channel_decide_kernel for every shape
-  if (!(lpc_search(cfg->qlpc.flags) && cfg->use_lpc)) {
+  // ... and FLACENC_HIP_FLAG_RICE_ESCAPE, whose pass sits between the batches and the decision
+  if (!((lpc_search(cfg->qlpc.flags) && cfg->use_lpc) || (cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE))) {
     // block size 4096, order <= 12: one fused kernel, a wave per channel (analysis, fixed-LPC
     // candidate, encode_subframe's choice, only the chosen residual written)
     bool composite = false;

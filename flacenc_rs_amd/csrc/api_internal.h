@@ -173,6 +173,7 @@ struct flacenc_hip_handle {
   flacenc_hip::DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
   // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
   flacenc_hip::DeviceBuffer d_order;
+  flacenc_hip::DeviceBuffer d_esc;  // the packers' list of frames with escaped partitions (FramePackArgs::escape_list)
   uint32_t order_guesses = 1;  // FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window (flacenc_hip_set_order_guesses)
   // FLACENC_HIP_FLAG_PRECISION_SEARCH: F, the lowest precision searched (flacenc_hip_set_precision_floor)
   uint32_t precision_floor = 5;

@@ -152,6 +152,15 @@ static int enqueue_pack(flacenc_hip_handle* h, const int32_t* frames, size_t n_f
     return FLACENC_HIP_ERR_UNSUPPORTED;
   }
   HIP_TRY(h, hipSetDevice(h->device));
+  // the list of frames with escaped partitions between the packer's two launches (FramePackArgs::escape_list); its
+  // counters are zero whenever no pack is in flight, a new buffer's are cleared here
+  {
+    const size_t before = h->d_esc.cap;
+    int rc = flacenc_hip::ensure(h, h->d_esc, (16 + n_frames) * sizeof(uint32_t));
+    if (rc != FLACENC_HIP_OK) return rc;
+    if (h->d_esc.cap != before) HIP_TRY(h, hipMemsetAsync(h->d_esc.ptr, 0, 64, static_cast<hipStream_t>(stream)));
+    a.escape_list = static_cast<uint32_t*>(h->d_esc.ptr);
+  }
   HIP_TRY(h, flacenc_hip::launch_frame_pack(a, static_cast<hipStream_t>(stream)));
   return FLACENC_HIP_OK;
 }

@@ -15,6 +15,7 @@
 
 #include "frame_bits.h"
 #include "lds_opt_in.h"
+#include "rice_escape_core.h"
 
 #ifndef FLACENC_DPP
 #define FLACENC_DPP(v, ctrl, rowmask) \
@@ -25,6 +26,7 @@ namespace flacenc_hip {
 namespace {
 
 constexpr int kPackThreads = 256;
+constexpr uint32_t kEscapeGrid = 512;  // workgroups of the launch for frames with escaped partitions
 #ifndef FLACENC_PACK_OCC
 #define FLACENC_PACK_OCC 8  // waves per SIMD asked of the register allocator (<= 64 VGPRs)
 #endif
@@ -111,16 +113,18 @@ struct ScanScratch {
 
 // One thread = one run of 16 samples inside one partition; `params` is the subframe's Rice parameter
 // list in global memory (each thread needs exactly one entry per round).  Writes the 6-bit residual header
-// too (it needs RICE2 = any parameter > 14, which rides on the first round's scan barrier).
-__device__ __forceinline__ void rice_runs16(uint32_t* words, const int32_t* __restrict__ e, int n, uint32_t order,
+// too (it needs RICE2 = any parameter > 14, which rides on the first round's scan barrier).  So does the answer to "is a
+// partition marked as escaped (0x80 | width)?": true comes back before anything of the residual is written, and the
+// caller leaves the frame to the escape launch.
+__device__ __forceinline__ bool rice_runs16(uint32_t* words, const int32_t* __restrict__ e, int n, uint32_t order,
                                             uint32_t porder, const uint8_t* __restrict__ params, uint32_t hdr_pos,
                                             ScanScratch* ss, uint32_t* scan_id, int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   const uint32_t part_len = (uint32_t)n >> porder;
   const float inv_pl16 = 1.0f / (float)(part_len >> 4);
   // any parameter above 14 switches the whole residual to 5-bit parameters (bitrepr.rs:540-543, 556-562)
-  uint32_t big = (uint32_t)tid < (1u << porder) ? (params[tid] > 14 ? 1u : 0u) : 0u;
-  big = __any((int)big) ? 1u : 0u;
+  const uint32_t mine = (uint32_t)tid < (1u << porder) ? params[tid] : 0u;
+  const uint32_t big = (__any(mine > 14u) ? 1u : 0u) | (__any((mine & 0x80u) != 0u) ? 2u : 0u);
   uint32_t pbits = 4u;
   uint32_t round_base = hdr_pos + 6u;
   for (int r0 = 0; r0 < n; r0 += 16 * kPackThreads) {
@@ -180,7 +184,9 @@ __device__ __forceinline__ void rice_runs16(uint32_t* words, const int32_t* __re
     __syncthreads();
     const uint32_t t0 = ss->total[buf][0], t1 = ss->total[buf][1], t2 = ss->total[buf][2], t3 = ss->total[buf][3];
     if (r0 == 0) {
-      const uint32_t rice2 = ss->flag[buf][0] | ss->flag[buf][1] | ss->flag[buf][2] | ss->flag[buf][3];
+      const uint32_t flags = ss->flag[buf][0] | ss->flag[buf][1] | ss->flag[buf][2] | ss->flag[buf][3];
+      if (flags & 2u) return true;  // (uniform)
+      const uint32_t rice2 = flags & 1u;
       pbits = rice2 ? 5u : 4u;
       if (tid == 192) put_bits(words, hdr_pos, (rice2 << 4) | porder, 6u);
     }
@@ -195,6 +201,91 @@ __device__ __forceinline__ void rice_runs16(uint32_t* words, const int32_t* __re
       else rice_emit16<false>(words, uc, p, pos, nskip);
     }
   }
+  return false;
+}
+
+// Does the record mark a partition as escaped (rice_params[q] = 0x80 | width, rice_escape_core.h)?  Every wave looks at
+// all 2^porder parameters, four per lane, so the answer needs no barrier.  (rice_params sits at a multiple of 4 bytes
+// in both result records.)
+__device__ __forceinline__ bool record_has_marks(const uint8_t* __restrict__ params, uint32_t nparts, int tid) {
+  const uint32_t first = 4u * (uint32_t)(tid & 63);
+  const uint32_t live = nparts > first ? nparts - first : 0u;  // parameters of this lane's word that exist
+  const uint32_t v = *reinterpret_cast<const uint32_t*>(params + first);
+  const uint32_t m = live >= 4u ? 0x80808080u : (live == 0u ? 0u : 0x80808080u >> (8u * (4u - live)));
+  return __any((v & m) != 0u) != 0;
+}
+
+// Residual::write for a record with marked partitions, any block size and partition length: the general walk (a
+// contiguous slice of samples per thread, counted, scanned, written) with the escaped form of RFC 9639 9.2.7.1 for a
+// marked partition -- the escape code at the parameter width, the 5-bit width, then every residual in two's complement
+// at that width (nothing at width 0).  RICE2 is decided over the unmarked parameters.  Compiled into the ESCAPE
+// instances of the kernels only: frames without marks never come here, and the kernels they take stay as they were.
+__device__ __forceinline__ void rice_escaped_walk(uint32_t* words, const int32_t* __restrict__ e, int n, uint32_t order,
+                                               uint32_t porder, const uint8_t* __restrict__ params, uint32_t hdr_pos,
+                                               uint8_t* rice_p, uint32_t* scan_scratch, int tid) {
+  const uint32_t nparts = 1u << porder, part_len = (uint32_t)n >> porder;
+  __syncthreads();  // the previous subframe is done with rice_p
+  rice_p[tid] = params[tid];
+  __syncthreads();
+  uint32_t rice2 = 0;
+  for (uint32_t q = tid; q < nparts; q += kPackThreads) rice2 |= rice_escape::wants_rice2(rice_p[q]) ? 1u : 0u;
+  rice2 = __syncthreads_or((int)rice2) ? 1u : 0u;
+  const uint32_t pbits = rice2 ? 5u : 4u, esc_code = rice2 ? 31u : 15u;
+  // bits of a partition's parameter field, and writing it at `pos`
+  auto field_bits = [&](uint32_t par) { return pbits + (rice_escape::is_marked(par) ? 5u : 0u); };
+  auto put_field = [&](uint32_t pos, uint32_t par) {
+    if (rice_escape::is_marked(par)) {
+      put_bits(words, pos, esc_code, pbits);
+      put_bits(words, pos + pbits, rice_escape::marked_width(par), 5u);
+    } else {
+      put_bits(words, pos, par, pbits);
+    }
+  };
+  // (an empty first partition still has its field: it goes out with the header, as in the general walk)
+  const uint32_t lead0 = (order != 0u && order == part_len) ? field_bits(rice_p[0]) : 0u;
+  if (tid == 192) {
+    put_bits(words, hdr_pos, (rice2 << 4) | porder, 6u);
+    if (lead0) put_field(hdr_pos + 6u, rice_p[0]);
+  }
+  const int per = (n + kPackThreads - 1) / kPackThreads;
+  const int t_lo = tid * per < n ? tid * per : n;
+  const int t_hi = t_lo + per < n ? t_lo + per : n;
+  const uint32_t q_lo = (uint32_t)t_lo / part_len;
+  auto walk = [&](auto&& emit) {
+    uint32_t q = q_lo, next = (q_lo + 1u) * part_len;
+    for (int ti = t_lo; ti < t_hi; ++ti) {
+      const uint32_t t = (uint32_t)ti;
+      if (t == next) {
+        ++q;
+        next += part_len;
+      }
+      if (t >= order) emit(e[ti], (uint32_t)rice_p[q & 255u], q == 0u ? t == order : t == next - part_len);
+    }
+  };
+  uint32_t my_bits = 0;
+  walk([&](int32_t v, uint32_t par, bool starts) {
+    my_bits += starts ? field_bits(par) : 0u;
+    my_bits += rice_escape::is_marked(par) ? rice_escape::marked_width(par) : (zigzag32(v) >> par) + 1u + par;
+  });
+  uint32_t total;
+  uint32_t pos = hdr_pos + 6u + lead0 + block_exclusive_scan(my_bits, scan_scratch, tid, &total);
+  walk([&](int32_t v, uint32_t par, bool starts) {
+    if (starts) {
+      put_field(pos, par);
+      pos += field_bits(par);
+    }
+    if (rice_escape::is_marked(par)) {
+      const uint32_t w = rice_escape::marked_width(par);
+      put_bits(words, pos, (uint32_t)v & ((1u << w) - 1u), w);
+      pos += w;
+    } else {
+      const uint32_t u = zigzag32(v);
+      pos += u >> par;  // unary quotient: zeros
+      put_bits(words, pos, (u & ((1u << par) - 1u)) | (1u << par), par + 1u);
+      pos += par + 1u;
+    }
+  });
+  (void)total;
 }
 
 // What the packer needs to know about one frame, for the two kinds of decision records.
@@ -248,8 +339,16 @@ struct ChannelView {  // flacenc_hip_channel_result x channels: Independent(n)
 
 // ALIGNED: the block size is a multiple of 4096, so every partition order up to 8 gives partitions that are
 // multiples of 16 samples and the walk over arbitrary partition boundaries is not compiled in.
-template <bool ALIGNED, class View>
+// ESCAPE: the instance for frames with marked (escaped) partitions.  The plain instance, one workgroup per frame, drops
+// a frame when it meets a marked record and puts it on a.escape_list; a second, small launch of the ESCAPE instance
+// writes the listed frames -- so what frames without marks run is the code it was before marks existed but for two wave
+// votes, and a launch without marked frames pays for a few hundred workgroups that read one counter.
+template <bool ALIGNED, bool ESCAPE, class View>
 __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const View& view, uint32_t f) {
+  // (the plain instance meets a marked record where it reads the parameters anyway, before anything leaves the LDS)
+  auto defer = [&]() {
+    if (threadIdx.x == 0) a.escape_list[16u + atomicAdd(&a.escape_list[0], 1u)] = f;
+  };
   extern __shared__ __attribute__((aligned(16))) uint32_t words[];
   __shared__ uint32_t scan_scratch[4];
   __shared__ ScanScratch scan_pairs;
@@ -351,18 +450,30 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
       const uint32_t nparts = 1u << porder;
       const uint32_t part_len = (uint32_t)n >> porder;
       const int32_t* __restrict__ e = a.residual + view.residual_row(c) * a.residual_stride;
-      if (ALIGNED || ((n & 15) == 0 && (part_len & 15u) == 0u)) {
+      if (ESCAPE && record_has_marks(rec->rice_params, nparts, tid)) {  // (uniform: a walk of its own)
+        rice_escaped_walk(words, e, n, order, porder, rec->rice_params, sb + head_bits, rice_p, scan_scratch, tid);
+      } else if (ALIGNED || ((n & 15) == 0 && (part_len & 15u) == 0u)) {
         // Aligned runs: a thread owns 16 consecutive samples of a round of 4096, which lie inside one
         // partition (its length is a multiple of 16) -- one Rice parameter per thread, no per-sample
         // partition walk.  A code of p + 1 <= 31 bits at bit offset <= 31 fits a 64-bit window over two
         // buffer words: one shift and two ORs per sample, no branch.
-        rice_runs16(words, e, n, order, porder, rec->rice_params, sb + head_bits, &scan_pairs, &scan_id, tid);
+        if (rice_runs16(words, e, n, order, porder, rec->rice_params, sb + head_bits, &scan_pairs, &scan_id, tid)) {
+          defer();
+          return;
+        }
       } else if (!ALIGNED) {
         __syncthreads();  // the previous subframe is done with rice_p
         rice_p[tid] = rec->rice_params[tid];
         __syncthreads();
-        uint32_t rice2 = 0;
-        for (uint32_t q = tid; q < nparts; q += kPackThreads) rice2 |= rice_p[q] > 14 ? 1u : 0u;
+        uint32_t rice2 = 0, marked = 0;
+        for (uint32_t q = tid; q < nparts; q += kPackThreads) {
+          rice2 |= rice_p[q] > 14 ? 1u : 0u;
+          marked |= rice_p[q] >> 7;
+        }
+        if (__syncthreads_or((int)marked)) {  // (uniform)
+          defer();
+          return;
+        }
         rice2 = __syncthreads_or((int)rice2) ? 1u : 0u;
         const uint32_t pbits = rice2 ? 5u : 4u;
         // A first partition without samples (order == part_len) still has its parameter (bitrepr.rs:567-571), and the
@@ -499,21 +610,16 @@ __device__ __forceinline__ void frame_pack_body(const FramePackArgs& a, const Vi
   }
 }
 
-template <bool ALIGNED>
-__global__ void __launch_bounds__(kPackThreads, ALIGNED ? FLACENC_PACK_OCC : 4) frame_pack_kernel(FramePackArgs a) {
-  const uint32_t f = blockIdx.x;
+__device__ __forceinline__ StereoView stereo_view(const FramePackArgs& a, uint32_t f) {
   StereoView v;
   v.fr = a.results + f;
   v.l = a.frames + (size_t)(2u * f) * a.stride;
   v.r = v.l + a.stride;
   v.bps0 = a.bits_per_sample;
   v.row0 = (size_t)(2u * f);
-  frame_pack_body<ALIGNED>(a, v, f);
+  return v;
 }
-
-template <bool ALIGNED>
-__global__ void __launch_bounds__(kPackThreads, ALIGNED ? FLACENC_PACK_OCC : 4) channel_pack_kernel(FramePackArgs a) {
-  const uint32_t f = blockIdx.x;
+__device__ __forceinline__ ChannelView channel_view(const FramePackArgs& a, uint32_t f) {
   ChannelView v;
   v.ch = a.chan_results + (size_t)f * a.channels;
   v.x = a.frames + (size_t)f * a.channels * a.stride;
@@ -521,7 +627,39 @@ __global__ void __launch_bounds__(kPackThreads, ALIGNED ? FLACENC_PACK_OCC : 4) 
   v.nch = a.channels;
   v.bps0 = a.bits_per_sample;
   v.row0 = (size_t)f * a.channels;
-  frame_pack_body<ALIGNED>(a, v, f);
+  return v;
+}
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(kPackThreads, ALIGNED ? FLACENC_PACK_OCC : 4) frame_pack_kernel(FramePackArgs a) {
+  const uint32_t f = blockIdx.x;
+  frame_pack_body<ALIGNED, false>(a, stereo_view(a, f), f);
+}
+
+template <bool ALIGNED>
+__global__ void __launch_bounds__(kPackThreads, ALIGNED ? FLACENC_PACK_OCC : 4) channel_pack_kernel(FramePackArgs a) {
+  const uint32_t f = blockIdx.x;
+  frame_pack_body<ALIGNED, false>(a, channel_view(a, f), f);
+}
+
+// The second launch: the workgroups share out the listed frames; the last one to leave clears the counter and the
+// tickets for the next launch on this list.
+template <bool ALIGNED, bool CHANNELS>
+__global__ void __launch_bounds__(kPackThreads, 2) frame_pack_escape_kernel(FramePackArgs a) {
+  const uint32_t count = a.escape_list[0];
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const uint32_t f = a.escape_list[16u + i];
+    if (CHANNELS) frame_pack_body<ALIGNED, true>(a, channel_view(a, f), f);
+    else frame_pack_body<ALIGNED, true>(a, stereo_view(a, f), f);
+    __syncthreads();  // the next frame clears the bit buffer
+  }
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(&a.escape_list[1], 1u) == gridDim.x - 1u) {  // every workgroup has read the count
+      a.escape_list[0] = 0u;
+      a.escape_list[1] = 0u;
+    }
+  }
 }
 
 // Frame::count_bits / 8 (bitrepr.rs:275-287) from the decision records alone
@@ -790,16 +928,22 @@ size_t stereo_frame_bytes_bound(uint32_t block_size, uint32_t bits_per_sample) {
 hipError_t launch_frame_pack(const FramePackArgs& a, hipStream_t stream) {
   if (a.n_frames == 0) return hipSuccess;
   const size_t smem = static_cast<size_t>(a.lds_words) * 4;
-  static DynamicLdsOptIn opt_in[4];  // per kernel, per device inside
+  static DynamicLdsOptIn opt_in[8];  // per kernel, per device inside
   const bool aligned = a.block_size % 4096u == 0u;
-  auto go = [&](auto kernel, DynamicLdsOptIn& opt) -> hipError_t {
+  auto go = [&](auto kernel, DynamicLdsOptIn& opt, uint32_t grid) -> hipError_t {
     if (hipError_t err = opt.ensure(reinterpret_cast<const void*>(kernel), smem); err != hipSuccess) return err;
-    hipLaunchKernelGGL(kernel, dim3(a.n_frames), dim3(kPackThreads), smem, stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPackThreads), smem, stream, a);
     return hipSuccess;
   };
   hipError_t err;
-  if (a.chan_results) err = aligned ? go(channel_pack_kernel<true>, opt_in[0]) : go(channel_pack_kernel<false>, opt_in[1]);
-  else err = aligned ? go(frame_pack_kernel<true>, opt_in[2]) : go(frame_pack_kernel<false>, opt_in[3]);
+  if (a.chan_results) err = aligned ? go(channel_pack_kernel<true>, opt_in[0], a.n_frames) : go(channel_pack_kernel<false>, opt_in[1], a.n_frames);
+  else err = aligned ? go(frame_pack_kernel<true>, opt_in[2], a.n_frames) : go(frame_pack_kernel<false>, opt_in[3], a.n_frames);
+  if (err != hipSuccess) return err;
+  if ((err = hipGetLastError()) != hipSuccess) return err;
+  // the frames with escaped partitions, as the first launch listed them
+  const uint32_t few = a.n_frames < kEscapeGrid ? a.n_frames : kEscapeGrid;
+  if (a.chan_results) err = aligned ? go(frame_pack_escape_kernel<true, true>, opt_in[4], few) : go(frame_pack_escape_kernel<false, true>, opt_in[5], few);
+  else err = aligned ? go(frame_pack_escape_kernel<true, false>, opt_in[6], few) : go(frame_pack_escape_kernel<false, false>, opt_in[7], few);
   if (err != hipSuccess) return err;
   return hipGetLastError();
 }

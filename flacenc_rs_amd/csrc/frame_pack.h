@@ -36,6 +36,10 @@ struct FramePackArgs {
   // (i < 16) with y = x^(8 crc_per) mod (x^16 + x^15 + x^2 + 1)
   uint32_t crc_per;
   uint16_t crc_pow[32];
+  // Frames with escaped partitions (rice_params[q] = 0x80 | width) are left to a second launch: [0] how many the first
+  // launch met, [1] the second launch's exit tickets, [16 + i] their frame indices.  Device, 16 + n_frames words, [0]
+  // and [1] zero on entry and again when the second launch has finished.
+  uint32_t* escape_list;
 };
 
 // worst-case frame length in bytes for a 2-channel frame (both subframes Verbatim, one a side channel)

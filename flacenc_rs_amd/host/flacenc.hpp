@@ -520,7 +520,9 @@ class HipContext {
   void set_sum_order(SumOrder o) { sum_order_ = o; }
   SumOrder sum_order() const { return sum_order_; }
   // (never FLACENC_HIP_FLAG_WASTED_BITS: the SubFrame rebuilt from the records has no wasted-bits field; a caller of
-  // encode_variable may pass it in cfg, and the frames' bytes then carry the wasted bits)
+  // encode_variable may pass it in cfg, and the frames' bytes then carry the wasted bits.  Nor
+  // FLACENC_HIP_FLAG_RICE_ESCAPE: component::Residual holds Rice parameters only, and a record with a partition marked
+  // 0x80 | width has no SubFrame; encode_variable takes the flag in cfg in the same way)
   // FLACENC_HIP_FLAG_ORDER_SEARCH: every LPC subframe's order searched over 1..lpc_order (the records stay ordinary
   // SubFrame::Lpc of the chosen order); off by default
   void set_order_search(bool on) { order_search_ = on; }

@@ -298,6 +298,48 @@ extern "C" {
  * inside the same 768 MiB slice bound; k_o stays 8 B per (subframe, window, order). */
 #define FLACENC_HIP_FLAG_PRECISION_SEARCH 8192u
 
+/* Escaped Rice partitions (RFC 9639 section 9.2.7.1), an extension like FLACENC_HIP_FLAG_WASTED_BITS: the reference never
+ * escapes (its parser reads the escape code as a parameter, src/component/parser.rs:653-690).  A partition may be stored
+ * as raw two's-complement samples of a 5-bit-coded width instead of Rice codes: 9 bits for a partition of digital silence,
+ * and never more than the container for noise.
+ * Record encoding: rice_params[q] = 0x80 | w marks partition q as escaped with raw width w, 0..31; values 0..30 stay Rice
+ * parameters; bits 5 and 6 of a marked byte are zero.  The record's size and wire form do not change.
+ * Definition, for one candidate record with status 0: residual row e, warm-up length o = record.order, block size n,
+ * max_p = max_rice_parameter.
+ *   1. F = finest_partition_order(n, max(64, o)) (src/rice.rs:157-165).  At level r = F .. 0 partition q covers
+ *      [max(q * (n >> r), o), (q + 1) * (n >> r)) and holds cnt samples.
+ *   2. R_r(q), the Rice cost, is what the unflagged search computes: PrcBitTable::from_errors(.., 4) at level F with its
+ *      clamps, merge(.., 4) below it, minimizer(max_p).
+ *   3. w_r(q), the raw width, is the smallest w with -2^(w-1) <= e < 2^(w-1) for every e of the partition; 0 when all
+ *      are zero or cnt = 0; a merged partition's width is the larger of its children's.
+ *   4. E_r(q) = 4 + 5 + cnt * w when w <= 31; a partition of width 32 cannot be escaped.
+ *   5. A partition is escaped iff E < R -- strictly: a tie stays Rice.
+ *   6. A level costs sum_q min(R, E); the walk is the reference's (src/rice.rs:277-291): from F, to a coarser level only
+ *      on a strictly smaller cost.  FLACENC_HIP_FLAG_FINEST_RICE_ORDER evaluates level F alone.
+ *   7. rice_order is the chosen level, rice_params its parameters or marks, code_bits its cost, sum_quotients the exact
+ *      sum of z >> k over the NON-escaped partitions, subframe_bits the exact count: everything in front of the residual
+ *      as Lpc::count_bits / FixedLpc::count_bits have it, then 2 + 4 + sum_q (pb + (escaped ? 5 + cnt * w :
+ *      sum(z >> k) + cnt * (k + 1))) with pb = 5 iff some NON-escaped parameter exceeds 14.  The escape code is 0b1111
+ *      under pb = 4 and 0b11111 under pb = 5.
+ * Consequences: a record in which no partition escapes is byte for byte the unflagged record (a level's flagged cost never
+ * exceeds its unflagged cost and both walks keep the finest level among the minima, so a chosen level without escapes is
+ * the unflagged choice); no flagged record or frame is longer than the same call's without the flag; records with
+ * status != 0 are left untouched.
+ * Honoured by the candidate batches (flacenc_hip_qlpc_batch[_async], _stereo_qlpc_batch[_async], _fixed_lpc_batch[_async]):
+ * a pass behind their kernels rewrites the five fields of the records they return; residual rows, `autocorr`,
+ * `lpc_coefs`, the selector keys of flacenc_hip_fixed_lpc_batch and the fixed order it selects are unchanged (the
+ * BitCount selector keeps comparing unescaped code_bits).  ORDER_SEARCH / WINDOW_SEARCH / ORDER_GUESS / PRECISION_SEARCH
+ * choose their winner by the unescaped key as without this flag, and the pass then runs on the winner's record:
+ * searching with escaped keys is not done.  The frame-level calls (flacenc_hip_encode_[stereo_]frames[_async],
+ * flacenc_hip_encode_pack_*_async, flacenc_hip_encode_pcm[_stereo], flacenc_hip_encode_variable[_async]) take the
+ * candidate batches and the stand-alone deciding kernels for every shape under this flag -- it trades the fused kernels
+ * for the general path -- and the deciding kernels compare the updated subframe_bits (the fixed candidate's selector key
+ * is held against the Verbatim size as without the flag).  FUSED_PACK is ignored.  Blocks below 64 samples have no
+ * candidates: their frames are the unflagged call's.  Composes with WASTED_BITS (the shifted rows go through the same
+ * batches), use_direct_mse and every summation-order flag.  No host synchronisation of its own.  The packers need no
+ * flag: they write marked records of any origin (see "The packers' domain" below). */
+#define FLACENC_HIP_FLAG_RICE_ESCAPE 16384u
+
 /* where the caller's sample / output buffers live */
 #define FLACENC_HIP_MEM_HOST 0
 #define FLACENC_HIP_MEM_DEVICE 1
@@ -599,8 +641,10 @@ int flacenc_hip_fixed_lpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_f
  *   - a record describes a subframe the project's decoder reads (flacenc_hip_decode_frames);
  *   - order <= block_size >> rice_order: the first Rice partition may be empty (its parameter is still written),
  *     never negative;
- *   - rice_params[0 .. 2^rice_order) are 0..30 -- the record cannot express an escaped partition; the residual is
- *     written with 5-bit parameters exactly when one of them exceeds 14;
+ *   - rice_params[0 .. 2^rice_order) are Rice parameters 0..30, or 0x80 | w for a partition stored escaped at raw width
+ *     w = 0..31 (FLACENC_HIP_FLAG_RICE_ESCAPE above; bits 5 and 6 zero): the escape code at the parameter width, the 5-bit
+ *     width, then the partition's residuals in two's complement at w bits each; every residual of a marked partition
+ *     fits its width; the residual is written with 5-bit parameters exactly when a NON-escaped parameter exceeds 14;
  *   - shift 0..15 and precision 1..15 (LPC); a Fixed record holds FIXED_LPC_COEFS[order], shift 0, precision 0;
  *   - every sample fits its width (bits_per_sample, + 1 for the side role, - pad[c] wasted bits) and every residual
  *     an int32; the residual row is that of the shifted signal, its first `order` slots are not read;

@@ -67,6 +67,10 @@ pub const FLAG_ORDER_GUESS: u32 = 4096;
 /// `quant_precision` down to the handle's floor (`flacenc_hip_set_precision_floor`, 5 on a fresh handle) and the
 /// shortest is kept.  The records stay ordinary `SubFrame::Lpc` at the chosen precision.  The drop-in never sets it.
 pub const FLAG_PRECISION_SEARCH: u32 = 8192;
+/// `FLACENC_HIP_FLAG_RICE_ESCAPE`: a Rice partition may be stored escaped (RFC 9639 section 9.2.7.1: raw samples of a
+/// 5-bit-coded width) where that is strictly shorter; `rice_params[q] = 0x80 | width` marks such a partition.  The
+/// frame-level calls take the candidate batches and the deciding kernels for every shape under this flag.
+pub const FLAG_RICE_ESCAPE: u32 = 16384;
 pub const DEFAULT_PRECISION_FLOOR: u32 = 5;
 /// Extra-window types of `FLAG_WINDOW_SEARCH` (the config's `window_type` keeps rejecting them), the most windows per
 /// subframe, and the unit of an extra window's `start` / `end`.

@@ -8,7 +8,7 @@ MD5 of the input (src/source.rs:406-428).  A short tail block is a second (one-f
 frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
-                                  [--window-search] [--order-guess [K]] [--precision-search [FLOOR]]
+                                  [--window-search] [--order-guess [K]] [--precision-search [FLOOR]] [--rice-escape]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -26,6 +26,9 @@ the histogram of the chosen orders is printed.  Not together with --order-search
 With --precision-search [FLOOR] (FLACENC_HIP_FLAG_PRECISION_SEARCH, libFLAC's -p) every LPC subframe is coded at each
 coefficient precision from 15 down to FLOOR (default 5) and the shortest kept; the histogram of the chosen precisions is
 printed.  Composes with the three searches above.
+With --rice-escape (FLACENC_HIP_FLAG_RICE_ESCAPE) a Rice partition is stored escaped -- raw samples of a 5-bit-coded
+width, 9 bits for a partition of digital silence -- where that is strictly shorter; how many partitions and frames
+escaped is printed.  The flag trades the fused kernels for the general path.  tools/decode_flac.py reads the result back.
 """
 import argparse
 import hashlib
@@ -133,6 +136,10 @@ def main():
                     metavar="FLOOR",
                     help="code every LPC subframe at each coefficient precision from 15 down to FLOOR, 1..15, default 5, "
                          "and keep the shortest (FLACENC_HIP_FLAG_PRECISION_SEARCH); composes with the other searches")
+    ap.add_argument("--rice-escape", action="store_true",
+                    help="store a Rice partition escaped (raw samples of a 5-bit-coded width) where that is strictly "
+                         "shorter (FLACENC_HIP_FLAG_RICE_ESCAPE: the general path for every shape); composes with every "
+                         "other switch")
     ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
     if args.order_guess and args.order_search:
@@ -145,6 +152,7 @@ def main():
     if args.precision_search < 0 or args.precision_search > 15:
         ap.error("--precision-search FLOOR must be in 1..15")
     flags |= _capi.FLAG_PRECISION_SEARCH if args.precision_search else 0
+    flags |= _capi.FLAG_RICE_ESCAPE if args.rice_escape else 0
     handle = _capi.Handle(0)
     if args.precision_search:
         handle.set_precision_floor(args.precision_search)
@@ -185,6 +193,11 @@ def main():
         orders = res["lpc"]["order"][res["kind"] == 3]
         hist = np.bincount(orders, minlength=args.lpc_order + 1)
         print("chosen LPC orders: " + ", ".join(f"{o}: {int(c)}" for o, c in enumerate(hist) if c))
+    if args.rice_escape:
+        coded = (res["kind"] >= 2)[..., None] & (np.arange(256) < (1 << res["lpc"]["rice_order"].astype(np.int64))[..., None])
+        marks = coded & ((res["lpc"]["rice_params"] & 0x80) != 0)
+        print(f"escaped partitions: {int(marks.sum())} of {int(coded.sum())}, in {int(marks.any(axis=(1, 2)).sum())} of "
+              f"{nf} frames")
     if args.precision_search:
         hist = np.bincount(res["lpc"]["precision"][res["kind"] == 3], minlength=16)
         print("chosen LPC precisions: " + ", ".join(f"{q}: {int(c)}" for q, c in enumerate(hist) if c))
