@@ -66,7 +66,8 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_set_adaptive_order", "flacenc_hip_debug_adaptive_state",
                  "flacenc_hip_debug_set_order_guess_trace", "flacenc_hip_debug_set_stream_chunk",
                  "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers",
-                 "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan")
+                 "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan",
+                 "flacenc_hip_debug_last_decode_streams_plan")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -121,6 +122,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_index_frames_async",
     "flacenc_hip_pack_le_bytes",
     "flacenc_hip_decode_pcm",
+    "flacenc_hip_decode_streams",
     "flacenc_hip_variable_bytes_bound",
     "flacenc_hip_variable_max_frames",
     "flacenc_hip_encode_variable_async",
@@ -163,6 +165,13 @@ PARAMS_DTYPE = np.dtype(
     align=True,
 )
 assert PARAMS_DTYPE.itemsize == 352
+
+
+# flacenc_hip_stream_desc (48 bytes): one stream of flacenc_hip_decode_streams
+STREAM_DESC_DTYPE = np.dtype([("offset", "<u8"), ("n_bytes", "<u8"), ("out_offset", "<u8"), ("out_capacity", "<u8"),
+                              ("channels", "<u4"), ("bits_per_sample", "<u4"), ("max_block_size", "<u4"),
+                              ("bytes_per_sample", "<u4")])
+assert STREAM_DESC_DTYPE.itemsize == 48
 
 
 class FrameConfig(C.Structure):
@@ -227,6 +236,18 @@ FRAME_RESULT_DTYPE = np.dtype(
     align=True,
 )
 assert FRAME_RESULT_DTYPE.itemsize == 752
+
+
+def stream_descs(streams) -> np.ndarray:
+    """A STREAM_DESC_DTYPE array from one, or from rows (offset, n_bytes, out_offset, out_capacity, channels,
+    bits_per_sample, max_block_size, bytes_per_sample); never empty memory, so that its address is not NULL."""
+    if isinstance(streams, np.ndarray) and streams.dtype == STREAM_DESC_DTYPE:
+        table = np.ascontiguousarray(streams)
+    else:
+        table = np.array([tuple(int(v) for v in row) for row in streams], STREAM_DESC_DTYPE)
+    if table.size == 0:
+        return np.zeros(1, STREAM_DESC_DTYPE)[:0]
+    return table
 
 
 class FlacencHipError(RuntimeError):
@@ -409,6 +430,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_decode_pcm.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp,
                                          C.c_uint64, vp]
     L.flacenc_hip_decode_pcm.restype = C.c_int
+    L.flacenc_hip_decode_streams.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, C.c_size_t, vp, C.c_uint64, vp, vp,
+                                             C.c_int]
+    L.flacenc_hip_decode_streams.restype = C.c_int
     L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -667,6 +691,13 @@ class Handle:
         v = [C.c_size_t(0) for _ in range(4)]
         self._check(self._hook("flacenc_hip_debug_last_decode_plan")(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
+
+    def debug_last_decode_streams_plan(self):
+        """(kernel launches, host synchronisations, host-device transfers, channel counts present) of the last
+        decode_streams call on this handle."""
+        plan = np.zeros(4, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_last_decode_streams_plan")(self._h, plan.ctypes.data))
+        return tuple(int(x) for x in plan)
 
     def synchronize(self):
         self._check(self._lib.flacenc_hip_synchronize(self._h))
@@ -1060,6 +1091,40 @@ class Handle:
                                               totals.ctypes.data)
         self._check(rc)
         return out[: int(totals[1]) * channels * width], [int(t) for t in totals]
+
+    def decode_streams(self, data, streams, max_frames: int, out: np.ndarray, totals: np.ndarray | None = None,
+                       check: bool = True):
+        """flacenc_hip_decode_streams on host arrays: `data` (bytes, or a uint8 array -- pinned or not) holds every
+        stream's frames, `streams` is a STREAM_DESC_DTYPE array (or rows of its eight fields), `out` the caller's uint8
+        buffer that holds every slot (written in place).  -> (totals uint64 [n_streams, 4], call totals [frames |
+        INDEX_ERROR, samples], the call's code); with check=False a failure is returned instead of raised."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table = stream_descs(streams)
+        if totals is None:
+            totals = np.zeros((len(table), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(table)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_streams(self._h, buf.ctypes.data, buf.size, table.ctypes.data, len(table),
+                                                  max_frames, out.ctypes.data, out.size, totals.ctypes.data,
+                                                  call.ctypes.data, MEM_HOST)
+        if check:
+            self._check(rc)
+        return totals, [int(call[0]), int(call[1])], rc
+
+    def decode_streams_device(self, bytes_ptr: int, n_bytes: int, streams, max_frames: int, out_ptr: int,
+                              out_bytes: int, totals_ptr: int, check: bool = True):
+        """flacenc_hip_decode_streams on device pointers (the table stays host memory); blocks on the handle's stream.
+        -> (call totals, the call's code)."""
+        table = stream_descs(streams)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_streams(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
+                                                  max_frames, out_ptr or None, out_bytes, totals_ptr or None,
+                                                  call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
 
     # -- block-size search: variable-blocking streams ---------------------------------------------------------
     def encode_variable(self, frames, bits_per_sample: int, cfg: FrameConfig, levels: int, total_samples: int | None = None,

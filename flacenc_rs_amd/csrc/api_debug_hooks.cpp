@@ -89,4 +89,10 @@ int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_byt
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_last_decode_streams_plan(flacenc_hip_handle* h, uint64_t plan[4]) {
+  if (!h || !plan) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  for (int i = 0; i < 4; ++i) plan[i] = h->last_streams_plan[i];
+  return FLACENC_HIP_OK;
+}
+
 }  // extern "C"

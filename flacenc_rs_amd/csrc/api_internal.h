@@ -14,6 +14,7 @@
 //   api_stream.cpp       the streaming host path (flacenc_hip_encode_pcm)
 //   api_decode.cpp       decode / verify / index
 //   api_decode_stream.cpp  rows to packed PCM (flacenc_hip_pack_le_bytes), the streaming way back (flacenc_hip_decode_pcm)
+//   flac_decode_streams.cpp  a batch of streams to packed PCM (flacenc_hip_decode_streams): its kernels and the call
 //   api_variable.cpp     the block-size search
 //   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
 #ifndef FLACENC_HIP_API_INTERNAL_H_
@@ -203,6 +204,9 @@ struct flacenc_hip_handle {
   // place of its rules (0: the rule), and the plan the last call ran
   size_t decode_window_override = 0, decode_group_override = 0;
   size_t last_decode_window = 0, last_decode_windows = 0, last_decode_group = 0, last_decode_groups = 0;
+  // test hook, see flacenc_hip_debug_last_decode_streams_plan: kernel launches, host synchronisations, host-device
+  // transfers and channel classes of the last flacenc_hip_decode_streams call
+  uint64_t last_streams_plan[4] = {0, 0, 0, 0};
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch

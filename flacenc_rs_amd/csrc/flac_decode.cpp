@@ -407,6 +407,24 @@ hipError_t launch_decode_frames(const uint8_t* bytes, uint64_t n_bytes, const ui
   return hipGetLastError();
 }
 
+// what the batch index (flac_decode_streams.cpp) shares with this one: neither kernel looks at stream parameters
+hipError_t launch_frame_crc16(const uint8_t* bytes, const uint64_t* offsets, uint32_t n, const uint32_t* n_dev,
+                              void* recs, hipStream_t stream) {
+  hipLaunchKernelGGL(crc16_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, stream, bytes, offsets, n, n_dev,
+                     static_cast<FrameRec*>(recs));
+  return hipGetLastError();
+}
+
+hipError_t launch_jump_levels(uint32_t* jump, const uint32_t* n_dev, size_t capacity, hipStream_t stream) {
+  const uint32_t cap = static_cast<uint32_t>(capacity), levels = jump_levels(capacity);
+  for (uint32_t k = 1; k < levels; ++k)
+    hipLaunchKernelGGL(jump_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream,
+                       jump + static_cast<size_t>(k - 1) * cap, jump + static_cast<size_t>(k) * cap, n_dev, cap);
+  return hipGetLastError();
+}
+
+uint32_t index_jump_levels(size_t capacity) { return jump_levels(capacity); }
+
 size_t index_candidate_capacity(size_t max_frames) { return max_frames + max_frames / 4 + 4096; }
 
 size_t index_scratch_bytes(uint64_t n_bytes, size_t capacity) {

@@ -27,6 +27,14 @@ hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t 
                                size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
                                void* scratch, size_t capacity, hipStream_t stream);
 
+// Pieces of the index for the batch index of flac_decode_streams.cpp.  The CRC-16 of frames offsets[0 .. min(n, *n_dev))
+// whose skim record (flacdec::FrameRec recs[]) has status 0: FRAME_CRC into the record where it fails.  The jump levels
+// 1 .. index_jump_levels(capacity) - 1 from level 0 (jump[0 .. capacity)), level k at jump + k * capacity.
+hipError_t launch_frame_crc16(const uint8_t* bytes, const uint64_t* offsets, uint32_t n, const uint32_t* n_dev,
+                              void* recs, hipStream_t stream);
+hipError_t launch_jump_levels(uint32_t* jump, const uint32_t* n_dev, size_t capacity, hipStream_t stream);
+uint32_t index_jump_levels(size_t capacity);
+
 }  // namespace flacenc_hip
 
 #endif  // FLACENC_FLAC_DECODE_H_

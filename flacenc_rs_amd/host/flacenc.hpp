@@ -1204,5 +1204,31 @@ inline DecodedPcm decode_pcm(HipContext& gpu, const uint8_t* bytes, size_t n_byt
   return r;
 }
 
+// A library of short files in one call (flacenc_hip_decode_streams on host memory): stream s is bytes[offset, offset +
+// n_bytes) and decodes into out[out_offset, out_offset + out_capacity); the result for each is what decode_pcm gives for
+// it alone.  Throws when the device fails and when the batch holds more frames than max_frames (nothing was written
+// then; call again with more).
+inline std::vector<DecodedPcm> decode_streams(HipContext& gpu, const uint8_t* bytes, size_t n_bytes,
+                                              const std::vector<flacenc_hip_stream_desc>& streams, size_t max_frames,
+                                              uint8_t* out, size_t out_bytes) {
+  std::vector<uint64_t> totals(4 * streams.size() + 4, 0);
+  uint64_t call[2] = {0, 0};
+  const flacenc_hip_stream_desc none{};
+  const int rc = flacenc_hip_decode_streams(gpu.get(), bytes, n_bytes, streams.empty() ? &none : streams.data(),
+                                            streams.size(), max_frames, out, out_bytes, totals.data(), call,
+                                            FLACENC_HIP_MEM_HOST);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  if (call[0] & FLACENC_HIP_INDEX_ERROR)
+    throw error::EncodeError(error::EncodeError::Device, "decode_streams: more frames than max_frames");
+  std::vector<DecodedPcm> r(streams.size());
+  for (size_t s = 0; s < streams.size(); ++s) {
+    r[s].frames = totals[4 * s];
+    r[s].samples = totals[4 * s + 1];
+    r[s].consumed = totals[4 * s + 2];
+    r[s].stop = static_cast<uint32_t>(totals[4 * s + 3]);
+  }
+  return r;
+}
+
 }  // namespace flacenc
 #endif  // FLACENC_HOST_FLACENC_HPP_

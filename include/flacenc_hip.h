@@ -979,6 +979,62 @@ int flacenc_hip_decode_pcm(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t
                            uint32_t bits_per_sample, uint32_t max_block_size, uint32_t bytes_per_sample, uint8_t* out,
                            uint64_t out_capacity, uint64_t totals[4]);
 
+/*
+ * A batch of streams in one call: what flacenc_hip_decode_pcm does for one stream, for every stream of a table, with a
+ * number of kernel launches, synchronisations and transfers that does not depend on the number of streams -- the call
+ * for a library of short files (a speech corpus, a sample pack, the tracks of an album), which otherwise pays the
+ * decoder's fixed latency once per file.
+ *   bytes, n_bytes   one buffer that holds every stream's frames.  Stream s is bytes [offset, offset + n_bytes) of it;
+ *                    spans ascend by offset and never overlap, gaps between them are legal and are never read as frames
+ *                    (whole .flac files back to back, each descriptor pointing behind that file's metadata blocks)
+ *   streams          n_streams descriptors (struct flacenc_hip_stream_desc, 48 bytes each), ALWAYS host memory, read
+ *                    before the call returns; channels, bits_per_sample, max_block_size and bytes_per_sample are the
+ *                    stream's, as for flacenc_hip_decode_pcm
+ *   out, out_bytes   one buffer for every stream's PCM: stream s owns the slot [out_offset, out_offset + out_capacity).
+ *                    Slots must be disjoint; the library does NOT check that (overlapping slots give unspecified bytes
+ *                    in the overlap, never a fault)
+ *   totals           [n_streams][4]: per stream what flacenc_hip_decode_pcm's totals say
+ *   call_totals      host memory in both kinds: [0] frames and [1] inter-channel samples decoded over all streams
+ *   memory_kind      FLACENC_HIP_MEM_HOST (pageable or flacenc_hip_host_alloc memory) or FLACENC_HIP_MEM_DEVICE: where
+ *                    bytes, out and totals live
+ * For every stream the bytes in its slot and totals[s][0..3] are exactly what flacenc_hip_decode_pcm gives when called on
+ * that stream alone with that slot as `out`: frames, samples, bytes consumed counted from the stream's own start, and the
+ * stop reason (0, NO_ROOM, CHAIN, or a frame's status bits: UNSUPPORTED for a block above the stream's max_block_size).
+ * A stream of 0 bytes gives all-zero totals.  Slot bytes beyond totals[s][1]*channels*bytes_per_sample and bytes of `out`
+ * in no slot are untouched; garbage gives a stop reason, never a fault, and changes nothing for the other streams.  The one
+ * difference: flacenc_hip_decode_pcm cuts its input into windows and therefore ends the chain at a frame longer than
+ * flacenc_hip_frame_bytes_bound; the batch sees every stream whole and has no such limit.
+ * max_frames bounds the frames of all chains together (at most 2^30; n_bytes / 9 + n_streams always suffices).
+ * FLACENC_HIP_INDEX_ERROR
+ * is set in call_totals[0] when the batch holds more chain frames than that, or more candidate headers than max_frames +
+ * max_frames / 4 + 4096 (the rule of flacenc_hip_index_frames_async): then nothing is written to `out`, every stream's
+ * totals are zero and the caller retries with a larger max_frames.
+ * n_streams == 0 is OK.  FLACENC_HIP_ERR_BAD_ARGUMENT: a null pointer, n_streams above 2^24, max_frames above 2^30, spans
+ * that do not ascend, overlap or reach past n_bytes, a slot that reaches past out_bytes, channels outside 1..8,
+ * max_block_size outside 1..65536, bytes_per_sample above 4 or below ceil(bits_per_sample / 8);
+ * FLACENC_HIP_ERR_UNSUPPORTED: a bits_per_sample outside 4..24.  In every error case nothing is written.
+ * The call blocks and runs on the handle's stream, all of it enqueued on that one stream; there is no stream-taking form
+ * yet.  Device scratch grows with n_bytes, max_frames and (host memory) the decoded size: a batch larger than device
+ * memory is the caller's to split, and the call returns FLACENC_HIP_ERR_DEVICE when scratch cannot be had.  Host results
+ * reach their slots through one transfer into pinned staging and the handle's host threads
+ * (flacenc_hip_set_host_threads), not through a transfer per stream.
+ * (`streams` is declared const void*: the descriptor is plain data every binding lays out itself.)
+ */
+struct flacenc_hip_stream_desc {
+  uint64_t offset;           /* the stream's frames: bytes [offset, offset + n_bytes) of `bytes` */
+  uint64_t n_bytes;
+  uint64_t out_offset;       /* its PCM slot: bytes [out_offset, out_offset + out_capacity) of `out` */
+  uint64_t out_capacity;
+  uint32_t channels;         /* as for flacenc_hip_decode_pcm */
+  uint32_t bits_per_sample;
+  uint32_t max_block_size;
+  uint32_t bytes_per_sample;
+};
+typedef struct flacenc_hip_stream_desc flacenc_hip_stream_desc;
+int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                               size_t n_streams, size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
+                               uint64_t call_totals[2], int memory_kind);
+
 /* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
 /*
  * Each region coded at the block size that compresses it best (BASELINE config 5's "beat-search block sizing"; the

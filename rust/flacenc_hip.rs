@@ -405,6 +405,12 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, channels: u32, bits_per_sample: u32, max_block_size: u32,
         bytes_per_sample: u32, out: *mut u8, out_capacity: u64, totals: *mut u64,
     ) -> c_int;
+    /// A batch of streams in one call: `streams` points at `n_streams` `StreamDesc` in host memory; `totals` is
+    /// `[n_streams][4]` as for `flacenc_hip_decode_pcm`, `call_totals` = frames (| `INDEX_ERROR`) and samples of the call.
+    pub fn flacenc_hip_decode_streams(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
+        out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
     /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
     /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.
@@ -578,6 +584,21 @@ impl Gpu {
     }
 }
 
+/// `struct flacenc_hip_stream_desc` (48 bytes): one stream of `flacenc_hip_decode_streams` -- its frames are
+/// `bytes[offset..offset + n_bytes]`, its PCM slot `out[out_offset..out_offset + out_capacity]`.
+#[repr(C)]
+#[derive(Clone, Copy, PartialEq, Eq, Debug, Default)]
+pub struct StreamDesc {
+    pub offset: u64,
+    pub n_bytes: u64,
+    pub out_offset: u64,
+    pub out_capacity: u64,
+    pub channels: u32,
+    pub bits_per_sample: u32,
+    pub max_block_size: u32,
+    pub bytes_per_sample: u32,
+}
+
 /// What `Gpu::decode_pcm` gives back: how far the call got and why it stopped (`flacenc_hip_decode_pcm`'s `totals`).
 #[derive(Clone, Copy, PartialEq, Eq, Debug)]
 pub struct DecodedPcm {
@@ -609,6 +630,32 @@ impl Gpu {
             return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_decode_pcm failed")));
         }
         Ok(DecodedPcm { frames: totals[0], samples: totals[1], consumed: totals[2], stop: totals[3] as u32 })
+    }
+}
+
+impl Gpu {
+    /// Decodes every stream of `streams` (spans of `bytes` in ascending order, disjoint slots of `out`) with
+    /// `flacenc_hip_decode_streams` on host memory: per stream what `decode_pcm` gives for it alone.  `Err` also when
+    /// the batch holds more frames than `max_frames` (`INDEX_ERROR`: nothing was written; retry with more).
+    pub fn decode_streams(
+        &mut self, bytes: &[u8], streams: &[StreamDesc], max_frames: usize, out: &mut [u8],
+    ) -> Result<Vec<DecodedPcm>, EncodeError> {
+        let mut totals = vec![0u64; 4 * streams.len().max(1)];
+        let mut call = [0u64; 2];
+        let rc = unsafe {
+            flacenc_hip_decode_streams(
+                self.0, bytes.as_ptr(), bytes.len() as u64, streams.as_ptr() as *const c_void, streams.len(), max_frames,
+                out.as_mut_ptr(), out.len() as u64, totals.as_mut_ptr(), call.as_mut_ptr(), MEM_HOST,
+            )
+        };
+        if rc != OK || call[0] & INDEX_ERROR != 0 {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_decode_streams failed")));
+        }
+        Ok((0..streams.len())
+            .map(|s| DecodedPcm {
+                frames: totals[4 * s], samples: totals[4 * s + 1], consumed: totals[4 * s + 2], stop: totals[4 * s + 3] as u32,
+            })
+            .collect())
     }
 }
 

@@ -64,6 +64,38 @@ def decode(data: bytes, handle):
     return pcm, info
 
 
+def wav_payload(pcm, bps):
+    """The call's PCM bytes as the data of an 8 / 16 / 24-bit PCM WAV."""
+    width = (bps + 7) // 8
+    if 8 * width == bps and width > 1:
+        return pcm.tobytes()   # 16 / 24 bits: the WAV payload as it stands
+    # a depth that does not fill its bytes sits in the high bits of the WAV sample; 8-bit WAV is offset binary
+    wide = np.zeros((pcm.size // width, 4), np.uint8)
+    wide[:, :width] = pcm.reshape(-1, width)
+    v = (wide.view("<i4").reshape(-1) << (32 - 8 * width)) >> (32 - 8 * width)   # sign-extend
+    shifted = v.astype(np.int64) << (8 * width - bps)
+    if width == 1:
+        return (shifted + 128).astype(np.uint8).tobytes()
+    return np.ascontiguousarray(shifted, "<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :width].tobytes()
+
+
+def write_wav(path, pcm, info):
+    with wave.open(path, "wb") as w:
+        w.setnchannels(info["channels"])
+        w.setsampwidth((info["bits_per_sample"] + 7) // 8)
+        w.setframerate(info["sample_rate"])
+        w.writeframes(wav_payload(pcm, info["bits_per_sample"]))
+
+
+def md5_status(pcm, info):
+    """The bytes the call returns are the ones the STREAMINFO MD5 is defined over; an all-zero digest means unchecked."""
+    if info["md5"] == bytes(16):
+        return "MD5 not checked (STREAMINFO has none)"
+    if hashlib.md5(pcm).digest() == info["md5"]:
+        return "MD5 OK"
+    return None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("input")
@@ -77,29 +109,10 @@ def main():
     samples = pcm.size // (info["channels"] * width)
     if info["total_samples"] and samples != info["total_samples"]:
         raise SystemExit(f"decoded {samples} samples, STREAMINFO says {info['total_samples']}")
-    if info["md5"] == bytes(16):
-        status = "MD5 not checked (STREAMINFO has none)"
-    elif hashlib.md5(pcm).digest() == info["md5"]:   # the bytes the call returns are the ones the MD5 is defined over
-        status = "MD5 OK"
-    else:
+    status = md5_status(pcm, info)
+    if status is None:
         raise SystemExit("MD5 mismatch")
-    if 8 * width == bps and width > 1:
-        raw = pcm.tobytes()   # 16 / 24 bits: the WAV payload as it stands
-    else:
-        # a depth that does not fill its bytes sits in the high bits of the WAV sample; 8-bit WAV is offset binary
-        wide = np.zeros((pcm.size // width, 4), np.uint8)
-        wide[:, :width] = pcm.reshape(-1, width)
-        v = (wide.view("<i4").reshape(-1) << (32 - 8 * width)) >> (32 - 8 * width)   # sign-extend
-        shifted = v.astype(np.int64) << (8 * width - bps)
-        if width == 1:
-            raw = (shifted + 128).astype(np.uint8).tobytes()
-        else:
-            raw = np.ascontiguousarray(shifted, "<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :width].tobytes()
-    with wave.open(args.output, "wb") as w:
-        w.setnchannels(info["channels"])
-        w.setsampwidth(width)
-        w.setframerate(info["sample_rate"])
-        w.writeframes(raw)
+    write_wav(args.output, pcm, info)
     print(f"{samples} samples x {info['channels']} channels, {bps} bits: {status}")
 
 

@@ -1,0 +1,76 @@
+"""Many .flac files -> .wav files with ONE call into the GPU library (flacenc_hip_decode_streams).
+
+The host reads every file's metadata blocks (tools/decode_flac.py's parser), lays the files back to back in one buffer
+and points one descriptor per file behind that file's metadata; the call indexes, decodes and packs all of them with a
+number of launches that does not depend on how many there are.  The host then checks each STREAMINFO MD5 over the bytes
+of that file's slot and writes the WAVs.
+
+    python tools/decode_many.py a.flac b.flac ... --out-dir wavs
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from flacenc_rs_amd import _capi  # noqa: E402
+import decode_flac  # noqa: E402
+
+
+def decode_all(files, handle):
+    """files: the bytes of each .flac.  -> per file (PCM uint8 array, STREAMINFO); raises on a stream that stops early."""
+    table = np.zeros(len(files), _capi.STREAM_DESC_DTYPE)
+    infos, at, out_at = [], 0, 0
+    for i, data in enumerate(files):
+        info, start = decode_flac.read_metadata(data)
+        ch, bps = info["channels"], info["bits_per_sample"]
+        width = (bps + 7) // 8
+        n = len(data) - start
+        room = (info["total_samples"] or (n // 9 + 1) * info["max_block_size"]) * ch * width
+        table[i] = (at + start, n, out_at, room, ch, bps, info["max_block_size"], width)
+        infos.append(info)
+        at += len(data)
+        out_at += room
+    everything = np.frombuffer(b"".join(files), np.uint8)
+    out = np.empty(max(1, out_at), np.uint8)
+    max_frames = len(everything) // 9 + len(files)   # a frame is at least 9 bytes
+    totals, call, _ = handle.decode_streams(everything, table, max_frames, out)
+    if call[0] & _capi.INDEX_ERROR:
+        raise ValueError("more frames or candidate headers than the call was given room for")
+    results = []
+    for i, info in enumerate(infos):
+        frames, samples, consumed, why = (int(v) for v in totals[i])
+        if why:
+            name = decode_flac.STOP_NAMES.get(why, f"decode status {why:#x}")
+            raise ValueError(f"file {i}: frame {frames} at byte {int(table[i]['offset']) - sum(map(len, files[:i])) + consumed}: {name}")
+        lo = int(table[i]["out_offset"])
+        results.append((out[lo:lo + samples * info["channels"] * int(table[i]["bytes_per_sample"])], info))
+    return results
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("inputs", nargs="+")
+    ap.add_argument("--out-dir", required=True)
+    args = ap.parse_args()
+    os.makedirs(args.out_dir, exist_ok=True)
+    files = [open(p, "rb").read() for p in args.inputs]
+    with _capi.Handle(0) as h:
+        results = decode_all(files, h)
+    for path, (pcm, info) in zip(args.inputs, results):
+        width = (info["bits_per_sample"] + 7) // 8
+        samples = pcm.size // (info["channels"] * width)
+        if info["total_samples"] and samples != info["total_samples"]:
+            raise SystemExit(f"{path}: decoded {samples} samples, STREAMINFO says {info['total_samples']}")
+        status = decode_flac.md5_status(pcm, info)
+        if status is None:
+            raise SystemExit(f"{path}: MD5 mismatch")
+        wav = os.path.join(args.out_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")
+        decode_flac.write_wav(wav, pcm, info)
+        print(f"{wav}: {samples} samples x {info['channels']} channels, {info['bits_per_sample']} bits: {status}")
+
+
+if __name__ == "__main__":
+    main()
