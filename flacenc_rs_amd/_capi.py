@@ -123,6 +123,8 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_pack_le_bytes",
     "flacenc_hip_decode_pcm",
     "flacenc_hip_decode_streams",
+    "flacenc_hip_md5_spans",
+    "flacenc_hip_decode_streams_md5",
     "flacenc_hip_variable_bytes_bound",
     "flacenc_hip_variable_max_frames",
     "flacenc_hip_encode_variable_async",
@@ -433,6 +435,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_decode_streams.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, C.c_size_t, vp, C.c_uint64, vp, vp,
                                              C.c_int]
     L.flacenc_hip_decode_streams.restype = C.c_int
+    L.flacenc_hip_md5_spans.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_size_t, vp, C.c_int]
+    L.flacenc_hip_md5_spans.restype = C.c_int
+    L.flacenc_hip_decode_streams_md5.argtypes = L.flacenc_hip_decode_streams.argtypes + [vp]
+    L.flacenc_hip_decode_streams_md5.restype = C.c_int
     L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -1122,6 +1128,77 @@ class Handle:
         rc = self._lib.flacenc_hip_decode_streams(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
                                                   max_frames, out_ptr or None, out_bytes, totals_ptr or None,
                                                   call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
+
+    @staticmethod
+    def _span_table(offsets, lengths):
+        """(offsets, lengths) as uint64 arrays of one size; never empty memory, so that their addresses are not NULL."""
+        off = np.ascontiguousarray(offsets, np.uint64).reshape(-1)
+        ln = np.ascontiguousarray(lengths, np.uint64).reshape(-1)
+        assert off.shape == ln.shape
+        if off.size == 0:
+            return np.zeros(1, np.uint64)[:0], np.zeros(1, np.uint64)[:0]
+        return off, ln
+
+    def md5_spans(self, data, offsets, lengths, check: bool = True):
+        """flacenc_hip_md5_spans on host arrays: `data` (bytes, or a uint8 array -- pinned or not), span i =
+        data[offsets[i] : offsets[i] + lengths[i]] -> the digests, uint8 [n, 16] (hashlib.md5(span).digest() each); with
+        check=False -> (digests, the call's code)."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        off, ln = self._span_table(offsets, lengths)
+        digests = np.zeros((off.size, 16), np.uint8)
+        base = buf if buf.size else np.zeros(1, np.uint8)
+        rc = self._lib.flacenc_hip_md5_spans(self._h, base.ctypes.data, buf.size, off.ctypes.data, ln.ctypes.data,
+                                             off.size, np.zeros(16, np.uint8).ctypes.data if off.size == 0
+                                             else digests.ctypes.data, MEM_HOST)
+        if check:
+            self._check(rc)
+            return digests
+        return digests, rc
+
+    def md5_spans_device(self, bytes_ptr: int, n_bytes: int, offsets, lengths, digests_ptr: int,
+                         check: bool = True) -> int:
+        """flacenc_hip_md5_spans on device pointers (the span table stays host memory): 16 bytes per span to
+        digests_ptr; blocks on the handle's stream.  -> the call's code."""
+        off, ln = self._span_table(offsets, lengths)
+        rc = self._lib.flacenc_hip_md5_spans(self._h, bytes_ptr or None, n_bytes, off.ctypes.data, ln.ctypes.data,
+                                             off.size, digests_ptr or None, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return rc
+
+    def decode_streams_md5(self, data, streams, max_frames: int, out: np.ndarray, totals: np.ndarray | None = None,
+                           check: bool = True):
+        """flacenc_hip_decode_streams_md5 on host arrays: decode_streams plus, per stream, the MD5 of the bytes the call
+        wrote to its slot.  -> (totals, call totals, the call's code, digests uint8 [n_streams, 16])."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table = stream_descs(streams)
+        if totals is None:
+            totals = np.zeros((len(table), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(table)
+        call = np.zeros(2, np.uint64)
+        digests = np.zeros((max(1, len(table)), 16), np.uint8)
+        rc = self._lib.flacenc_hip_decode_streams_md5(self._h, buf.ctypes.data, buf.size, table.ctypes.data, len(table),
+                                                      max_frames, out.ctypes.data, out.size, totals.ctypes.data,
+                                                      call.ctypes.data, MEM_HOST, digests.ctypes.data)
+        if check:
+            self._check(rc)
+        return totals, [int(call[0]), int(call[1])], rc, digests[:len(table)]
+
+    def decode_streams_md5_device(self, bytes_ptr: int, n_bytes: int, streams, max_frames: int, out_ptr: int,
+                                  out_bytes: int, totals_ptr: int, digests_ptr: int, check: bool = True):
+        """flacenc_hip_decode_streams_md5 on device pointers (the table stays host memory): 16 digest bytes per stream to
+        digests_ptr; blocks on the handle's stream.  -> (call totals, the call's code)."""
+        table = stream_descs(streams)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_streams_md5(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
+                                                      max_frames, out_ptr or None, out_bytes, totals_ptr or None,
+                                                      call.ctypes.data, MEM_DEVICE, digests_ptr or None)
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc

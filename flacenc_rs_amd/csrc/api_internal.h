@@ -14,7 +14,8 @@
 //   api_stream.cpp       the streaming host path (flacenc_hip_encode_pcm)
 //   api_decode.cpp       decode / verify / index
 //   api_decode_stream.cpp  rows to packed PCM (flacenc_hip_pack_le_bytes), the streaming way back (flacenc_hip_decode_pcm)
-//   flac_decode_streams.cpp  a batch of streams to packed PCM (flacenc_hip_decode_streams): its kernels and the call
+//   flac_decode_streams.cpp  a batch of streams to packed PCM (flacenc_hip_decode_streams, _md5): its kernels and the call
+//   md5_streams.cpp      MD5 digests of a batch of spans (flacenc_hip_md5_spans): its kernel, launcher and the call
 //   api_variable.cpp     the block-size search
 //   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
 #ifndef FLACENC_HIP_API_INTERNAL_H_
@@ -168,6 +169,7 @@ struct flacenc_hip_handle {
   flacenc_hip::DeviceBuffer d_dec, d_dec_io, d_idx;  // frame decoder: skim records, host-pointer staging, index candidates
   // pack_le_bytes: the offsets when the caller wants none, host-pointer staging; decode_pcm: a window's index
   flacenc_hip::DeviceBuffer d_ppk_off, d_ppk_io, d_dpcm_idx;
+  flacenc_hip::DeviceBuffer d_md5;  // md5_spans: the span table and (host pointers) the digests
   // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
   flacenc_hip::DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
   // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
@@ -205,7 +207,7 @@ struct flacenc_hip_handle {
   size_t decode_window_override = 0, decode_group_override = 0;
   size_t last_decode_window = 0, last_decode_windows = 0, last_decode_group = 0, last_decode_groups = 0;
   // test hook, see flacenc_hip_debug_last_decode_streams_plan: kernel launches, host synchronisations, host-device
-  // transfers and channel classes of the last flacenc_hip_decode_streams call
+  // transfers and channel classes of the last flacenc_hip_decode_streams / flacenc_hip_decode_streams_md5 call
   uint64_t last_streams_plan[4] = {0, 0, 0, 0};
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
@@ -301,6 +303,14 @@ bool is_pinned(const void* p);
 int ensure_pinned(flacenc_hip_handle* h, void** slot, size_t* cap_field, size_t bytes);
 int ensure_stream_objects(flacenc_hip_handle* h);
 int ensure_copy_pool(flacenc_hip_handle* h, const char* what);
+
+// ---- md5_streams.cpp ----
+// One lane per span: the MD5 of bytes[offsets[i * offset_stride] .. + lengths[i]) to digests + 16 * slot[i] (lengths null:
+// every span empty; slot null: digests + 16 * i).  All pointers are device memory; one launch on `stream`, none for
+// n_spans == 0.
+hipError_t launch_md5_spans(const uint8_t* bytes, const uint64_t* offsets, uint32_t offset_stride,
+                            const uint64_t* lengths, const uint32_t* slot, uint32_t n_spans, uint8_t* digests,
+                            hipStream_t stream);
 
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);

@@ -14,9 +14,12 @@
 // a stereo pair on an even / odd lane pair, a wave at its largest order bucket.  A lane writes its channel's samples
 // straight into the packed interleaved little-endian PCM (the flacenc_hip_pack_le_bytes layout) at the frame's own
 // destination, channel count and width: no intermediate rows.
+// flacenc_hip_decode_streams_md5 is the same call with one more step behind the decode launches: one lane per stream
+// hashes the bytes the stream's lanes just wrote (md5_streams.cpp), on the device, before the PCM is downloaded.
 #include "api_internal.h"
 #include "flac_decode.h"
 #include "flac_decode_core.h"
+#include "md5_core.h"
 #include "stream_batch_core.h"
 
 namespace flacenc_hip {
@@ -417,20 +420,25 @@ struct Drain {
   }
 };
 
-}  // namespace
-}  // namespace flacenc_hip
+// the digest of the empty string, for the streams of a call that wrote nothing
+void empty_digests(uint8_t* digests, size_t n) {
+  uint8_t d[16];
+  md5core::md5_bytes(nullptr, 0, d);
+  for (size_t s = 0; s < n; ++s) std::memcpy(digests + 16 * s, d, 16);
+}
 
-using namespace flacenc_hip;
-
-extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
-                                          const void* streams, size_t n_streams, size_t max_frames, uint8_t* out,
-                                          uint64_t out_bytes, uint64_t* totals, uint64_t call_totals[2],
-                                          int memory_kind) {
+// flacenc_hip_decode_streams (md5 false: `digests` is not looked at, and the plan is the one that call has always had)
+// and flacenc_hip_decode_streams_md5: the same call, plus one lane per stream that hashes what the stream's lanes wrote
+// -- behind the decode launches, in front of the download, on the device copy of the PCM.
+int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                        size_t n_streams, size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
+                        uint64_t call_totals[2], int memory_kind, bool md5, uint8_t* digests) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   uint64_t* plan = h->last_streams_plan;  // launches, synchronisations, transfers, channel classes
   plan[0] = plan[1] = plan[2] = plan[3] = 0;
   if ((memory_kind != FLACENC_HIP_MEM_HOST && memory_kind != FLACENC_HIP_MEM_DEVICE) || !bytes || !streams || !out ||
-      !totals || !call_totals || n_streams > streambatch::MAX_STREAMS || max_frames > streambatch::MAX_FRAMES ||
+      !totals || !call_totals || (md5 && !digests) || n_streams > streambatch::MAX_STREAMS ||
+      max_frames > streambatch::MAX_FRAMES ||
       n_bytes > (static_cast<uint64_t>(0xFFFFFFFFu) << 12)) {
     h->last_error = "decode_streams: null pointer, unknown memory kind, more than 2^24 streams, max_frames above 2^30 or "
                     "n_bytes >= 16 TiB";
@@ -457,8 +465,10 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   // ---- the table on its way to the device: the descriptors and the slot order (streams sorted by channel count) ----
   const size_t table_bytes = n_streams * sizeof(Desc) + n_streams * 4;
   const size_t result_words = M_WORDS + (n_streams + 1) + (host ? 4 * n_streams + (n_streams + 1) : 0);
-  if ((rc = ensure_pinned(h, h->pin_meta, &h->pin_meta_cap,
-                          table_bytes > result_words * 8 ? table_bytes : result_words * 8)) != FLACENC_HIP_OK)
+  // (host memory, md5: the digests come down into the same pinned slot, behind the results)
+  const size_t result_bytes = result_words * 8 + (host && md5 ? n_streams * 16 : 0);
+  if ((rc = ensure_pinned(h, h->pin_meta, &h->pin_meta_cap, table_bytes > result_bytes ? table_bytes : result_bytes)) !=
+      FLACENC_HIP_OK)
     return rc;
   Desc* p_desc = static_cast<Desc*>(h->pin_meta[1]);
   uint32_t* p_perm = reinterpret_cast<uint32_t*>(p_desc + n_streams);
@@ -497,6 +507,7 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   const size_t o_swhy = take(n_streams * 4), o_sacc = take(n_streams * 4), o_sbytes = take(n_streams * 8);
   const size_t o_fnode = take(F * 4), o_fslot = take(F * 4), o_fpcm = take(F * 8), o_fbad = take(F * 8);
   const size_t o_pcm = take((F + 1) * 8), o_bad = take((F + 1) * 8);
+  const size_t o_digests = host && md5 ? take(n_streams * 16) : 0;
   if ((rc = ensure(h, h->d_idx, need)) != FLACENC_HIP_OK) return rc;
   char* S = static_cast<char*>(h->d_idx.ptr);
   uint32_t* counters = reinterpret_cast<uint32_t*>(S + o_counters);
@@ -524,6 +535,7 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   uint64_t* f_bad = reinterpret_cast<uint64_t*>(S + o_fbad);
   uint64_t* pcm = reinterpret_cast<uint64_t*>(S + o_pcm);
   uint64_t* bad = reinterpret_cast<uint64_t*>(S + o_bad);
+  uint8_t* d_digests = host ? reinterpret_cast<uint8_t*>(S + o_digests) : digests;
 
   // ---- the input ----
   const uint8_t* d_bytes = bytes;
@@ -586,6 +598,12 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   if (host)
     SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, s_bytes, nullptr, nullptr, static_cast<uint64_t>(ns),
               nullptr, where, nullptr);
+  // device memory: should the call end with INDEX_ERROR, every digest is the empty string's.  Written now, in front of
+  // the one synchronisation that path has; the launch behind the decode overwrites it.  (Host memory: the host writes.)
+  if (md5 && !host) {
+    HIP_TRY(h, launch_md5_spans(d_bytes, nullptr, 0, nullptr, nullptr, ns, d_digests, st));
+    ++plan[0];
+  }
   HIP_TRY(h, hipGetLastError());
   const uint64_t* r_meta = static_cast<const uint64_t*>(h->pin_meta[0]);
   HIP_TRY(h, hipMemcpyAsync(h->pin_meta[0], meta, result_words * 8, hipMemcpyDeviceToHost, st));
@@ -597,6 +615,7 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   const uint64_t* r_where = r_totals + 4 * n_streams;
   if (r_meta[M_ERR]) {  // nothing reaches `out`; every stream's totals are zero (the kernel wrote them so)
     if (host) std::memcpy(totals, r_totals, n_streams * 32);
+    if (host && md5) empty_digests(digests, n_streams);
     call_totals[0] = FLACENC_HIP_INDEX_ERROR;
     drain.armed = false;
     return FLACENC_HIP_OK;
@@ -619,6 +638,19 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
   }
 #undef SB_LAUNCH
   HIP_TRY(h, hipGetLastError());
+  if (md5) {
+    // stream s wrote s_bytes[s] bytes from d_out + where[s] (the compact staging) resp. + its out_offset, the third of
+    // the descriptor's six words
+    const uint64_t* first = where ? where : reinterpret_cast<const uint64_t*>(descs) + 2;
+    HIP_TRY(h, launch_md5_spans(d_out, first, where ? 1u : static_cast<uint32_t>(sizeof(Desc) / 8), s_bytes, nullptr, ns,
+                                d_digests, st));
+    ++plan[0];
+    if (host) {
+      HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(h->pin_meta[0]) + result_words * 8, d_digests, n_streams * 16,
+                                hipMemcpyDeviceToHost, st));
+      ++plan[2];
+    }
+  }
   if (host) {
     // one transfer of the streams' PCM back to back into pinned staging, then every stream to its slot on the host
     if ((rc = ensure_pinned(h, h->pin_out, &h->pin_out_cap, static_cast<size_t>(pcm_bytes))) != FLACENC_HIP_OK) return rc;
@@ -636,8 +668,30 @@ extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* 
       if (n) h->copy_pool->copy(out + table[s].out_offset, staged + r_where[s], static_cast<size_t>(n));
     }
     std::memcpy(totals, r_totals, n_streams * 32);
+    if (md5) std::memcpy(digests, static_cast<const char*>(h->pin_meta[0]) + result_words * 8, n_streams * 16);
   }
   call_totals[0] = r_meta[M_FRAMES];
   call_totals[1] = r_meta[M_SAMPLES];
   return FLACENC_HIP_OK;
+}
+
+}  // namespace
+}  // namespace flacenc_hip
+
+using namespace flacenc_hip;
+
+extern "C" int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
+                                          const void* streams, size_t n_streams, size_t max_frames, uint8_t* out,
+                                          uint64_t out_bytes, uint64_t* totals, uint64_t call_totals[2],
+                                          int memory_kind) {
+  return decode_streams_impl(h, bytes, n_bytes, streams, n_streams, max_frames, out, out_bytes, totals, call_totals,
+                             memory_kind, false, nullptr);
+}
+
+extern "C" int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
+                                              const void* streams, size_t n_streams, size_t max_frames, uint8_t* out,
+                                              uint64_t out_bytes, uint64_t* totals, uint64_t call_totals[2],
+                                              int memory_kind, uint8_t* digests) {
+  return decode_streams_impl(h, bytes, n_bytes, streams, n_streams, max_frames, out, out_bytes, totals, call_totals,
+                             memory_kind, true, digests);
 }

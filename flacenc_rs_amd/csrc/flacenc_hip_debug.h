@@ -78,7 +78,7 @@ int flacenc_hip_debug_set_decode_plan(flacenc_hip_handle* h, size_t window_bytes
  * no window (n_bytes == 0, rejected arguments) leaves zeros.  Any pointer may be NULL. */
 int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_bytes, size_t* n_windows,
                                        size_t* group_frames, size_t* n_groups);
-/* What the last flacenc_hip_decode_streams call on the handle did: plan[0] kernel launches, plan[1] host
+/* What the last flacenc_hip_decode_streams (or flacenc_hip_decode_streams_md5) call on the handle did: plan[0] kernel launches, plan[1] host
  * synchronisations, plan[2] host-device transfers, plan[3] channel counts present in its table.  None of the first three
  * depends on the number of streams.  Zeros after a call that was rejected or had no stream. */
 int flacenc_hip_debug_last_decode_streams_plan(flacenc_hip_handle* h, uint64_t plan[4]);

@@ -16,7 +16,8 @@
 // The controller logic (`encode_subframe` src/coding.rs:384-418, `try_stereo_coding`
 // :469-527) runs on the host exactly as in the reference; every `estimated_qlpc` call is served
 // by the GPU through flacenc_hip_*_qlpc_batch.  There is no CPU implementation of the path here.
-// Not mirrored (out of scope): bit writer, container metadata, MD5, serde.
+// Not mirrored (out of scope): bit writer, container metadata, a single stream's MD5, serde.
+// (The MD5 digests of a BATCH of streams come from the device: md5_spans / decode_streams_md5 at the end of this file.)
 // Fixed-LPC candidate (`fixed_lpc`, src/coding.rs:298): fused into the on-GPU controller where that
 // exists (flacenc_hip_encode_stereo_frames: 2 channels, block 4096, lpc_order <= 12,
 // ApproxEnt.partitions a power of two), served by flacenc_hip_fixed_lpc_batch everywhere else.
@@ -415,7 +416,9 @@ struct StreamInfo {  // datatype.rs:435-445, defaults :476-479
   size_t min_block_size = 0xFFFF, max_block_size = 0;
   size_t min_frame_size = 0xFFFFFFFFu, max_frame_size = 0;
   uint64_t total_samples = 0;
-  uint8_t md5_digest[16] = {0};  // all zero = "not computed" (MD5 is host work outside this mirror)
+  // all zero = "not computed": one stream's MD5 is host work outside this mirror; a host that encodes many files gets
+  // all their digests in one call from md5_spans (below)
+  uint8_t md5_digest[16] = {0};
   // update_frame_info, datatype.rs:514-523 (total_samples is counted by the encoder loop here)
   void update_frame_info(const Frame& f) {
     min_block_size = std::min(min_block_size, f.block_size);
@@ -1220,6 +1223,51 @@ inline std::vector<DecodedPcm> decode_streams(HipContext& gpu, const uint8_t* by
   if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
   if (call[0] & FLACENC_HIP_INDEX_ERROR)
     throw error::EncodeError(error::EncodeError::Device, "decode_streams: more frames than max_frames");
+  std::vector<DecodedPcm> r(streams.size());
+  for (size_t s = 0; s < streams.size(); ++s) {
+    r[s].frames = totals[4 * s];
+    r[s].samples = totals[4 * s + 1];
+    r[s].consumed = totals[4 * s + 2];
+    r[s].stop = static_cast<uint32_t>(totals[4 * s + 3]);
+  }
+  return r;
+}
+
+// The MD5 digests of a batch of spans of host memory in one call (flacenc_hip_md5_spans): span i is bytes[offsets[i],
+// offsets[i] + lengths[i]), its digest the 16 bytes at 16 * i of the result -- what STREAMINFO stores.  One lane of the
+// device hashes one span: the call for the digests of many files, not of one (one span alone is faster on the host).
+inline std::vector<uint8_t> md5_spans(HipContext& gpu, const uint8_t* bytes, size_t n_bytes,
+                                      const std::vector<uint64_t>& offsets, const std::vector<uint64_t>& lengths) {
+  if (offsets.size() != lengths.size())
+    throw error::EncodeError(error::EncodeError::Device, "md5_spans: offsets and lengths differ in size");
+  std::vector<uint8_t> digests(16 * offsets.size() + 16, 0);
+  const uint64_t none = 0;
+  const uint8_t no_bytes = 0;
+  const int rc = flacenc_hip_md5_spans(gpu.get(), bytes ? bytes : &no_bytes, n_bytes, offsets.empty() ? &none : offsets.data(),
+                                       lengths.empty() ? &none : lengths.data(), offsets.size(), digests.data(),
+                                       FLACENC_HIP_MEM_HOST);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  digests.resize(16 * offsets.size());
+  return digests;
+}
+
+// decode_streams plus every stream's MD5 (flacenc_hip_decode_streams_md5): digests[16 * s ..] is the digest of the bytes
+// the call wrote to stream s's slot, computed on the device before the PCM left it -- for a stream that decoded to its
+// end (stop == 0) the value its STREAMINFO must hold.
+inline std::vector<DecodedPcm> decode_streams_md5(HipContext& gpu, const uint8_t* bytes, size_t n_bytes,
+                                                  const std::vector<flacenc_hip_stream_desc>& streams, size_t max_frames,
+                                                  uint8_t* out, size_t out_bytes, std::vector<uint8_t>& digests) {
+  std::vector<uint64_t> totals(4 * streams.size() + 4, 0);
+  uint64_t call[2] = {0, 0};
+  const flacenc_hip_stream_desc none{};
+  digests.assign(16 * streams.size() + 16, 0);
+  const int rc = flacenc_hip_decode_streams_md5(gpu.get(), bytes, n_bytes, streams.empty() ? &none : streams.data(),
+                                                streams.size(), max_frames, out, out_bytes, totals.data(), call,
+                                                FLACENC_HIP_MEM_HOST, digests.data());
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  if (call[0] & FLACENC_HIP_INDEX_ERROR)
+    throw error::EncodeError(error::EncodeError::Device, "decode_streams_md5: more frames than max_frames");
+  digests.resize(16 * streams.size());
   std::vector<DecodedPcm> r(streams.size());
   for (size_t s = 0; s < streams.size(); ++s) {
     r[s].frames = totals[4 * s];

@@ -834,7 +834,8 @@ int flacenc_hip_fill_le_bytes_async(flacenc_hip_handle* h, const uint8_t* bytes,
  *                  metadata blocks) and each frame's byte length; out_total = bytes written
  * `pcm` / `out` may be ordinary (pageable) memory -- then they are staged through the handle's pinned
  * buffers with a host memcpy -- or memory from flacenc_hip_host_alloc, which is transferred directly.
- * The MD5 of the input and STREAMINFO stay with the caller (src/source.rs:406-428).
+ * The MD5 of the input and STREAMINFO stay with the caller (src/source.rs:406-428); a caller that encodes many files
+ * gets all their digests in one call from flacenc_hip_md5_spans.
  */
 int flacenc_hip_encode_pcm_stereo(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const uint8_t* pcm,
                                   uint64_t total_samples, uint32_t bytes_per_sample, uint32_t bits_per_sample,
@@ -1034,6 +1035,44 @@ typedef struct flacenc_hip_stream_desc flacenc_hip_stream_desc;
 int flacenc_hip_decode_streams(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
                                size_t n_streams, size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
                                uint64_t call_totals[2], int memory_kind);
+
+/*
+ * MD5 digests (RFC 1321) of a batch of byte spans, one lane of the device per span: span i is bytes [offsets[i],
+ * offsets[i] + lengths[i]) of `bytes`, and its 16 digest bytes -- A, B, C, D, each little-endian: what STREAMINFO
+ * stores -- go to digests + 16*i.  The call for a host that needs one digest per file of a library: the STREAMINFO MD5 of
+ * every stream it encodes (flacenc_hip_encode_pcm leaves the MD5 with the caller) or decodes.
+ *   bytes, n_bytes    the buffer the spans lie in; digests: [n_spans][16].  Host (pageable or flacenc_hip_host_alloc) or
+ *                     device memory, chosen by memory_kind
+ *   offsets, lengths  n_spans entries each, ALWAYS host memory, read before the call returns.  Any byte alignment, any
+ *                     length, 0 included (the digest of the empty string).  Spans may overlap, repeat and leave gaps; a
+ *                     digest depends on no byte outside its span, and no byte outside a span is read
+ * n_spans == 0 is OK.  FLACENC_HIP_ERR_BAD_ARGUMENT: a null pointer, an unknown memory kind, n_spans above 2^24 or a span
+ * that reaches past n_bytes (offsets[i] + lengths[i] is checked without overflow); nothing is written then.
+ * The call blocks and runs on the handle's stream: one upload of the span table, one launch and, for host memory, one
+ * upload of `bytes` and one download of the digests, whatever n_spans is; there is no stream-taking form yet.
+ * MD5 is serial inside one span, so the rate comes from the number of spans: on an MI355X 2 048 spans of 320 KiB hash
+ * at 185 GB/s, ONE span at under 0.1 GB/s -- an order of magnitude slower than on one host core.  That case is out of
+ * scope: a single stream's MD5 stays host work, which is why flacenc_hip_decode_pcm has no MD5 form.
+ */
+int flacenc_hip_md5_spans(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets,
+                          const uint64_t* lengths, size_t n_spans, uint8_t* digests, int memory_kind);
+/*
+ * flacenc_hip_decode_streams plus the STREAMINFO check's digest of every stream, computed on the device from the PCM
+ * before it leaves it.  Bytes in `out`, totals, call_totals, error returns and untouched regions are exactly those of
+ * flacenc_hip_decode_streams on the same arguments.  In addition
+ *   digests           [n_streams][16], where totals live (memory_kind): digests[s] is the MD5 of the first
+ *                     totals[s][1]*channels*bytes_per_sample bytes of stream s's slot -- exactly the bytes the call
+ *                     wrote.  For bytes_per_sample == ceil(bits_per_sample / 8) that is the STREAMINFO digest of the
+ *                     decoded prefix: of the whole stream when totals[s][3] is 0
+ * A stream that stopped early (NO_ROOM, CHAIN, a frame's status) is digested over what was written; a stream of zero
+ * samples, and every stream of a call that ends with FLACENC_HIP_INDEX_ERROR, gets the digest of the empty string
+ * (d41d8cd98f00b204e9800998ecf8427e).  A null `digests` is FLACENC_HIP_ERR_BAD_ARGUMENT; in every error case nothing is
+ * written.  The digests cost at most two more launches and one more transfer than flacenc_hip_decode_streams and no
+ * further synchronisation, whatever n_streams is.  No stream-taking form yet.
+ */
+int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                                   size_t n_streams, size_t max_frames, uint8_t* out, uint64_t out_bytes,
+                                   uint64_t* totals, uint64_t call_totals[2], int memory_kind, uint8_t* digests);
 
 /* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
 /*

@@ -411,6 +411,19 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
         out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int,
     ) -> c_int;
+    /// MD5 digests of a batch of spans, one device lane per span: span `i` is `bytes[offsets[i]..offsets[i] + lengths[i]]`
+    /// (`offsets` / `lengths` always host memory), its 16 digest bytes go to `digests[16 * i..]`.  For batches: one span
+    /// alone is slower than one host core.
+    pub fn flacenc_hip_md5_spans(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, offsets: *const u64, lengths: *const u64, n_spans: usize,
+        digests: *mut u8, memory_kind: c_int,
+    ) -> c_int;
+    /// `flacenc_hip_decode_streams` plus `digests` (`[n_streams][16]`, where `totals` live): the MD5 of the bytes the
+    /// call wrote to each stream's slot -- the STREAMINFO digest of the decoded prefix.
+    pub fn flacenc_hip_decode_streams_md5(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
+        out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int, digests: *mut u8,
+    ) -> c_int;
     /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
     /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
     /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.

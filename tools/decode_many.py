@@ -3,9 +3,11 @@
 The host reads every file's metadata blocks (tools/decode_flac.py's parser), lays the files back to back in one buffer
 and points one descriptor per file behind that file's metadata; the call indexes, decodes and packs all of them with a
 number of launches that does not depend on how many there are.  The host then checks each STREAMINFO MD5 over the bytes
-of that file's slot and writes the WAVs.
+of that file's slot and writes the WAVs.  With --device-md5 the digests come out of the same call
+(flacenc_hip_decode_streams_md5: one lane of the device per file hashes the PCM before it leaves the device) and the host
+only compares 16 bytes per file; the lines printed and the exit codes are the same.
 
-    python tools/decode_many.py a.flac b.flac ... --out-dir wavs
+    python tools/decode_many.py a.flac b.flac ... --out-dir wavs [--device-md5]
 """
 import argparse
 import os
@@ -19,8 +21,18 @@ from flacenc_rs_amd import _capi  # noqa: E402
 import decode_flac  # noqa: E402
 
 
-def decode_all(files, handle):
-    """files: the bytes of each .flac.  -> per file (PCM uint8 array, STREAMINFO); raises on a stream that stops early."""
+def device_md5_status(digest, info):
+    """decode_flac.md5_status with the digest the device computed over the bytes of the file's slot."""
+    if info["md5"] == bytes(16):
+        return "MD5 not checked (STREAMINFO has none)"
+    if bytes(digest) == info["md5"]:
+        return "MD5 OK"
+    return None
+
+
+def decode_all(files, handle, device_md5=False):
+    """files: the bytes of each .flac.  -> per file (PCM uint8 array, STREAMINFO) and, with device_md5, the 16 digest
+    bytes of that PCM as the device computed them; raises on a stream that stops early."""
     table = np.zeros(len(files), _capi.STREAM_DESC_DTYPE)
     infos, at, out_at = [], 0, 0
     for i, data in enumerate(files):
@@ -36,7 +48,10 @@ def decode_all(files, handle):
     everything = np.frombuffer(b"".join(files), np.uint8)
     out = np.empty(max(1, out_at), np.uint8)
     max_frames = len(everything) // 9 + len(files)   # a frame is at least 9 bytes
-    totals, call, _ = handle.decode_streams(everything, table, max_frames, out)
+    if device_md5:
+        totals, call, _, digests = handle.decode_streams_md5(everything, table, max_frames, out)
+    else:
+        totals, call, _ = handle.decode_streams(everything, table, max_frames, out)
     if call[0] & _capi.INDEX_ERROR:
         raise ValueError("more frames or candidate headers than the call was given room for")
     results = []
@@ -46,7 +61,8 @@ def decode_all(files, handle):
             name = decode_flac.STOP_NAMES.get(why, f"decode status {why:#x}")
             raise ValueError(f"file {i}: frame {frames} at byte {int(table[i]['offset']) - sum(map(len, files[:i])) + consumed}: {name}")
         lo = int(table[i]["out_offset"])
-        results.append((out[lo:lo + samples * info["channels"] * int(table[i]["bytes_per_sample"])], info))
+        pcm = out[lo:lo + samples * info["channels"] * int(table[i]["bytes_per_sample"])]
+        results.append((pcm, info, digests[i].tobytes()) if device_md5 else (pcm, info))
     return results
 
 
@@ -54,17 +70,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("inputs", nargs="+")
     ap.add_argument("--out-dir", required=True)
+    ap.add_argument("--device-md5", action="store_true",
+                    help="take every file's MD5 from the device (flacenc_hip_decode_streams_md5), not from hashlib")
     args = ap.parse_args()
     os.makedirs(args.out_dir, exist_ok=True)
     files = [open(p, "rb").read() for p in args.inputs]
     with _capi.Handle(0) as h:
-        results = decode_all(files, h)
-    for path, (pcm, info) in zip(args.inputs, results):
+        results = decode_all(files, h, device_md5=args.device_md5)
+    for path, (pcm, info, *digest) in zip(args.inputs, results):
         width = (info["bits_per_sample"] + 7) // 8
         samples = pcm.size // (info["channels"] * width)
         if info["total_samples"] and samples != info["total_samples"]:
             raise SystemExit(f"{path}: decoded {samples} samples, STREAMINFO says {info['total_samples']}")
-        status = decode_flac.md5_status(pcm, info)
+        status = device_md5_status(digest[0], info) if args.device_md5 else decode_flac.md5_status(pcm, info)
         if status is None:
             raise SystemExit(f"{path}: MD5 mismatch")
         wav = os.path.join(args.out_dir, os.path.splitext(os.path.basename(path))[0] + ".wav")
