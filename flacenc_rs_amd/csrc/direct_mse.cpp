@@ -25,9 +25,13 @@
 // rounding to float) restated; checked against the host libm for y = -1.2 over every float in [0.0099, 1e6]
 // (223 M arguments, no mismatch, with and without fma contraction).
 //
-// PARITY: bit-equal to the oracle's restatement of the same algorithms (tests/test_gpu_direct_mse.py).  The
-// solver is a third-party crate outside the reference tree, the reference's tests of this path are qualitative:
-// beyond those tests (restated in tests/test_oracle_kat.py) this row is "parity unpinned".
+// PARITY: bit-equal to the oracle's restatement of the same algorithms, in every kernel form below and on worst-case
+// material (tests/test_gpu_direct_mse.py, tests/test_gpu_direct_mse_extremes.py).  The oracle is pinned by the
+// reference's tests of this path (qualitative; restated in tests/test_oracle_kat.py) and by the covariance method's
+// system built in exact integer arithmetic from the reference's source, which its solution must solve to a backward
+// error of 2^-4 (n + P^2) 2^-53 (tests/test_direct_mse_cases_cpu.py).  The solver is a third-party crate outside the
+// reference tree: what stays unpinned is bit-equality with nalgebra's Cholesky itself.
+// Blocks of n <= P samples never arrive: the entry points require block_size >= 64.
 #include "direct_mse.h"
 
 #include "flacenc_hip.h"

@@ -357,8 +357,12 @@ typedef struct flacenc_hip_handle flacenc_hip_handle;
  * mean absolute error (lpc_with_irls_mae, :814-850; steps is ignored unless use_direct_mse is set, as there).
  * The reference's stable `Verify` rejects both switches outside its `experimental` feature (config.rs:302-326);
  * this ABI follows the experimental build.  Its linear solver is nalgebra's (not part of the reference tree):
- * results equal the oracle's restatement of nalgebra 0.32's published algorithm bit for bit, which is as far
- * as this estimator can be pinned.  mae_optimization_steps is limited to FLACENC_HIP_MAX_MAE_STEPS. */
+ * results equal the oracle's restatement of nalgebra 0.32's published algorithm bit for bit, and the oracle's
+ * solution solves the covariance method's exact system to rounding; what cannot be pinned is bit-equality with
+ * nalgebra itself.  mae_optimization_steps is limited to
+ * FLACENC_HIP_MAX_MAE_STEPS.  A block of block_size <= lpc_order samples (nothing to estimate from, lpc.rs:542, :587)
+ * never reaches these estimators: the candidate batches answer FLACENC_HIP_ERR_BAD_ARGUMENT for every
+ * block_size < 64, the frame-level calls code such blocks as Constant or Verbatim (coding.rs:396). */
 typedef struct flacenc_hip_qlpc_config {
   uint32_t lpc_order;          /* 1..=24 (..=32 with ALLOW_ORDER_32) */
   uint32_t quant_precision;    /* 1..=15 */

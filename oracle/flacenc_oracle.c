@@ -705,9 +705,11 @@ int orc_certificate_bounds(const int32_t* signal, size_t n, const orc_qlpc_confi
 /* ------------------------------------------------------------------------ */
 /* experimental: covariance-method LPC ("direct MSE") and IRLS  */
 /*                                                                            */
-/* PARITY UNPINNED beyond the reference's own (mostly qualitative) tests: the */
-/* linear solver is nalgebra 0.32 (Cargo.toml:45, optional dependency, not    */
-/* under /root/reference).  Its published algorithm is restated below from    */
+/* Pinned by the reference's own (mostly qualitative) tests and by the exact   */
+/* system of the covariance method, which the solution below must solve to    */
+/* rounding (tests/test_direct_mse_cases_cpu.py).  UNPINNED: bit-equality     */
+/* with the linear solver itself, nalgebra 0.32 (Cargo.toml:45, optional      */
+/* dependency, not in the reference tree).  Its algorithm is restated from    */
 /* nalgebra 0.32.x src/linalg/cholesky.rs (Cholesky::new_internal, solve_mut),*/
 /* src/linalg/solve.rs (solve_lower_triangular_vector_unchecked_mut,          */
 /* xx_solve_lower_triangular_vector_unchecked_mut) and src/base/blas.rs       */
@@ -818,7 +820,13 @@ int orc_weighted_lpc_with_direct_mse(const int32_t* signal, size_t n, const orc_
                                      double* autocorr_out, double* gram_out, double* coefs_out) {
   size_t order = cfg->lpc_order;
   for (size_t i = 0; i < order; ++i) coefs_out[i] = 0.0;
-  if (order == 0 || n < order + 1) return ORC_STATUS_OK;
+  if (order == 0 || n < order + 1) {
+    /* both sums are empty (lpc.rs:542, :587): corr_coefs stays as :863-864 zeroed it, the matrix is 0, the loop loads
+     * it to the identity and the solution is 0 */
+    if (autocorr_out)
+      for (size_t i = 0; i <= order; ++i) autocorr_out[i] = 0.0;
+    return ORC_STATUS_OK;
+  }
   const float* xw = orc_windowed(signal, n, cfg);
   double corr[ORC_MAX_LPC_ORDER + 1];
   double gram[ORC_MAX_LPC_ORDER * ORC_MAX_LPC_ORDER];

@@ -48,7 +48,8 @@ extern "C" {
 #define ORC_ACORR_NIGHTLY 2   /* weighted_auto_correlation_simd, src/lpc.rs:510-531 (aligned buffer) */
 /* config::Qlpc::use_direct_mse (src/config.rs:280): covariance-method LPC, src/lpc.rs:853-903; bits 8.. of
  * acorr_order carry config::Qlpc::mae_optimization_steps (src/config.rs:285; IRLS, src/lpc.rs:814-850).
- * Experimental in the reference, solver from nalgebra: parity unpinned (see flacenc_oracle.c). */
+ * Experimental in the reference, solver from nalgebra: pinned to the covariance method's exact system, not to
+ * nalgebra's bits (see flacenc_oracle.c). */
 #define ORC_ACORR_DIRECT_MSE 3
 /* the kernels' own order as it is, without the certificate of orc_default_order_is_certified() (the product's
  * FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER): the fused kernel's lane order on its shapes, the chunk tree elsewhere */

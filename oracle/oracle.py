@@ -436,7 +436,8 @@ def lpc_from_autocorr(signal, cfg: QlpcConfig):
     return corr[: cfg.lpc_order + 1], coefs[: cfg.lpc_order], st
 
 
-# ---- experimental: covariance-method LPC and IRLS (src/lpc.rs:573-618, 814-903; parity unpinned) ----
+# ---- experimental: covariance-method LPC and IRLS (src/lpc.rs:573-618, 814-903; pinned to the exact system by
+# tests/test_direct_mse_cases_cpu.py, unpinned in bit-equality with nalgebra's Cholesky) ----
 def lagged_outer_prod_sum(order: int, signal, weight=None, wshift: int = 0) -> np.ndarray:
     """weighted_lagged_outer_prod_sum (src/lpc.rs:573-600) -> [order, order] f64"""
     x = np.ascontiguousarray(signal, np.float32)

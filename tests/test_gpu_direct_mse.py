@@ -4,8 +4,10 @@ perform_qlpc (src/coding.rs:333-351).
 
 The GPU must equal the oracle's restatement bit for bit: R[], the unquantised solution of the Cholesky solve, the
 quantised predictor, residual, Rice partition and bit counts, for every block shape and through every entry point.
-What the oracle itself is pinned by is the reference's own tests of this path (tests/test_oracle_kat.py); the
-solver is nalgebra's, outside the reference tree: beyond those tests this row is parity-unpinned."""
+What the oracle itself is pinned by is the reference's own tests of this path (tests/test_oracle_kat.py) and the
+covariance method's system in exact arithmetic, which its solution must solve (tests/test_direct_mse_cases_cpu.py);
+the solver is nalgebra's, outside the reference tree: what stays unpinned is bit-equality with nalgebra itself.
+Every kernel form on worst-case material: tests/test_gpu_direct_mse_extremes.py."""
 import numpy as np
 import pytest
 
