@@ -13,14 +13,17 @@
 //   flacenc::encode_with_fixed_block_size                src/coding.rs:645 (pub, lib.rs:162)
 //   Decode (feature "decode")                            src/component/decode.rs
 //
-// The controller logic (`encode_subframe` src/coding.rs:384-418, `try_stereo_coding`
-// :469-527) runs on the host exactly as in the reference; every `estimated_qlpc` call is served
-// by the GPU through flacenc_hip_*_qlpc_batch.  There is no CPU implementation of the path here.
-// Not mirrored (out of scope): bit writer, container metadata, a single stream's MD5, serde.
+// The controller logic (`encode_subframe` src/coding.rs:384-418, `try_stereo_coding` :469-527) and the frames' bit
+// writer run on the GPU (flacenc_hip_encode_stereo_frames / _encode_frames and the packers) for every group of frames,
+// the tail block below MIN_BLOCK_SIZE_FOR_PREDICTION and a config without predictors included: every Frame of a
+// returned Stream carries its bytes (except one too large for the device bit writer, FLACENC_HIP_ERR_UNSUPPORTED of
+// the packers), and Stream::to_bytes() is the reference's stream byte for byte but for the MD5 field.  There is no CPU
+// implementation of the path here.
+// Not mirrored (out of scope): host-side bit writer, container metadata, a single stream's MD5, serde.
 // (The MD5 digests of a BATCH of streams come from the device: md5_spans / decode_streams_md5 at the end of this file.)
-// Fixed-LPC candidate (`fixed_lpc`, src/coding.rs:298): fused into the on-GPU controller where that
-// exists (flacenc_hip_encode_stereo_frames: 2 channels, block 4096, lpc_order <= 12,
-// ApproxEnt.partitions a power of two), served by flacenc_hip_fixed_lpc_batch everywhere else.
+// Fixed-LPC candidate (`fixed_lpc`, src/coding.rs:298): part of the on-GPU controller -- fused into one kernel for
+// 2 channels, block 4096, lpc_order <= 12 and ApproxEnt.partitions a power of two, candidate batches and the deciding
+// kernel behind the same entry points everywhere else.
 #ifndef FLACENC_HOST_FLACENC_HPP_
 #define FLACENC_HOST_FLACENC_HPP_
 
@@ -438,8 +441,8 @@ struct Stream {  // datatype.rs:65
   }
   // BitRepr for Stream::write (bitrepr.rs:185-196): "fLaC", the STREAMINFO block (:207-216,
   // :246-270, last-block flag set as Stream::write does for a stream without further metadata),
-  // then every frame's precomputed bitstream (:290-293).  Frames that did not go through the GPU
-  // bit writer have none: the host-side bit writer is outside this mirror.
+  // then every frame's precomputed bitstream (:290-293).  A frame that the GPU bit writer refused as too large
+  // has none: the host-side bit writer is outside this mirror.
   std::vector<uint8_t> to_bytes() const {
     std::vector<uint8_t> out = {0x66, 0x4c, 0x61, 0x43, 0x80, 0x00, 0x00, 34};
     auto be = [&](uint64_t v, int bytes) {
@@ -455,8 +458,8 @@ struct Stream {  // datatype.rs:65
     out.insert(out.end(), stream_info.md5_digest, stream_info.md5_digest + 16);
     for (const Frame& f : frames) {
       if (f.precomputed_bitstream.empty())
-        throw std::runtime_error("Stream::to_bytes: a frame has no precomputed bitstream (only 2-channel "
-                                 "streams go through the GPU bit writer)");
+        throw std::runtime_error("Stream::to_bytes: a frame has no precomputed bitstream (too large for "
+                                 "the GPU bit writer)");
       out.insert(out.end(), f.precomputed_bitstream.begin(), f.precomputed_bitstream.end());
     }
     return out;
@@ -655,12 +658,6 @@ inline flacenc_hip_qlpc_config to_abi(const config::SubFrameCoding& c) {
   return o;
 }
 
-inline bool is_constant(const int32_t* s, size_t n) {  // arrayutils::is_constant, arrayutils.rs:382
-  for (size_t t = 1; t < n; ++t)
-    if (s[t] != s[0]) return false;
-  return true;
-}
-
 // SubFrame::Lpc from one GPU record + residual row (Lpc::from_parts, coding.rs:373-380)
 inline component::Lpc make_lpc(const flacenc_hip_subframe_params& p, const int32_t* residual,
                                const int32_t* signal, size_t n, uint8_t bps) {
@@ -698,40 +695,13 @@ inline component::FixedLpc make_fixed_lpc(const flacenc_hip_subframe_params& p, 
   fx.bits_per_sample = bps;
   return fx;
 }
-
-// encode_subframe, src/coding.rs:384-418, with the LPC and fixed-LPC candidates supplied by the GPU
-// (`fixed_key` = the order selector's key of the fixed candidate: fixed_lpc returned Some iff it is
-// below verbatim_bits, coding.rs:262, :284)
-inline component::SubFrame encode_subframe(const config::SubFrameCoding& cfg, const int32_t* samples, size_t n,
-                                           uint8_t bps, const flacenc_hip_subframe_params* lpc_rec,
-                                           const int32_t* lpc_residual,
-                                           const flacenc_hip_subframe_params* fixed_rec = nullptr,
-                                           const int32_t* fixed_residual = nullptr, uint64_t fixed_key = 0) {
-  if (cfg.use_constant && is_constant(samples, n)) return component::Constant{n, samples[0], bps};
-  const size_t verbatim_bits = component::Verbatim::count_bits_from_metadata(n, bps);
-  const bool too_short = n < constant::MIN_BLOCK_SIZE_FOR_PREDICTION;
-  const bool have_fixed = !too_short && cfg.use_fixed && fixed_rec != nullptr && fixed_key < verbatim_bits;
-  size_t baseline_bits = verbatim_bits;
-  if (have_fixed) baseline_bits = std::min<size_t>(verbatim_bits, fixed_rec->subframe_bits);
-  if (!too_short && cfg.use_lpc && lpc_rec != nullptr) {
-    if (lpc_rec->status != FLACENC_HIP_SUBFRAME_OK)
-      throw std::runtime_error("LPC analysis reported a non-finite result (the reference panics here, lpc.rs:786)");
-    component::Lpc cand = make_lpc(*lpc_rec, lpc_residual, samples, n, bps);
-    if (cand.count_bits() < baseline_bits) return cand;  // then also < verbatim_bits
-  }
-  if (have_fixed) {
-    component::FixedLpc cand = make_fixed_lpc(*fixed_rec, fixed_residual, samples, n, bps);
-    if (cand.count_bits() < verbatim_bits) return cand;
-  }
-  return component::Verbatim{std::vector<int32_t>(samples, samples + n), bps};
-}
 }  // namespace detail
 
 namespace detail {
 // encode_fixed_size_frame (src/coding.rs:581-606) for a run of frames on ONE GPU: `bufs[i]` is stream
 // frame first_number + i*number_step (number_step > 1 when frames were dealt round-robin over several
-// GPUs).  Frames of equal filled size (all but the stream's last) are analysed in one batch; the
-// reference's per-frame controller runs on the device where the ABI offers it and on the host otherwise.
+// GPUs).  Frames of equal filled size (all but the stream's last) are coded in one batch; the reference's
+// per-frame controller (encode_frame, coding.rs:530-544) and its bit writer run on the device for every group.
 inline std::vector<component::Frame> encode_frame_run(const config::Encoder& config,
                                                       const std::vector<const source::FrameBuf*>& bufs,
                                                       size_t first_number, size_t number_step, size_t nch,
@@ -742,7 +712,6 @@ inline std::vector<component::Frame> encode_frame_run(const config::Encoder& con
   flacenc_hip_qlpc_config abi_cfg = detail::to_abi(sc);
   abi_cfg.flags |= gpu.sum_order_flags(sc.qlpc.lpc_order);
   const bool stereo = (nch == 2);
-  const size_t per_frame = stereo ? 4 : nch;  // analyses per frame (coding.rs:530-544)
 
   // 2. group frames by filled size (all but the last are block_size) and batch each group
   size_t f0 = 0;
@@ -751,13 +720,11 @@ inline std::vector<component::Frame> encode_frame_run(const config::Encoder& con
     size_t f1 = f0;
     while (f1 < bufs.size() && bufs[f1]->filled_size() == n) ++f1;
     const size_t nf = f1 - f0;
-    const bool use_gpu = sc.use_lpc && n >= constant::MIN_BLOCK_SIZE_FOR_PREDICTION;
-    // 2a. stereo: try the entry point that also runs the controller on the GPU
-    //     (flacenc_hip_encode_stereo_frames: block 4096, order <= 12); its records are turned
-    //     into Frames directly.  Anything else falls through to the 4-candidate path below and the
-    //     host-side controller -- same result either way (tests/test_gpu_parity.py).
-    const bool fused_ok = (sc.use_lpc || sc.use_fixed) && n >= constant::MIN_BLOCK_SIZE_FOR_PREDICTION;
-    if (fused_ok && stereo) {
+    // 2a. stereo: encode_frame on the GPU (flacenc_hip_encode_stereo_frames), its records turned into Frames directly,
+    //     and the frames' bytes (flacenc_hip_pack_stereo_frames).  A block below MIN_BLOCK_SIZE_FOR_PREDICTION and a
+    //     config with neither predictor go the same way: the library codes them Constant / Verbatim (too_short,
+    //     coding.rs:396).
+    if (stereo) {
       PinnedBuffer<int32_t> staged(nf * 2 * n);
       for (size_t f = 0; f < nf; ++f)
         for (size_t c = 0; c < 2; ++c)
@@ -831,12 +798,11 @@ inline std::vector<component::Frame> encode_frame_run(const config::Encoder& con
       }
       if (rc == FLACENC_HIP_ERR_BAD_CONFIG)
         throw error::EncodeError(error::EncodeError::Config, flacenc_hip_last_error(gpu.get()));
-      if (rc != FLACENC_HIP_ERR_UNSUPPORTED)
-        throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
     }
     // 2a'. mono / multi-channel: encode_frame for Independent(n) on the GPU (flacenc_hip_encode_frames)
     //      and the frames' bytes (flacenc_hip_pack_frames)
-    if (fused_ok && !stereo) {
+    {
       PinnedBuffer<int32_t> staged(nf * nch * n);
       for (size_t f = 0; f < nf; ++f)
         for (size_t c = 0; c < nch; ++c)
@@ -899,124 +865,8 @@ inline std::vector<component::Frame> encode_frame_run(const config::Encoder& con
       }
       if (rc == FLACENC_HIP_ERR_BAD_CONFIG)
         throw error::EncodeError(error::EncodeError::Config, flacenc_hip_last_error(gpu.get()));
-      if (rc != FLACENC_HIP_ERR_UNSUPPORTED)
-        throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
     }
-    // 2b. the LPC candidates of every channel (stereo: L, R, M, S) in one batch
-    std::vector<flacenc_hip_subframe_params> recs(use_gpu ? nf * per_frame : 0);
-    PinnedBuffer<int32_t> resid(use_gpu ? nf * per_frame * n : 0);
-    if (use_gpu) {
-      PinnedBuffer<int32_t> staged(nf * nch * n);
-      for (size_t f = 0; f < nf; ++f)
-        for (size_t c = 0; c < nch; ++c)
-          std::memcpy(&staged[(f * nch + c) * n], bufs[f0 + f]->channel_slice(c), n * sizeof(int32_t));
-      int rc;
-      if (stereo) {
-        rc = flacenc_hip_stereo_qlpc_batch(gpu.get(), &abi_cfg, staged.data(), nf, static_cast<uint32_t>(n), n,
-                                           static_cast<uint32_t>(bps), recs.data(), resid.data(), n,
-                                           FLACENC_HIP_MEM_HOST);
-      } else {
-        std::vector<uint8_t> bpsv(nf * nch, static_cast<uint8_t>(bps));
-        rc = flacenc_hip_qlpc_batch(gpu.get(), &abi_cfg, staged.data(), nf * nch, static_cast<uint32_t>(n), n,
-                                    bpsv.data(), recs.data(), resid.data(), n, nullptr, nullptr,
-                                    FLACENC_HIP_MEM_HOST);
-      }
-      if (rc == FLACENC_HIP_ERR_BAD_CONFIG)
-        throw error::EncodeError(error::EncodeError::Config, flacenc_hip_last_error(gpu.get()));
-      if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
-    }
-    // 2c. the fixed-LPC candidates of the same subframes (fixed_lpc, coding.rs:298-331)
-    const bool use_fixed_gpu = sc.use_fixed && n >= constant::MIN_BLOCK_SIZE_FOR_PREDICTION;
-    std::vector<flacenc_hip_subframe_params> frecs;
-    std::vector<int32_t> fresid;
-    std::vector<uint64_t> fkeys;
-    if (use_fixed_gpu) {
-      frecs.resize(nf * per_frame);
-      fresid.resize(nf * per_frame * n);
-      fkeys.resize(nf * per_frame);
-      PinnedBuffer<int32_t> staged(nf * nch * n);
-      for (size_t f = 0; f < nf; ++f)
-        for (size_t c = 0; c < nch; ++c)
-          std::memcpy(&staged[(f * nch + c) * n], bufs[f0 + f]->channel_slice(c), n * sizeof(int32_t));
-      flacenc_hip_frame_config fc{};
-      fc.qlpc = abi_cfg;
-      fc.use_fixed = 1;
-      fc.fixed_max_order = static_cast<uint32_t>(sc.fixed.max_order);
-      fc.fixed_order_sel = sc.fixed.order_sel.type == config::OrderSel::BitCount ? FLACENC_HIP_ORDERSEL_BITCOUNT
-                                                                                 : FLACENC_HIP_ORDERSEL_APPROXENT;
-      fc.fixed_partitions = static_cast<uint32_t>(sc.fixed.order_sel.partitions);
-      const int rc = flacenc_hip_fixed_lpc_batch(
-          gpu.get(), &fc, staged.data(), stereo ? nf : nf * nch, static_cast<uint32_t>(n), n, nullptr,
-          static_cast<uint32_t>(bps), stereo ? FLACENC_HIP_LAYOUT_STEREO_FRAMES : FLACENC_HIP_LAYOUT_SUBFRAMES,
-          frecs.data(), fresid.data(), n, fkeys.data(), FLACENC_HIP_MEM_HOST);
-      if (rc == FLACENC_HIP_ERR_BAD_CONFIG)
-        throw error::EncodeError(error::EncodeError::Config, flacenc_hip_last_error(gpu.get()));
-      if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
-    }
-    // 3. the reference's controller per frame (encode_frame, coding.rs:530-544)
-    for (size_t f = 0; f < nf; ++f) {
-      const source::FrameBuf& fb = *bufs[f0 + f];
-      component::Frame frame;
-      frame.frame_number = static_cast<uint32_t>(first_number + (f0 + f) * number_step);
-      frame.block_size = n;
-      auto rec = [&](size_t k) { return use_gpu ? &recs[f * per_frame + k] : nullptr; };
-      auto res = [&](size_t k) { return use_gpu ? &resid[(f * per_frame + k) * n] : nullptr; };
-      auto frec = [&](size_t k) { return use_fixed_gpu ? &frecs[f * per_frame + k] : nullptr; };
-      auto fres = [&](size_t k) { return use_fixed_gpu ? &fresid[(f * per_frame + k) * n] : nullptr; };
-      auto fkey = [&](size_t k) { return use_fixed_gpu ? fkeys[f * per_frame + k] : uint64_t(0); };
-      if (!stereo) {
-        for (size_t c = 0; c < nch; ++c)
-          frame.subframes.push_back(detail::encode_subframe(sc, fb.channel_slice(c), n, static_cast<uint8_t>(bps),
-                                                            rec(c), res(c), frec(c), fres(c), fkey(c)));
-      } else {
-        // try_stereo_coding, coding.rs:469-527
-        const int32_t* l = fb.channel_slice(0);
-        const int32_t* r = fb.channel_slice(1);
-        std::vector<int32_t> m(n), s(n);
-        for (size_t t = 0; t < n; ++t) {
-          m[t] = (l[t] + r[t]) >> 1;
-          s[t] = l[t] - r[t];
-        }
-        component::SubFrame sl = detail::encode_subframe(sc, l, n, static_cast<uint8_t>(bps), rec(0), res(0), frec(0), fres(0), fkey(0));
-        component::SubFrame sr = detail::encode_subframe(sc, r, n, static_cast<uint8_t>(bps), rec(1), res(1), frec(1), fres(1), fkey(1));
-        component::SubFrame sm = detail::encode_subframe(sc, m.data(), n, static_cast<uint8_t>(bps), rec(2), res(2), frec(2), fres(2), fkey(2));
-        component::SubFrame ss = detail::encode_subframe(sc, s.data(), n, static_cast<uint8_t>(bps + 1), rec(3), res(3), frec(3), fres(3), fkey(3));
-        const size_t bl = component::count_bits(sl), br = component::count_bits(sr);
-        const size_t bm = component::count_bits(sm), bs = component::count_bits(ss);
-        size_t min_bits = bl + br;
-        component::ChannelAssignment best = component::ChannelAssignment::Independent;
-        if (config.stereo_coding.use_leftside && bl + bs < min_bits) {
-          min_bits = bl + bs;
-          best = component::ChannelAssignment::LeftSide;
-        }
-        if (config.stereo_coding.use_rightside && br + bs < min_bits) {
-          min_bits = br + bs;
-          best = component::ChannelAssignment::RightSide;
-        }
-        if (config.stereo_coding.use_midside && bm + bs < min_bits) {
-          min_bits = bm + bs;
-          best = component::ChannelAssignment::MidSide;
-        }
-        frame.channel_assignment = best;
-        // ChannelAssignment::select_channels, datatype.rs:1145-1171
-        switch (best) {
-          case component::ChannelAssignment::Independent:
-            frame.subframes = {std::move(sl), std::move(sr)};
-            break;
-          case component::ChannelAssignment::LeftSide:
-            frame.subframes = {std::move(sl), std::move(ss)};
-            break;
-          case component::ChannelAssignment::RightSide:
-            frame.subframes = {std::move(ss), std::move(sr)};
-            break;
-          case component::ChannelAssignment::MidSide:
-            frame.subframes = {std::move(sm), std::move(ss)};
-            break;
-        }
-      }
-      out.push_back(std::move(frame));
-    }
-    f0 = f1;
   }
   return out;
 }
@@ -1030,11 +880,22 @@ std::vector<source::FrameBuf> drain_source(SourceT& src, size_t block_size, size
     source::FrameBuf fb(nch, block_size);
     const size_t got = src.read_samples(block_size, fb);
     if (got == 0) break;
-    fb.verify_samples(bps);
+    try {  // encode_fixed_size_frame's `verify_samples(..)?` (coding.rs:593): From<VerifyError> for EncodeError is Config
+      fb.verify_samples(bps);  // (error.rs:489-491)
+    } catch (const error::VerifyError& e) {
+      throw error::EncodeError(error::EncodeError::Config, e.what());
+    }
     stream.stream_info.total_samples += got;
     bufs.push_back(std::move(fb));
   }
   return bufs;
+}
+
+// fixed-block mode exposes one block size in STREAMINFO, the largest block seen (a stream shorter than one block: its
+// only frame's); a stream without frames keeps StreamInfo::new's values (coding.rs:676-687)
+inline void finalize_block_sizes(component::Stream& stream) {
+  if (stream.frames.empty()) return;
+  stream.stream_info.min_block_size = stream.stream_info.max_block_size;
 }
 
 template <class SourceT>
@@ -1057,9 +918,9 @@ component::Stream new_stream_for(const config::Encoder& config, const SourceT& s
 }
 }  // namespace detail
 
-// encode_with_fixed_block_size, src/coding.rs:645-700: reads the whole source, analyses all
-// full-size frames in ONE GPU batch (the tail frame, if shorter, in a second one), then runs the
-// reference's per-frame controller (on the device for the shapes the ABI covers, else on the host).
+// encode_with_fixed_block_size, src/coding.rs:645-700: reads the whole source and codes all full-size frames in ONE
+// GPU batch (the tail frame, if shorter, in a second one): the reference's per-frame controller and bit writer on the
+// device.
 template <class SourceT>
 component::Stream encode_with_fixed_block_size(const config::Encoder& config, SourceT src, size_t block_size,
                                                HipContext& gpu) {
@@ -1071,9 +932,7 @@ component::Stream encode_with_fixed_block_size(const config::Encoder& config, So
   for (const source::FrameBuf& fb : bufs) run.push_back(&fb);
   for (component::Frame& f : detail::encode_frame_run(config, run, 0, 1, nch, bps, src.sample_rate(), gpu))
     stream.add_frame(std::move(f));
-  // fixed-block mode exposes one block size in STREAMINFO (coding.rs:676-690)
-  stream.stream_info.min_block_size = block_size;
-  stream.stream_info.max_block_size = block_size;
+  detail::finalize_block_sizes(stream);
   return stream;
 }
 
@@ -1138,8 +997,7 @@ component::Stream encode_with_fixed_block_size(const config::Encoder& config, So
   for (const std::exception_ptr& e : failures)
     if (e) std::rethrow_exception(e);
   sink.finalize([&](component::Frame f) { stream.add_frame(std::move(f)); });
-  stream.stream_info.min_block_size = block_size;
-  stream.stream_info.max_block_size = block_size;
+  detail::finalize_block_sizes(stream);
   return stream;
 }
 

@@ -33,13 +33,12 @@ class Bits:
     def __init__(self, data, pos=0):
         self.bits = np.unpackbits(np.frombuffer(bytes(data), np.uint8))
         self.ones = np.flatnonzero(self.bits)
+        self.value = int.from_bytes(bytes(data), "big")   # the same bits as one integer: a field is a shift and a mask
         self.pos = pos
 
     def u(self, n):
-        v = 0
-        for b in self.bits[self.pos:self.pos + n]:
-            v = (v << 1) | int(b)
         assert self.pos + n <= len(self.bits), "ran past the end of the frame"
+        v = (self.value >> (len(self.bits) - self.pos - n)) & ((1 << n) - 1)
         self.pos += n
         return v
 
@@ -64,8 +63,10 @@ def _residual(br, n, order):
     assert n % nparts == 0
     out = np.zeros(n, np.int64)
     t = order
+    params = []
     for q in range(nparts):
         p = br.u(pbits)
+        params.append(p)
         count = n // nparts - (order if q == 0 else 0)
         if p == esc:
             raw = br.u(5)
@@ -77,6 +78,7 @@ def _residual(br, n, order):
                 u = (br.unary() << p) | br.u(p)
                 out[t] = (u >> 1) ^ -(u & 1)
                 t += 1
+    br.partitions = (porder, params)   # what the residual header said, for parse_frame's per-subframe keys
     return out
 
 
@@ -87,16 +89,19 @@ def _subframe(br, n, bps, wasted_ok=False):
         assert wasted_ok, "wasted bits are not produced by this encoder"
         k = br.unary() + 1
         assert k < bps
-        x, kind, order = _subframe_body(br, n, bps - k, typ)
-        return x << k, kind, order
+        x, kind, order, detail = _subframe_body(br, n, bps - k, typ)
+        return x << k, kind, order, detail
     return _subframe_body(br, n, bps, typ)
 
 
 def _subframe_body(br, n, bps, typ):
+    """-> (samples, kind, order, detail): detail = (precision, shift, partition order, the partitions' parameter fields;
+    an escaped partition's is 15 or 31), zeros and an empty list where the kind has none."""
     if typ == 0:
-        return np.full(n, br.s(bps), np.int64), "constant", 0
+        return np.full(n, br.s(bps), np.int64), "constant", 0, (0, 0, 0, [])
     if typ == 1:
-        return np.array([br.s(bps) for _ in range(n)], np.int64), "verbatim", 0
+        return np.array([br.s(bps) for _ in range(n)], np.int64), "verbatim", 0, (0, 0, 0, [])
+    prec = 0
     if 8 <= typ <= 12:
         order = typ - 8
         coefs, shift, kind = FIXED_COEFS[order], 0, "fixed"
@@ -111,17 +116,20 @@ def _subframe_body(br, n, bps, typ):
         assert shift >= 0
         coefs, kind = [br.s(prec) for _ in range(order)], "lpc"
     out = _residual(br, n, order)
+    porder, params = br.partitions
     out[:order] = warm
     for t in range(order, n):
         pred = sum(int(c) * int(out[t - 1 - j]) for j, c in enumerate(coefs))
         out[t] += pred >> shift
-    return out, kind, order
+    return out, kind, order, (prec, shift, porder, params)
 
 
 def parse_frame(data, stream_bps=None, stream_rate=None, wasted_ok=False):
     """-> dict(header fields, channels = int64 [nch, n] after undoing the stereo decorrelation,
-    kinds, orders, length = bytes consumed).  Asserts the sync code, reserved bits and both CRCs, and -- unless
-    wasted_ok -- that no subframe carries wasted bits."""
+    kinds, orders, length = bytes consumed; header_bits = the header's bits with its CRC-8; per subframe sub_bps (the
+    width it is coded at), precisions, shifts, partition_orders, rice_params and subframe_bits (its bits in the frame)).
+    Asserts the sync code, reserved bits and both CRCs, and -- unless wasted_ok -- that no subframe carries wasted
+    bits."""
     data = bytes(data)
     br = Bits(data)
     assert br.u(14) == 0x3FFE, "sync code"
@@ -155,17 +163,22 @@ def parse_frame(data, stream_bps=None, stream_rate=None, wasted_ok=False):
         rate = SAMPLE_RATES.get(sr_tag, stream_rate)
     hdr_len = br.pos // 8
     assert br.u(8) == crc8(data[:hdr_len]), "header CRC-8"
+    header_bits = br.pos
     bps = SAMPLE_SIZES.get(ss_tag, stream_bps)
     assert bps is not None
     nch = ch_tag + 1 if ch_tag < 8 else 2
     assert ch_tag <= 10
-    subs, kinds, orders = [], [], []
+    subs, kinds, orders, details, sub_bits, sub_bps = [], [], [], [], [], []
     for c in range(nch):
         side = (ch_tag == 8 and c == 1) or (ch_tag == 9 and c == 0) or (ch_tag == 10 and c == 1)
-        x, kind, order = _subframe(br, n, bps + (1 if side else 0), wasted_ok)
+        at = br.pos
+        x, kind, order, detail = _subframe(br, n, bps + (1 if side else 0), wasted_ok)
         subs.append(x)
         kinds.append(kind)
         orders.append(order)
+        details.append(detail)
+        sub_bits.append(br.pos - at)
+        sub_bps.append(bps + (1 if side else 0))
     br.pos = (br.pos + 7) // 8 * 8
     body_len = br.pos // 8
     assert br.u(16) == crc16(data[:body_len]), "frame CRC-16"
@@ -179,4 +192,7 @@ def parse_frame(data, stream_bps=None, stream_rate=None, wasted_ok=False):
         subs = [(mid + side) >> 1, (mid - side) >> 1]
     return {"variable": variable, "number": number, "block_size": n, "sample_rate": rate, "bps": bps,
             "channel_tag": ch_tag, "channels": np.stack(subs), "kinds": kinds, "orders": orders,
-            "length": br.pos // 8}
+            "length": br.pos // 8, "header_bits": header_bits, "sub_bps": sub_bps,
+            "precisions": [d[0] for d in details], "shifts": [d[1] for d in details],
+            "partition_orders": [d[2] for d in details], "rice_params": [d[3] for d in details],
+            "subframe_bits": sub_bits}

@@ -143,8 +143,8 @@ int main(int argc, char** argv) {
     }
     CHECK(thrown);
   }
-  // the reference's default configuration (use_fixed = true): fused path for stereo 4096 blocks,
-  // flacenc_hip_fixed_lpc_batch for the short tail block and every other shape
+  // the reference's default configuration (use_fixed = true): fused path for stereo 4096 blocks, the
+  // candidate batches behind the same frame-level entry points for the short tail block and every other shape
   {
     config::Encoder def;
     for (size_t channels : {1, 2, 3}) integrity_test(gpu, def, channels, 16123, 16, 4096);
