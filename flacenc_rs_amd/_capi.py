@@ -57,6 +57,7 @@ COMM_ID_BYTES = 128  # FLACENC_HIP_COMM_ID_BYTES
 DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 8
 DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
 DECODE_NO_ROOM, DECODE_CHAIN = 256, 512  # totals[3] of flacenc_hip_decode_pcm: why the call stopped
+ENCODE_NO_ROOM = 256  # FLACENC_HIP_ENCODE_NO_ROOM: totals[s][3] of flacenc_hip_encode_streams
 INDEX_ERROR = 1 << 63
 VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flacenc_hip_encode_variable*
 
@@ -67,7 +68,8 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_set_order_guess_trace", "flacenc_hip_debug_set_stream_chunk",
                  "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers",
                  "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan",
-                 "flacenc_hip_debug_last_decode_streams_plan")
+                 "flacenc_hip_debug_last_decode_streams_plan", "flacenc_hip_debug_set_encode_streams_chunk",
+                 "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -125,6 +127,8 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_streams",
     "flacenc_hip_md5_spans",
     "flacenc_hip_decode_streams_md5",
+    "flacenc_hip_encode_streams_frames",
+    "flacenc_hip_encode_streams",
     "flacenc_hip_variable_bytes_bound",
     "flacenc_hip_variable_max_frames",
     "flacenc_hip_encode_variable_async",
@@ -174,6 +178,13 @@ STREAM_DESC_DTYPE = np.dtype([("offset", "<u8"), ("n_bytes", "<u8"), ("out_offse
                               ("channels", "<u4"), ("bits_per_sample", "<u4"), ("max_block_size", "<u4"),
                               ("bytes_per_sample", "<u4")])
 assert STREAM_DESC_DTYPE.itemsize == 48
+
+
+# flacenc_hip_pcm_stream_desc (48 bytes): one stream of flacenc_hip_encode_streams
+PCM_STREAM_DESC_DTYPE = np.dtype([("offset", "<u8"), ("total_samples", "<u8"), ("out_offset", "<u8"),
+                                  ("out_capacity", "<u8"), ("channels", "<u4"), ("bits_per_sample", "<u4"),
+                                  ("bytes_per_sample", "<u4"), ("sample_rate", "<u4")])
+assert PCM_STREAM_DESC_DTYPE.itemsize == 48
 
 
 class FrameConfig(C.Structure):
@@ -252,6 +263,24 @@ def stream_descs(streams) -> np.ndarray:
     return table
 
 
+def pcm_stream_descs(streams) -> np.ndarray:
+    """A PCM_STREAM_DESC_DTYPE array from one, or from rows (offset, total_samples, out_offset, out_capacity, channels,
+    bits_per_sample, bytes_per_sample, sample_rate); never empty memory, so that its address is not NULL."""
+    if isinstance(streams, np.ndarray) and streams.dtype == PCM_STREAM_DESC_DTYPE:
+        table = np.ascontiguousarray(streams)
+    else:
+        table = np.array([tuple(int(v) for v in row) for row in streams], PCM_STREAM_DESC_DTYPE)
+    if table.size == 0:
+        return np.zeros(1, PCM_STREAM_DESC_DTYPE)[:0]
+    return table
+
+
+def encode_streams_frames(streams, block_size: int) -> int:
+    """flacenc_hip_encode_streams_frames: the sum of ceil(total_samples / block_size) over the table."""
+    table = pcm_stream_descs(streams)
+    return int(load().flacenc_hip_encode_streams_frames(table.ctypes.data, len(table), block_size))
+
+
 class FlacencHipError(RuntimeError):
     def __init__(self, code, message=""):
         self.code = code
@@ -326,6 +355,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
         L.flacenc_hip_debug_set_stream_chunk.argtypes = [vp, C.c_size_t]
         L.flacenc_hip_debug_last_stream_plan.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.flacenc_hip_debug_last_stream_buffers.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "flacenc_hip_debug_set_encode_streams_chunk"):
+        L.flacenc_hip_debug_set_encode_streams_chunk.argtypes = [vp, C.c_size_t]
+        L.flacenc_hip_debug_streams_fill.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32,
+                                                     vp, C.c_size_t]
     if hasattr(L, "flacenc_hip_debug_set_decode_plan"):
         L.flacenc_hip_debug_set_decode_plan.argtypes = [vp, C.c_size_t, C.c_size_t]
         L.flacenc_hip_debug_last_decode_plan.argtypes = [vp] + [C.POINTER(C.c_size_t)] * 4
@@ -439,6 +472,11 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_md5_spans.restype = C.c_int
     L.flacenc_hip_decode_streams_md5.argtypes = L.flacenc_hip_decode_streams.argtypes + [vp]
     L.flacenc_hip_decode_streams_md5.restype = C.c_int
+    L.flacenc_hip_encode_streams_frames.argtypes = [vp, C.c_size_t, C.c_uint32]
+    L.flacenc_hip_encode_streams_frames.restype = C.c_size_t
+    L.flacenc_hip_encode_streams.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp,
+                                             C.c_uint64, vp, C.c_size_t, vp, vp, C.c_int]
+    L.flacenc_hip_encode_streams.restype = C.c_int
     L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -704,6 +742,30 @@ class Handle:
         plan = np.zeros(4, np.uint64)
         self._check(self._hook("flacenc_hip_debug_last_decode_streams_plan")(self._h, plan.ctypes.data))
         return tuple(int(x) for x in plan)
+
+    def debug_set_encode_streams_chunk(self, frames: int):
+        """encode_streams cuts every run of a class into frame-level calls of at most `frames` frames in place of its
+        rule (flacenc_hip_debug.h); 0: the rule again.  More than 8192 is refused."""
+        self._check(self._hook("flacenc_hip_debug_set_encode_streams_chunk")(self._h, int(frames)))
+
+    def debug_last_encode_streams_plan(self):
+        """dict(launches, syncs, transfers, classes, full_runs, tail_runs, calls) of the last encode_streams call on
+        this handle: launches are the call's own kernels, calls the frame-level calls (= full_runs + tail_runs)."""
+        plan = np.zeros(8, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_last_encode_streams_plan")(self._h, plan.ctypes.data))
+        names = ("launches", "syncs", "transfers", "classes", "full_runs", "tail_runs", "calls")
+        return {k: int(v) for k, v in zip(names, plan)}
+
+    def debug_streams_fill(self, bytes_ptr: int, total_samples: int, channels: int, bytes_per_sample: int, n_frames: int,
+                           block_size: int, frames_ptr: int, stride: int, check: bool = True) -> int:
+        """The fill kernel of encode_streams alone, on device pointers, with the arguments of fill_le_bytes
+        (flacenc_hip_debug.h): rows 16-byte aligned, stride a multiple of 4, rows written up to the stride; blocks."""
+        rc = self._hook("flacenc_hip_debug_streams_fill")(self._h, bytes_ptr or None, total_samples, channels,
+                                                          bytes_per_sample, n_frames, block_size, frames_ptr or None,
+                                                          stride)
+        if check:
+            self._check(rc)
+        return rc
 
     def synchronize(self):
         self._check(self._lib.flacenc_hip_synchronize(self._h))
@@ -1199,6 +1261,52 @@ class Handle:
         rc = self._lib.flacenc_hip_decode_streams_md5(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
                                                       max_frames, out_ptr or None, out_bytes, totals_ptr or None,
                                                       call.ctypes.data, MEM_DEVICE, digests_ptr or None)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
+
+    def encode_streams(self, pcm, streams, cfg: FrameConfig, block_size: int, out: np.ndarray,
+                       frame_lengths: np.ndarray | None = None, totals: np.ndarray | None = None,
+                       max_frames: int | None = None, check: bool = True):
+        """flacenc_hip_encode_streams on host arrays: `pcm` (bytes, or a uint8 array -- pinned or not) holds every
+        stream's packed PCM, `streams` is a PCM_STREAM_DESC_DTYPE array (or rows of its eight fields), `out` the caller's
+        uint8 buffer that holds every slot (written in place).  -> (frame lengths uint32 [frames], totals uint64
+        [n_streams, 4], call totals [frames, bytes], the call's code); with check=False a failure is returned instead of
+        raised."""
+        buf = pcm if isinstance(pcm, np.ndarray) else np.frombuffer(bytes(pcm), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table = pcm_stream_descs(streams)
+        n_frames = int(self._lib.flacenc_hip_encode_streams_frames(table.ctypes.data, len(table), block_size))
+        if frame_lengths is None:
+            frame_lengths = np.zeros(max(1, min(n_frames, 1 << 31)), np.uint32)
+        assert frame_lengths.dtype == np.uint32 and frame_lengths.flags["C_CONTIGUOUS"]
+        if totals is None:
+            totals = np.zeros((max(1, len(table)), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(table)
+        call = np.zeros(2, np.uint64)
+        base = buf if buf.size else np.zeros(1, np.uint8)
+        obase = out if out.size else np.zeros(1, np.uint8)
+        rc = self._lib.flacenc_hip_encode_streams(self._h, C.byref(cfg), base.ctypes.data, buf.size, table.ctypes.data,
+                                                  len(table), block_size, obase.ctypes.data, out.size,
+                                                  frame_lengths.ctypes.data,
+                                                  frame_lengths.size if max_frames is None else max_frames,
+                                                  totals.ctypes.data, call.ctypes.data, MEM_HOST)
+        if check:
+            self._check(rc)
+        return frame_lengths[:n_frames] if rc == OK else frame_lengths, totals[:len(table)], [int(call[0]), int(call[1])], rc
+
+    def encode_streams_device(self, pcm_ptr: int, pcm_bytes: int, streams, cfg: FrameConfig, block_size: int,
+                              out_ptr: int, out_bytes: int, frame_lengths_ptr: int, max_frames: int, totals_ptr: int,
+                              check: bool = True):
+        """flacenc_hip_encode_streams on device pointers (the table stays host memory); blocks on the handle's stream.
+        -> (call totals, the call's code)."""
+        table = pcm_stream_descs(streams)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_encode_streams(self._h, C.byref(cfg), pcm_ptr or None, pcm_bytes, table.ctypes.data,
+                                                  len(table), block_size, out_ptr or None, out_bytes,
+                                                  frame_lengths_ptr or None, max_frames, totals_ptr or None,
+                                                  call.ctypes.data, MEM_DEVICE)
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc

@@ -2,6 +2,7 @@
 // libflacenc_hip_hooks.so only, so the product library has none of them.
 #include "api_internal.h"
 #include "flacenc_hip_debug.h"
+#include "stream_encode_core.h"
 
 extern "C" {
 
@@ -92,6 +93,53 @@ int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_byt
 int flacenc_hip_debug_last_decode_streams_plan(flacenc_hip_handle* h, uint64_t plan[4]) {
   if (!h || !plan) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   for (int i = 0; i < 4; ++i) plan[i] = h->last_streams_plan[i];
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_set_encode_streams_chunk(flacenc_hip_handle* h, size_t frames) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (frames > 8192) {  // the rule's own upper end
+    h->last_error = "debug_set_encode_streams_chunk: more than 8192 frames per frame-level call";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->encode_streams_chunk_override = frames;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_last_encode_streams_plan(flacenc_hip_handle* h, uint64_t plan[8]) {
+  if (!h || !plan) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  for (int i = 0; i < 8; ++i) plan[i] = h->last_encode_streams_plan[i];
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t total_samples, uint32_t channels,
+                                   uint32_t bytes_per_sample, size_t n_frames, uint32_t block_size, int32_t* frames,
+                                   size_t stride) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (n_frames == 0) return FLACENC_HIP_OK;
+  if (!bytes || !frames || channels < 1 || channels > 8 || bytes_per_sample < 1 || bytes_per_sample > 4 ||
+      block_size < 1 || block_size > FLACENC_HIP_MAX_BLOCK_SIZE || stride < block_size || (stride & 3) ||
+      (reinterpret_cast<uintptr_t>(frames) & 15) || n_frames > 0x7FFFFFFFull) {
+    h->last_error = "debug_streams_fill: null pointer, channels not in 1..=8, bytes_per_sample not in 1..=4, rows not "
+                    "16-byte aligned, stride no multiple of 4 or below block_size, or 2^31 frames or more";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  std::vector<streamenc::LaunchFrame> table(n_frames);
+  const uint64_t per = static_cast<uint64_t>(channels) * bytes_per_sample;
+  for (size_t f = 0; f < n_frames; ++f) {
+    const uint64_t at = static_cast<uint64_t>(f) * block_size;
+    const uint64_t left = at < total_samples ? total_samples - at : 0;
+    table[f] = {at * per, static_cast<uint32_t>(left < block_size ? left : block_size), static_cast<uint32_t>(f)};
+  }
+  HIP_TRY(h, hipSetDevice(h->device));
+  int rc;
+  if ((rc = flacenc_hip::ensure(h, h->d_encs, n_frames * sizeof(streamenc::LaunchFrame))) != FLACENC_HIP_OK) return rc;
+  HIP_TRY(h, hipMemcpyAsync(h->d_encs.ptr, table.data(), n_frames * sizeof(streamenc::LaunchFrame), hipMemcpyHostToDevice,
+                            h->stream));
+  HIP_TRY(h, flacenc_hip::launch_streams_fill(bytes, static_cast<const streamenc::LaunchFrame*>(h->d_encs.ptr),
+                                              static_cast<uint32_t>(n_frames), channels, bytes_per_sample, 0, stride, frames,
+                                              h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return FLACENC_HIP_OK;
 }
 

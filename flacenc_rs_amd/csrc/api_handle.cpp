@@ -94,7 +94,7 @@ void flacenc_hip_destroy(flacenc_hip_handle* h) {
                           &h->d_fparams, &h->d_fresid, &h->d_fkeys, &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram, &h->d_esc,
                           &h->d_dec, &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack,
                           &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk, &h->d_wlist, &h->d_wrows, &h->d_wbps, &h->d_order,
-                          &h->d_ppk_off, &h->d_ppk_io, &h->d_dpcm_idx, &h->d_md5})
+                          &h->d_ppk_off, &h->d_ppk_io, &h->d_dpcm_idx, &h->d_md5, &h->d_encs})
     if (b->ptr) (void)hipFree(b->ptr);
   if (h->d_cert_fb) (void)hipFree(h->d_cert_fb);  // (the order mode's counters and their pinned mirror)
   if (h->h_cert_fb) (void)hipHostFree(h->h_cert_fb);

@@ -16,6 +16,7 @@
 //   api_decode_stream.cpp  rows to packed PCM (flacenc_hip_pack_le_bytes), the streaming way back (flacenc_hip_decode_pcm)
 //   flac_decode_streams.cpp  a batch of streams to packed PCM (flacenc_hip_decode_streams, _md5): its kernels and the call
 //   md5_streams.cpp      MD5 digests of a batch of spans (flacenc_hip_md5_spans): its kernel, launcher and the call
+//   encode_streams.cpp   a batch of PCM streams to frames (flacenc_hip_encode_streams): its kernels and the call
 //   api_variable.cpp     the block-size search
 //   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
 #ifndef FLACENC_HIP_API_INTERNAL_H_
@@ -35,6 +36,10 @@
 #include "flacenc_hip.h"
 #include "frame_pack.h"
 #include "qlpc_kernel.h"
+
+namespace streamenc {
+struct LaunchFrame;  // stream_encode_core.h
+}
 
 namespace flacenc_hip {
 
@@ -170,6 +175,7 @@ struct flacenc_hip_handle {
   // pack_le_bytes: the offsets when the caller wants none, host-pointer staging; decode_pcm: a window's index
   flacenc_hip::DeviceBuffer d_ppk_off, d_ppk_io, d_dpcm_idx;
   flacenc_hip::DeviceBuffer d_md5;  // md5_spans: the span table and (host pointers) the digests
+  flacenc_hip::DeviceBuffer d_encs;  // encode_streams: the plan's tables, lengths, offsets and totals
   // block-size search: the levels' frames, decision records and packed frames, its own records, host-pointer staging
   flacenc_hip::DeviceBuffer d_vbs_frames, d_vbs_results, d_vbs_pack, d_vbs_meta, d_vbs_io;
   // wasted bits: k per row, the marked frames (count first), the shifted rows and their widths
@@ -209,6 +215,10 @@ struct flacenc_hip_handle {
   // test hook, see flacenc_hip_debug_last_decode_streams_plan: kernel launches, host synchronisations, host-device
   // transfers and channel classes of the last flacenc_hip_decode_streams / flacenc_hip_decode_streams_md5 call
   uint64_t last_streams_plan[4] = {0, 0, 0, 0};
+  // test hooks, see flacenc_hip_debug_set_encode_streams_chunk / flacenc_hip_debug_last_encode_streams_plan: frames per
+  // frame-level call of flacenc_hip_encode_streams in place of its rule (0: the rule), and what the last call did
+  size_t encode_streams_chunk_override = 0;
+  uint64_t last_encode_streams_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch
@@ -311,6 +321,17 @@ int ensure_copy_pool(flacenc_hip_handle* h, const char* what);
 hipError_t launch_md5_spans(const uint8_t* bytes, const uint64_t* offsets, uint32_t offset_stride,
                             const uint64_t* lengths, const uint32_t* slot, uint32_t n_spans, uint8_t* digests,
                             hipStream_t stream);
+
+// ---- flac_decode_streams.cpp ----
+// its single-workgroup scan, for the batch encoder: out[i] = the sum of in[j] over j < i, out[n] the total
+hipError_t launch_streams_scan(const uint64_t* in, uint64_t n, uint64_t* out, hipStream_t stream);
+
+// ---- encode_streams.cpp ----
+// streams_fill_kernel on `stream`: frames table[0 .. n_frames) into rows row0 .. of `rows` (channel-major, `stride` words
+// per row, stride a multiple of 4, rows 16-byte aligned).  All pointers are device memory; one launch.
+hipError_t launch_streams_fill(const uint8_t* pcm, const streamenc::LaunchFrame* table, uint32_t n_frames,
+                               uint32_t channels, uint32_t bytes_per_sample, uint32_t row0, size_t stride, int32_t* rows,
+                               hipStream_t stream);
 
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);

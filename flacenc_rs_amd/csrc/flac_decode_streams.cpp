@@ -676,6 +676,13 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
 }
 
 }  // namespace
+
+// streams_scan_kernel for the batch encoder (encode_streams.cpp): out[i] = the sum of in[j] over j < i, out[n] the total
+hipError_t launch_streams_scan(const uint64_t* in, uint64_t n, uint64_t* out, hipStream_t stream) {
+  hipLaunchKernelGGL(streams_scan_kernel, dim3(1), dim3(1024), 0, stream, in, nullptr, nullptr, n, nullptr, out, nullptr);
+  return hipGetLastError();
+}
+
 }  // namespace flacenc_hip
 
 using namespace flacenc_hip;

@@ -83,6 +83,29 @@ int flacenc_hip_debug_last_decode_plan(flacenc_hip_handle* h, size_t* window_byt
  * depends on the number of streams.  Zeros after a call that was rejected or had no stream. */
 int flacenc_hip_debug_last_decode_streams_plan(flacenc_hip_handle* h, uint64_t plan[4]);
 
+/* Test hook (no reference counterpart): the plan of flacenc_hip_encode_streams.  `frames` != 0: the calls that follow cut
+ * every run of a class -- its full blocks, and the last blocks of one length -- into frame-level calls of at most `frames`
+ * frames in place of the rule clamp(48 MiB / frame bytes, 768, 8192).  The bytes a call returns do not depend on the plan;
+ * the hook brings the seams between frame-level calls down to a handful of frames.  0 (a fresh handle): the rule.  More
+ * than 8192 is FLACENC_HIP_ERR_BAD_ARGUMENT. */
+int flacenc_hip_debug_set_encode_streams_chunk(flacenc_hip_handle* h, size_t frames);
+/* What the last flacenc_hip_encode_streams call on the handle did: plan[0] launches of the call's own kernels (fill,
+ * lengths, scans, cut, place), plan[1] host synchronisations, plan[2] host-device transfers, plan[3] classes present in
+ * its table, plan[4] full-frame runs, plan[5] tail runs, plan[6] frame-level calls (= plan[4] + plan[5]; each enqueues
+ * what flacenc_hip_encode_pack_stereo_frames_async resp. flacenc_hip_encode_pack_frames_async enqueues for its shape),
+ * plan[7] 0.  plan[1] and plan[2] do not depend on the number of streams; plan[0] depends on the classes only.  Zeros
+ * after a call that was rejected or had no stream. */
+int flacenc_hip_debug_last_encode_streams_plan(flacenc_hip_handle* h, uint64_t plan[8]);
+/* Test and profiling hook (no reference counterpart): the fill kernel of flacenc_hip_encode_streams on its own, with the
+ * arguments and the result of flacenc_hip_fill_le_bytes on device pointers -- `bytes` (any byte alignment) holds
+ * total_samples inter-channel samples of one stream, frame f gets samples [f*block_size, (f+1)*block_size) and zeros
+ * beyond total_samples -- except that `frames` must be 16-byte aligned and `stride` a multiple of 4 (rows are written up
+ * to the stride, not up to block_size), and that n_frames is bounded by 2^31 - 1, not by 65535.  Builds the frame table
+ * on the host, uploads it, launches once on the handle's stream and blocks. */
+int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t total_samples, uint32_t channels,
+                                   uint32_t bytes_per_sample, size_t n_frames, uint32_t block_size, int32_t* frames,
+                                   size_t stride);
+
 #ifdef __cplusplus
 }
 #endif

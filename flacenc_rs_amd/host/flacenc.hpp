@@ -1136,5 +1136,44 @@ inline std::vector<DecodedPcm> decode_streams_md5(HipContext& gpu, const uint8_t
   return r;
 }
 
+// The way there for a library of short files (flacenc_hip_encode_streams on host memory): stream s is the packed PCM
+// pcm[offset, offset + total_samples * channels * bytes_per_sample) and its frames go to out[out_offset, out_offset +
+// out_capacity) -- exactly the bytes flacenc_hip_encode_pcm gives for it alone, frame numbers from 0.  frame_lengths gets
+// every frame's length, stream after stream; a stream whose slot was too small holds the whole frames that fit and says
+// so (no_room).  Their STREAMINFO digests come from md5_spans over the same PCM spans.
+struct EncodedStream {
+  uint64_t frames = 0;        // frames written to the slot
+  uint64_t bytes = 0;         // bytes written
+  uint64_t first_length = 0;  // index of the stream's first entry in frame_lengths
+  bool no_room = false;       // FLACENC_HIP_ENCODE_NO_ROOM: frames behind `frames` did not fit
+};
+
+inline std::vector<EncodedStream> encode_streams(HipContext& gpu, const flacenc_hip_frame_config& cfg, const uint8_t* pcm,
+                                                 size_t pcm_bytes, const std::vector<flacenc_hip_pcm_stream_desc>& streams,
+                                                 size_t block_size, uint8_t* out, size_t out_bytes,
+                                                 std::vector<uint32_t>& frame_lengths) {
+  const flacenc_hip_pcm_stream_desc none{};
+  const flacenc_hip_pcm_stream_desc* table = streams.empty() ? &none : streams.data();
+  const size_t n_frames = flacenc_hip_encode_streams_frames(table, streams.size(), static_cast<uint32_t>(block_size));
+  frame_lengths.assign(n_frames + 1, 0);
+  std::vector<uint64_t> totals(4 * streams.size() + 4, 0);
+  uint64_t call[2] = {0, 0};
+  const uint8_t no_bytes = 0;
+  uint8_t no_out = 0;
+  const int rc = flacenc_hip_encode_streams(gpu.get(), &cfg, pcm ? pcm : &no_bytes, pcm_bytes, table, streams.size(),
+                                            static_cast<uint32_t>(block_size), out ? out : &no_out, out_bytes,
+                                            frame_lengths.data(), n_frames, totals.data(), call, FLACENC_HIP_MEM_HOST);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  frame_lengths.resize(n_frames);
+  std::vector<EncodedStream> r(streams.size());
+  for (size_t s = 0; s < streams.size(); ++s) {
+    r[s].frames = totals[4 * s];
+    r[s].bytes = totals[4 * s + 1];
+    r[s].first_length = totals[4 * s + 2];
+    r[s].no_room = totals[4 * s + 3] == FLACENC_HIP_ENCODE_NO_ROOM;
+  }
+  return r;
+}
+
 }  // namespace flacenc
 #endif  // FLACENC_HOST_FLACENC_HPP_

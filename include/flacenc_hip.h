@@ -1078,6 +1078,75 @@ int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, 
                                    size_t n_streams, size_t max_frames, uint8_t* out, uint64_t out_bytes,
                                    uint64_t* totals, uint64_t call_totals[2], int memory_kind, uint8_t* digests);
 
+/*
+ * The way there in one call: a batch of PCM streams to FLAC frames, what flacenc_hip_encode_pcm does for one stream, for
+ * every stream of a table -- a speech corpus, a sample pack, the tracks of an album -- with a number of synchronisations
+ * and transfers that does not depend on the number of streams, and a number of launches that depends only on the
+ * classes of streams and the distinct lengths of their last blocks (below).
+ *   pcm, pcm_bytes   one buffer that holds every stream's packed interleaved little-endian PCM (the layout of
+ *                    flacenc_hip_encode_pcm).  Stream s is bytes [offset, offset + total_samples*channels*
+ *                    bytes_per_sample) of it.  Spans may touch, leave gaps, overlap or repeat, at any byte alignment; no
+ *                    byte outside a span is read
+ *   streams          n_streams descriptors (struct flacenc_hip_pcm_stream_desc, 48 bytes each), ALWAYS host memory,
+ *                    read before the call returns
+ *   block_size       of every frame but a stream's last, 64..32767 as for flacenc_hip_encode_pcm
+ *   out, out_bytes   one buffer for every stream's frames: stream s owns the slot [out_offset, out_offset +
+ *                    out_capacity).  Slots must be disjoint; the library does NOT check that (overlapping slots give
+ *                    unspecified bytes in the overlap, never a fault)
+ *   frame_lengths    max_frames entries of room, at least flacenc_hip_encode_streams_frames(streams, n_streams,
+ *                    block_size) = the sum of ceil(total_samples / block_size): the byte length of every frame, stream
+ *                    after stream in table order
+ *   totals           [n_streams][4]: [0] frames written to the slot, [1] bytes written, [2] the index of the stream's
+ *                    first entry in frame_lengths, [3] 0 or FLACENC_HIP_ENCODE_NO_ROOM
+ *   call_totals      host memory in both kinds: [0] frames and [1] bytes written over all streams
+ *   memory_kind      FLACENC_HIP_MEM_HOST (pageable or flacenc_hip_host_alloc memory) or FLACENC_HIP_MEM_DEVICE: where
+ *                    pcm, out, frame_lengths and totals live
+ * Per-stream equivalence: for every stream s its slot and frame_lengths[totals[s][2] ..] hold exactly what
+ * flacenc_hip_encode_pcm gives for that stream alone on the same handle with the same cfg (flags included), the stream's
+ * channels, bytes_per_sample, bits_per_sample and sample_rate, block_size, first_frame_number = 0 and frame_number_step
+ * = 1.  Every frame has block_size samples except a stream's last; a last block below 64 samples is the usual Constant /
+ * Verbatim frame.  channels == 2 takes the stereo decision, any other count Independent(channels).  Every
+ * FLACENC_HIP_FLAG_* the frame-level calls honour is honoured: the same frame-level calls run underneath
+ * (flacenc_hip_encode_pack_stereo_frames_async resp. flacenc_hip_encode_pack_frames_async, every frame packed with
+ * number 0 and renumbered when it is placed).
+ * The one difference: flacenc_hip_encode_pcm returns FLACENC_HIP_ERR_BAD_ARGUMENT when out_capacity is too small; here a
+ * slot that is too small gets the longest prefix of whole frames that fits and totals[s][3] = FLACENC_HIP_ENCODE_NO_ROOM;
+ * the lengths of the frames behind the cut are still written to frame_lengths.  Slot bytes beyond totals[s][1] and
+ * bytes of `out` in no slot are untouched.  n_streams == 0 and streams of 0 samples are OK (no frame, all-zero totals
+ * but [2]).
+ * FLACENC_HIP_ERR_BAD_ARGUMENT, with nothing written: a null pointer, an unknown memory kind, n_streams above 2^24, a span
+ * that reaches past pcm_bytes, a slot that reaches past out_bytes, max_frames below
+ * flacenc_hip_encode_streams_frames(...), a stream -- or a call -- of 2^31 frames or more, block_size outside 64..32767,
+ * channels outside 1..8, bytes_per_sample outside 1..4, bits_per_sample outside 8..24.
+ * The plan: a class is (channels, bits_per_sample, bytes_per_sample, sample_rate).  The full blocks of all streams of a
+ * class are one run, cut into frame-level calls of at most clamp(48 MiB / frame bytes, 768, 8192) frames; the last blocks
+ * of a class are one further run PER DISTINCT LENGTH, since the analysis kernels take one block size per launch (a corpus
+ * with k distinct tail lengths in a class pays k tail runs).  The call blocks and runs on the handle's stream, all of it
+ * enqueued on that one stream (no overlap of transfers with compute, unlike flacenc_hip_encode_pcm: a single long stream is
+ * that call's case); there is no stream-taking form yet.  Device scratch grows with the batch (the rows of the largest
+ * class, a pack slot per frame, and for host memory the PCM and the frames): a batch larger than device memory is the
+ * caller's to split, and the call returns FLACENC_HIP_ERR_DEVICE when scratch cannot be had.  Host results reach their
+ * slots through one transfer into pinned staging and the handle's host threads (flacenc_hip_set_host_threads).
+ * (`streams` is declared const void*: the descriptor is plain data every binding lays out itself.)
+ */
+#define FLACENC_HIP_ENCODE_NO_ROOM 256u
+struct flacenc_hip_pcm_stream_desc {
+  uint64_t offset;           /* the stream's PCM: bytes [offset, offset + total_samples*channels*bytes_per_sample) of `pcm` */
+  uint64_t total_samples;    /* inter-channel samples; 0 is legal */
+  uint64_t out_offset;       /* its slot: bytes [out_offset, out_offset + out_capacity) of `out` */
+  uint64_t out_capacity;
+  uint32_t channels;         /* 1..8; 2 = the stereo decision, else Independent(channels), as flacenc_hip_encode_pcm */
+  uint32_t bits_per_sample;  /* 8..24 */
+  uint32_t bytes_per_sample; /* 1..4 */
+  uint32_t sample_rate;
+};
+typedef struct flacenc_hip_pcm_stream_desc flacenc_hip_pcm_stream_desc;
+size_t flacenc_hip_encode_streams_frames(const void* streams, size_t n_streams, uint32_t block_size);
+int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const uint8_t* pcm,
+                               uint64_t pcm_bytes, const void* streams, size_t n_streams, uint32_t block_size,
+                               uint8_t* out, uint64_t out_bytes, uint32_t* frame_lengths, size_t max_frames,
+                               uint64_t* totals, uint64_t call_totals[2], int memory_kind);
+
 /* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
 /*
  * Each region coded at the block size that compresses it best (BASELINE config 5's "beat-search block sizing"; the

@@ -424,6 +424,17 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
         out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int, digests: *mut u8,
     ) -> c_int;
+    /// The sum of `ceil(total_samples / block_size)` over `n_streams` `PcmStreamDesc`: the entries `frame_lengths` needs.
+    pub fn flacenc_hip_encode_streams_frames(streams: *const c_void, n_streams: usize, block_size: u32) -> usize;
+    /// A batch of PCM streams to frames in one call: `streams` points at `n_streams` `PcmStreamDesc` in host memory; per
+    /// stream its slot and its `frame_lengths` entries hold what `flacenc_hip_encode_pcm` gives for it alone (frame
+    /// numbers from 0); `totals` is `[n_streams][4]` = frames, bytes, first `frame_lengths` index, 0 or
+    /// `ENCODE_NO_ROOM`; `call_totals` = frames and bytes of the call.
+    pub fn flacenc_hip_encode_streams(
+        h: *mut Handle, cfg: *const FrameConfig, pcm: *const u8, pcm_bytes: u64, streams: *const c_void,
+        n_streams: usize, block_size: u32, out: *mut u8, out_bytes: u64, frame_lengths: *mut u32, max_frames: usize,
+        totals: *mut u64, call_totals: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
     /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
     /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.
@@ -611,6 +622,24 @@ pub struct StreamDesc {
     pub max_block_size: u32,
     pub bytes_per_sample: u32,
 }
+
+/// `struct flacenc_hip_pcm_stream_desc` (48 bytes): one stream of `flacenc_hip_encode_streams` -- its packed PCM is
+/// `pcm[offset..offset + total_samples * channels * bytes_per_sample]`, its slot `out[out_offset..out_offset + out_capacity]`.
+#[repr(C)]
+#[derive(Clone, Copy, PartialEq, Eq, Debug, Default)]
+pub struct PcmStreamDesc {
+    pub offset: u64,
+    pub total_samples: u64,
+    pub out_offset: u64,
+    pub out_capacity: u64,
+    pub channels: u32,
+    pub bits_per_sample: u32,
+    pub bytes_per_sample: u32,
+    pub sample_rate: u32,
+}
+
+/// `totals[s][3]` of `flacenc_hip_encode_streams`: the slot held only a prefix of the stream's frames.
+pub const ENCODE_NO_ROOM: u64 = 256;
 
 /// What `Gpu::decode_pcm` gives back: how far the call got and why it stopped (`flacenc_hip_decode_pcm`'s `totals`).
 #[derive(Clone, Copy, PartialEq, Eq, Debug)]
