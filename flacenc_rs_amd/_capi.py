@@ -57,6 +57,7 @@ COMM_ID_BYTES = 128  # FLACENC_HIP_COMM_ID_BYTES
 DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 8
 DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
 DECODE_NO_ROOM, DECODE_CHAIN = 256, 512  # totals[3] of flacenc_hip_decode_pcm: why the call stopped
+DECODE_RANGE_END = 1024  # totals[r][1] of flacenc_hip_decode_ranges: the chain ended at the span's end before the range
 ENCODE_NO_ROOM = 256  # FLACENC_HIP_ENCODE_NO_ROOM: totals[s][3] of flacenc_hip_encode_streams
 INDEX_ERROR = 1 << 63
 VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flacenc_hip_encode_variable*
@@ -68,7 +69,8 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_set_order_guess_trace", "flacenc_hip_debug_set_stream_chunk",
                  "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers",
                  "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan",
-                 "flacenc_hip_debug_last_decode_streams_plan", "flacenc_hip_debug_set_encode_streams_chunk",
+                 "flacenc_hip_debug_last_decode_streams_plan", "flacenc_hip_debug_last_decode_ranges_plan",
+                 "flacenc_hip_debug_set_encode_streams_chunk",
                  "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
@@ -127,6 +129,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_streams",
     "flacenc_hip_md5_spans",
     "flacenc_hip_decode_streams_md5",
+    "flacenc_hip_decode_ranges",
     "flacenc_hip_encode_streams_frames",
     "flacenc_hip_encode_streams",
     "flacenc_hip_variable_bytes_bound",
@@ -179,6 +182,11 @@ STREAM_DESC_DTYPE = np.dtype([("offset", "<u8"), ("n_bytes", "<u8"), ("out_offse
                               ("bytes_per_sample", "<u4")])
 assert STREAM_DESC_DTYPE.itemsize == 48
 
+
+# flacenc_hip_range_desc (32 bytes): one range of flacenc_hip_decode_ranges
+RANGE_DESC_DTYPE = np.dtype([("first_sample", "<u8"), ("n_samples", "<u8"), ("out_offset", "<u8"), ("stream", "<u4"),
+                             ("reserved", "<u4")])
+assert RANGE_DESC_DTYPE.itemsize == 32
 
 # flacenc_hip_pcm_stream_desc (48 bytes): one stream of flacenc_hip_encode_streams
 PCM_STREAM_DESC_DTYPE = np.dtype([("offset", "<u8"), ("total_samples", "<u8"), ("out_offset", "<u8"),
@@ -260,6 +268,17 @@ def stream_descs(streams) -> np.ndarray:
         table = np.array([tuple(int(v) for v in row) for row in streams], STREAM_DESC_DTYPE)
     if table.size == 0:
         return np.zeros(1, STREAM_DESC_DTYPE)[:0]
+    return table
+
+
+def range_descs(ranges) -> np.ndarray:
+    """A RANGE_DESC_DTYPE array from one, or from rows (first_sample, n_samples, out_offset, stream[, reserved])."""
+    if isinstance(ranges, np.ndarray) and ranges.dtype == RANGE_DESC_DTYPE:
+        table = np.ascontiguousarray(ranges)
+    else:
+        table = np.array([tuple(int(v) for v in (tuple(row) + (0,))[:5]) for row in ranges], RANGE_DESC_DTYPE)
+    if len(table) == 0:  # never empty memory, so that its address is not NULL
+        return np.zeros(1, RANGE_DESC_DTYPE)[:0]
     return table
 
 
@@ -472,6 +491,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_md5_spans.restype = C.c_int
     L.flacenc_hip_decode_streams_md5.argtypes = L.flacenc_hip_decode_streams.argtypes + [vp]
     L.flacenc_hip_decode_streams_md5.restype = C.c_int
+    L.flacenc_hip_decode_ranges.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp,
+                                            C.c_uint64, vp, vp, C.c_int]
+    L.flacenc_hip_decode_ranges.restype = C.c_int
     L.flacenc_hip_encode_streams_frames.argtypes = [vp, C.c_size_t, C.c_uint32]
     L.flacenc_hip_encode_streams_frames.restype = C.c_size_t
     L.flacenc_hip_encode_streams.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp,
@@ -747,6 +769,13 @@ class Handle:
         """encode_streams cuts every run of a class into frame-level calls of at most `frames` frames in place of its
         rule (flacenc_hip_debug.h); 0: the rule again.  More than 8192 is refused."""
         self._check(self._hook("flacenc_hip_debug_set_encode_streams_chunk")(self._h, int(frames)))
+
+    def debug_last_decode_ranges_plan(self):
+        """[launches, synchronisations, transfers, channel counts among the ranges' streams] of the last decode_ranges
+        call on this handle."""
+        plan = np.zeros(4, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_last_decode_ranges_plan")(self._h, plan.ctypes.data))
+        return [int(v) for v in plan]
 
     def debug_last_encode_streams_plan(self):
         """dict(launches, syncs, transfers, classes, full_runs, tail_runs, calls) of the last encode_streams call on
@@ -1190,6 +1219,41 @@ class Handle:
         rc = self._lib.flacenc_hip_decode_streams(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
                                                   max_frames, out_ptr or None, out_bytes, totals_ptr or None,
                                                   call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
+
+    def decode_ranges(self, data, streams, ranges, max_frames: int, out: np.ndarray, totals: np.ndarray | None = None,
+                      check: bool = True):
+        """flacenc_hip_decode_ranges on host arrays: `data` and `streams` as for decode_streams (out_offset and
+        out_capacity are ignored), `ranges` a RANGE_DESC_DTYPE array (or rows first_sample, n_samples, out_offset,
+        stream), `out` the caller's uint8 buffer that holds every range's slot (written in place).  -> (totals uint64
+        [n_ranges, 4] = samples written, stop reason, seek offset, seek position; call totals [frame decodes |
+        INDEX_ERROR, samples]; the call's code); with check=False a failure is returned instead of raised."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table, rtable = stream_descs(streams), range_descs(ranges)
+        if totals is None:
+            totals = np.zeros((len(rtable), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(rtable)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_ranges(self._h, buf.ctypes.data, buf.size, table.ctypes.data, len(table),
+                                                 rtable.ctypes.data, len(rtable), max_frames, out.ctypes.data, out.size,
+                                                 totals.ctypes.data, call.ctypes.data, MEM_HOST)
+        if check:
+            self._check(rc)
+        return totals, [int(call[0]), int(call[1])], rc
+
+    def decode_ranges_device(self, bytes_ptr: int, n_bytes: int, streams, ranges, max_frames: int, out_ptr: int,
+                             out_bytes: int, totals_ptr: int, check: bool = True):
+        """flacenc_hip_decode_ranges on device pointers (both tables stay host memory); blocks on the handle's stream.
+        -> (call totals, the call's code)."""
+        table, rtable = stream_descs(streams), range_descs(ranges)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_ranges(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
+                                                 rtable.ctypes.data, len(rtable), max_frames, out_ptr or None, out_bytes,
+                                                 totals_ptr or None, call.ctypes.data, MEM_DEVICE)
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc

@@ -1,0 +1,426 @@
+// flac_decode_ranges.cpp -- flacenc_hip_decode_ranges: sample ranges of a batch of FLAC streams to packed PCM in one
+// call, with a number of launches, synchronisations and transfers that does not depend on the number of streams or of
+// ranges.
+//
+// The segmented index is flacenc_hip_decode_streams' own (stream_index.h): every stream's verified chain, every chain
+// frame enumerated, and the scans of PCM bytes and of frames with a status over the frame sequence.  Positions are read
+// off the scan of PCM bytes (stream_ranges_core.h).  On top of it:
+//   ranges_streams_kernel    one lane per stream: the chain frames that decode, S (its samples), W (why it stops) and
+//                            where the chain stopped
+//   ranges_locate_kernel     one lane per range: bisects its stream's positions for the frame that holds first_sample
+//                            and the frame that holds the last wanted sample below S; writes the range's frame count,
+//                            its totals and its seek point
+//   one scan                 range-frame bases and (host memory) where each range's PCM starts in compact staging
+//   ranges_verdict_kernel    one thread: more range-frames than max_frames end the call with the flag
+//   ranges_enumerate_kernel  one lane per range-frame: its range, by bisection, and its chain frame
+//   ranges_decode_kernel     one launch per channel count present among the ranges' streams (ranges are numbered in
+//                            `rslot` order: the range table sorted by their stream's channel count), with the lane rules
+//                            of streams_decode_kernel and a window per frame: the recurrence runs from the frame's first
+//                            sample -- it is serial -- to the last sample wanted, and only samples inside the range are
+//                            stored
+#include "api_internal.h"
+#include "flac_decode.h"
+#include "flac_decode_core.h"
+#include "stream_batch_core.h"
+#include "stream_index.h"
+#include "stream_ranges_core.h"
+
+namespace flacenc_hip {
+namespace {
+
+using namespace streamindex;
+using flacdec::FrameRec;
+using Desc = flacenc_hip_stream_desc;
+using Range = flacenc_hip_range_desc;
+
+inline uint32_t ceil_div(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
+
+// per stream, what the ranges on it share
+struct StreamEnd {
+  uint64_t first;     // its first frame in the sequence
+  uint64_t good;      // the chain frames in front of the first one with a status
+  uint64_t why;       // W: 0, CHAIN, or the status of frame `good`
+  uint64_t consumed;  // where the chain stopped, from the span's start
+};
+
+// range-frames in front of the ranges of c channels, c = 1 .. 9, in rslot order
+struct ClassLo {
+  uint32_t lo[10];
+};
+
+__global__ void __launch_bounds__(256) ranges_streams_kernel(const Desc* __restrict__ descs,
+                                                             const uint32_t* __restrict__ perm, uint32_t n_streams,
+                                                             const uint64_t* __restrict__ base,
+                                                             const uint64_t* __restrict__ pcm,
+                                                             const uint64_t* __restrict__ bad,
+                                                             const uint32_t* __restrict__ f_node,
+                                                             const uint64_t* __restrict__ cand_pos,
+                                                             const uint64_t* __restrict__ s_end,
+                                                             const uint32_t* __restrict__ s_why,
+                                                             const uint32_t* __restrict__ counters,
+                                                             StreamEnd* __restrict__ ends) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_streams) return;
+  const uint32_t s = perm[i];
+  StreamEnd e{0, 0, 0, 0};
+  if (!counters[C_ERR]) {
+    const Desc& d = descs[s];
+    const uint64_t first = base[i], count = base[i + 1] - first;
+    e.first = first;
+    e.good = streambatch::accepted_frames(pcm, bad, first, count, ~0ull);
+    if (e.good < count) {  // a frame of the chain with a status: a block above the stream's max_block_size
+      e.why = FLACENC_HIP_DECODE_UNSUPPORTED;
+      e.consumed = cand_pos[f_node[first + e.good]] - d.offset;
+    } else {
+      e.why = s_why[s];
+      e.consumed = s_end[s] - d.offset;
+    }
+  }
+  ends[s] = e;
+}
+
+// lane q: the range rperm[q]
+__global__ void __launch_bounds__(256) ranges_locate_kernel(const Desc* __restrict__ descs,
+                                                            const Range* __restrict__ ranges,
+                                                            const uint32_t* __restrict__ rperm, uint32_t n_ranges,
+                                                            const StreamEnd* __restrict__ ends,
+                                                            const uint64_t* __restrict__ pcm,
+                                                            const uint32_t* __restrict__ f_node,
+                                                            const uint64_t* __restrict__ cand_pos,
+                                                            const uint32_t* __restrict__ counters,
+                                                            uint64_t* __restrict__ r_frames,
+                                                            uint64_t* __restrict__ r_bytes,
+                                                            uint64_t* __restrict__ r_first,
+                                                            uint64_t* __restrict__ r_written,
+                                                            uint64_t* __restrict__ totals, uint64_t* __restrict__ meta) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n_ranges) return;
+  const uint32_t r = rperm[q];
+  const Range x = ranges[r];
+  const Desc& d = descs[x.stream];
+  const uint64_t fb = static_cast<uint64_t>(d.channels) * d.bytes_per_sample;
+  uint64_t frames = 0, written = 0, first_frame = 0, why = 0, seek_off = 0, seek_pos = 0;
+  if (!counters[C_ERR]) {
+    const StreamEnd e = ends[x.stream];
+    const streamranges::Located l = streamranges::locate(pcm, e.first, e.good, fb, x.first_sample, x.n_samples);
+    frames = l.frames;
+    written = l.written;
+    first_frame = e.first + l.f0;
+    why = streamranges::stop_reason(written, x.n_samples, e.why);
+    seek_pos = streamranges::position(pcm, e.first, l.f0, fb);
+    seek_off = l.f0 < e.good ? cand_pos[f_node[first_frame]] - d.offset : e.consumed;
+    if (written) atomicAdd(reinterpret_cast<unsigned long long*>(meta + M_SAMPLES), static_cast<unsigned long long>(written));
+  }
+  r_frames[q] = frames;
+  r_bytes[q] = written * fb;
+  r_first[q] = first_frame;
+  r_written[q] = written;
+  totals[4 * static_cast<size_t>(r) + 0] = written;
+  totals[4 * static_cast<size_t>(r) + 1] = why;
+  totals[4 * static_cast<size_t>(r) + 2] = seek_off;
+  totals[4 * static_cast<size_t>(r) + 3] = seek_pos;
+}
+
+// one thread: more range-frames than max_frames end the call with the flag; else the range-frames in front of every
+// channel class go where the host reads them
+__global__ void ranges_verdict_kernel(const uint64_t* __restrict__ r_base, uint32_t n_ranges, uint64_t max_frames,
+                                      ClassLo rslot_lo, uint32_t* __restrict__ counters, uint64_t* __restrict__ meta) {
+  const uint64_t total = r_base[n_ranges];
+  if (counters[C_ERR]) {
+    counters[C_FRAMES] = 0;
+    return;
+  }
+  const uint32_t err = total > max_frames;
+  counters[C_ERR] = err;
+  counters[C_FRAMES] = err ? 0u : static_cast<uint32_t>(total);  // from here on: the range-frames
+  meta[M_ERR] = err;
+  meta[M_FRAMES] = total;
+  for (uint32_t c = 0; c < 10; ++c) meta[M_CLASS + c] = r_base[rslot_lo.lo[c]];
+}
+
+__global__ void __launch_bounds__(256) ranges_enumerate_kernel(const uint64_t* __restrict__ r_base, uint32_t n_ranges,
+                                                               const uint64_t* __restrict__ r_first,
+                                                               const uint32_t* __restrict__ counters,
+                                                               uint32_t* __restrict__ rf_range,
+                                                               uint32_t* __restrict__ rf_frame) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= counters[C_FRAMES]) return;
+  const uint32_t q = streambatch::slot_of_frame(r_base, n_ranges, k);
+  rf_range[k] = q;
+  rf_frame[k] = static_cast<uint32_t>(r_first[q] + (k - r_base[q]));
+}
+
+// ---------------------------------------------------------------- reconstruction: one lane per subframe
+// Samples [skip, skip + take) of channel c of a frame of `bs` samples into packed PCM: sample t at dst + ((t - skip) *
+// channels + c) * B, the low B bytes of its value, little-endian.  The recurrence runs from sample 0 and stops at
+// skip + take.  Whole samples where the address allows, else bytes: a neighbouring sample's bytes are another lane's and
+// are never read back.  Both lanes of a stereo pair have the same bounds, so the exchange stays convergent.
+template <int MAXP>
+__device__ void decode_window(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip,
+                              uint32_t take, uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t channels, uint32_t B,
+                              uint8_t* dst) {
+  flacdec::SubDecoder<MAXP> d;
+  if (bs) d.init(fp, flen, start, bs, sbps);
+  const bool stereo = ch_tag >= 8;
+  uint8_t* p = dst + static_cast<size_t>(c) * B;
+  const size_t step = static_cast<size_t>(channels) * B;
+  const bool whole = (B == 2 || B == 4) && (reinterpret_cast<uintptr_t>(p) & (B - 1)) == 0;
+  const uint32_t stop = skip + take;
+  for (uint32_t t = 0; t < stop; ++t) {
+    int32_t v = d.next();
+    if (stereo) {
+      const int32_t o = __shfl_xor(v, 1);
+      int32_t a = c == 0 ? v : o, b = c == 0 ? o : v;
+      flacdec::undo_stereo(ch_tag, a, b);
+      v = c == 0 ? a : b;
+    }
+    if (t < skip) continue;
+    const uint32_t u = static_cast<uint32_t>(v);
+    if (whole && B == 2) {
+      *reinterpret_cast<uint16_t*>(p) = static_cast<uint16_t>(u);
+    } else if (whole) {
+      *reinterpret_cast<uint32_t*>(p) = u;
+    } else {
+      for (uint32_t k = 0; k < B; ++k) p[k] = static_cast<uint8_t>(u >> (8u * k));
+    }
+    p += step;
+  }
+}
+
+// The range-frames [k_lo, k_hi) all belong to streams of `channels` channels; lane (range-frame, c) as in
+// streams_decode_kernel.  A range's PCM starts at out + where[q] (`where` given: the compact staging of the host path)
+// or at out + its out_offset.
+__global__ void __launch_bounds__(256) ranges_decode_kernel(const uint8_t* __restrict__ bytes,
+                                                            const Desc* __restrict__ descs,
+                                                            const Range* __restrict__ ranges,
+                                                            const uint32_t* __restrict__ rperm,
+                                                            const uint64_t* __restrict__ base,
+                                                            const uint64_t* __restrict__ pcm,
+                                                            const uint32_t* __restrict__ f_node,
+                                                            const uint32_t* __restrict__ f_slot,
+                                                            const uint32_t* __restrict__ rf_range,
+                                                            const uint32_t* __restrict__ rf_frame,
+                                                            const uint64_t* __restrict__ r_written,
+                                                            const uint64_t* __restrict__ cand_pos,
+                                                            const FrameRec* __restrict__ recs, uint32_t k_lo,
+                                                            uint32_t k_hi, uint32_t channels,
+                                                            const uint64_t* __restrict__ where, uint8_t* __restrict__ out) {
+  const uint32_t per_block = blockDim.x / channels;  // frames never straddle workgroups
+  const uint32_t lf = threadIdx.x / channels, c = threadIdx.x % channels;
+  const uint64_t k = static_cast<uint64_t>(k_lo) + static_cast<uint64_t>(blockIdx.x) * per_block + lf;
+  uint32_t bs = 0, skip = 0, take = 0, ch_tag = 0, flen = 0, start = 0, bps = 0, B = 1;
+  const uint8_t* fp = bytes;
+  uint8_t* dst = out;
+  if (lf < per_block && k < k_hi) {
+    const uint32_t q = rf_range[k], m = rf_frame[k];
+    const Range& x = ranges[rperm[q]];
+    const Desc& d = descs[x.stream];
+    const uint32_t node = f_node[m];
+    const FrameRec& r = recs[node];
+    const uint64_t fb = static_cast<uint64_t>(d.channels) * d.bytes_per_sample;
+    const uint64_t pos = (pcm[m] - pcm[base[f_slot[m]]]) / fb;
+    const streamranges::Window w = streamranges::window(pos, r.block_size, x.first_sample, x.first_sample + r_written[q]);
+    bs = r.block_size;
+    skip = w.skip;
+    take = w.take;
+    ch_tag = (r.info >> 4) & 15u;
+    flen = r.len;
+    start = r.sub_bit[c];
+    bps = d.bits_per_sample;
+    B = d.bytes_per_sample;
+    fp = bytes + cand_pos[node];
+    dst = out + (where ? where[q] : x.out_offset) + w.dst * fb;
+  }
+  uint32_t order = 0;
+  const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
+  if (bs) {
+    flacdec::BitReader r;
+    r.init(fp, flen, start);
+    flacdec::SubInfo si;
+    flacdec::parse_subframe_header(r, bs, sbps, si);
+    order = si.order;
+  }
+  const int bucket = flacdec::order_bucket(order);
+  if (__any(bucket == 32)) decode_window<32>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
+  else if (__any(bucket == 16)) decode_window<16>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
+  else if (__any(bucket == 8)) decode_window<8>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
+  else decode_window<4>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
+}
+
+}  // namespace
+}  // namespace flacenc_hip
+
+using namespace flacenc_hip;
+
+extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
+                                         const void* streams, size_t n_streams, const void* ranges, size_t n_ranges,
+                                         size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
+                                         uint64_t call_totals[2], int memory_kind) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  uint64_t* plan = h->last_ranges_plan;  // launches, synchronisations, transfers, channel classes of the ranges
+  plan[0] = plan[1] = plan[2] = plan[3] = 0;
+  if ((memory_kind != FLACENC_HIP_MEM_HOST && memory_kind != FLACENC_HIP_MEM_DEVICE) || !bytes || !streams || !ranges ||
+      !out || !totals || !call_totals || n_streams > streambatch::MAX_STREAMS || n_ranges > streamranges::MAX_RANGES ||
+      max_frames > streambatch::MAX_FRAMES || n_bytes > (static_cast<uint64_t>(0xFFFFFFFFu) << 12)) {
+    h->last_error = "decode_ranges: null pointer, unknown memory kind, more than 2^24 streams or ranges, max_frames above "
+                    "2^30 or n_bytes >= 16 TiB";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  const Desc* table = static_cast<const Desc*>(streams);
+  const Range* rtable = static_cast<const Range*>(ranges);
+  int rc = streamranges::check_spans(table, n_streams, n_bytes);
+  if (rc == FLACENC_HIP_ERR_UNSUPPORTED) {
+    h->last_error = "decode_ranges: a stream's bits_per_sample not in 4..=24";
+    return rc;
+  }
+  if (rc != FLACENC_HIP_OK) {
+    h->last_error = "decode_ranges: spans not ascending, overlapping or past n_bytes, channels not in 1..=8, "
+                    "max_block_size not in 1..=65536 or bytes_per_sample not in ceil(bits / 8)..=4";
+    return rc;
+  }
+  if ((rc = streamranges::check_ranges(rtable, n_ranges, table, n_streams, out_bytes)) != FLACENC_HIP_OK) {
+    h->last_error = "decode_ranges: a range's stream >= n_streams, reserved != 0, first_sample + n_samples overflows or "
+                    "its slot reaches past out_bytes";
+    return rc;
+  }
+  call_totals[0] = call_totals[1] = 0;
+  if (n_ranges == 0) return FLACENC_HIP_OK;
+  const bool host = memory_kind == FLACENC_HIP_MEM_HOST;
+  const uint32_t ns = static_cast<uint32_t>(n_streams), nr = static_cast<uint32_t>(n_ranges);
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t st = h->stream;
+
+  // ---- the range table on its way to the device: the descriptors and the rslot order (sorted by channel count) ----
+  h->ranges_table.resize(n_ranges * sizeof(Range) + n_ranges * 4);
+  std::memcpy(h->ranges_table.data(), rtable, n_ranges * sizeof(Range));
+  uint32_t* p_rperm = reinterpret_cast<uint32_t*>(h->ranges_table.data() + n_ranges * sizeof(Range));
+  ClassLo rslot_lo{};  // rslots [lo[c], lo[c + 1]) hold the ranges on streams of c channels
+  for (size_t r = 0; r < n_ranges; ++r) ++rslot_lo.lo[table[rtable[r].stream].channels + 1];
+  uint32_t classes = 0;
+  for (uint32_t c = 1; c <= 8; ++c) {
+    classes += rslot_lo.lo[c + 1] != 0;
+    rslot_lo.lo[c + 1] += rslot_lo.lo[c];
+  }
+  {
+    uint32_t at[9];
+    for (uint32_t c = 1; c <= 8; ++c) at[c] = rslot_lo.lo[c];
+    for (size_t r = 0; r < n_ranges; ++r) p_rperm[at[table[rtable[r].stream].channels]++] = static_cast<uint32_t>(r);
+  }
+
+  // ---- the index; behind `base`, host memory: where[n_ranges + 1] | totals[n_ranges][4] ----
+  const size_t F = max_frames;
+  size_t own = 0;
+  auto take = [&own](size_t bytes_) {
+    const size_t at = own;
+    own += a256(bytes_ + 8);
+    return at;
+  };
+  const size_t o_ends = take(n_streams * sizeof(StreamEnd));
+  const size_t o_rframes = take(n_ranges * 8), o_rbytes = take(n_ranges * 8), o_rfirst = take(n_ranges * 8);
+  const size_t o_rwritten = take(n_ranges * 8), o_rbase = take((n_ranges + 1) * 8);
+  const size_t o_rfrange = take(F * 4), o_rfframe = take(F * 4);
+  Request rq{};
+  rq.bytes = bytes;
+  rq.n_bytes = n_bytes;
+  rq.table = table;
+  rq.n_streams = n_streams;
+  rq.max_frames = max_frames;
+  rq.host = host;
+  rq.who = "decode_ranges";
+  rq.extra_words = host ? (n_ranges + 1) + 4 * n_ranges : 0;
+  rq.extra_table = h->ranges_table.data();
+  rq.extra_table_bytes = h->ranges_table.size();
+  rq.extra_scratch = own;
+  Index ix;
+  Drain drain{h};
+  if ((rc = build(h, plan, rq, ix)) != FLACENC_HIP_OK) return rc;
+  plan[3] = classes;
+  const Range* d_ranges = reinterpret_cast<const Range*>(ix.extra_table);
+  const uint32_t* rperm = reinterpret_cast<const uint32_t*>(ix.extra_table + n_ranges * sizeof(Range));
+  uint64_t* where = host ? ix.extra : nullptr;
+  uint64_t* d_totals = host ? ix.extra + (n_ranges + 1) : totals;
+  StreamEnd* ends = reinterpret_cast<StreamEnd*>(ix.scratch + o_ends);
+  uint64_t* r_frames = reinterpret_cast<uint64_t*>(ix.scratch + o_rframes);
+  uint64_t* r_bytes = reinterpret_cast<uint64_t*>(ix.scratch + o_rbytes);
+  uint64_t* r_first = reinterpret_cast<uint64_t*>(ix.scratch + o_rfirst);
+  uint64_t* r_written = reinterpret_cast<uint64_t*>(ix.scratch + o_rwritten);
+  uint64_t* r_base = reinterpret_cast<uint64_t*>(ix.scratch + o_rbase);
+  uint32_t* rf_range = reinterpret_cast<uint32_t*>(ix.scratch + o_rfrange);
+  uint32_t* rf_frame = reinterpret_cast<uint32_t*>(ix.scratch + o_rfframe);
+#define SR_LAUNCH(...)                 \
+  do {                                 \
+    hipLaunchKernelGGL(__VA_ARGS__);   \
+    ++plan[0];                         \
+  } while (0)
+  // ---- which frames every range touches ----
+  SR_LAUNCH(ranges_streams_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, ix.descs, ix.perm, ns, ix.base, ix.pcm,
+            ix.bad, ix.f_node, ix.cand_pos, ix.s_end, ix.s_why, ix.counters, ends);
+  SR_LAUNCH(ranges_locate_kernel, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges, rperm, nr, ends, ix.pcm,
+            ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written, d_totals, ix.meta);
+  HIP_TRY(h, launch_scan2(r_frames, host ? r_bytes : nullptr, nr, r_base, where, st));
+  ++plan[0];
+  SR_LAUNCH(ranges_verdict_kernel, dim3(1), dim3(1), 0, st, r_base, nr, static_cast<uint64_t>(max_frames), rslot_lo,
+            ix.counters, ix.meta);
+  if (F)
+    SR_LAUNCH(ranges_enumerate_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, r_base, nr, r_first, ix.counters,
+              rf_range, rf_frame);
+  HIP_TRY(h, hipGetLastError());
+  const uint64_t* r_meta = static_cast<const uint64_t*>(h->pin_meta[0]);
+  HIP_TRY(h, hipMemcpyAsync(h->pin_meta[0], ix.meta, ix.result_words * 8, hipMemcpyDeviceToHost, st));
+  ++plan[2];
+  HIP_TRY(h, hipStreamSynchronize(st));
+  ++plan[1];
+  const uint64_t* r_where = r_meta + M_WORDS + (n_streams + 1);
+  const uint64_t* r_totals = r_where + (n_ranges + 1);
+  if (r_meta[M_ERR]) {  // nothing reaches `out`; every range's totals are zero
+    if (host) {
+      std::memset(totals, 0, n_ranges * 32);
+    } else {
+      HIP_TRY(h, hipMemsetAsync(totals, 0, n_ranges * 32, st));
+      HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    call_totals[0] = FLACENC_HIP_INDEX_ERROR;
+    drain.armed = false;
+    return FLACENC_HIP_OK;
+  }
+
+  // ---- decode the ranges' frames straight into packed PCM: one launch per channel count present ----
+  uint8_t* d_out = out;
+  const uint64_t pcm_bytes = host ? r_where[n_ranges] : 0;
+  if (host) {
+    if ((rc = ensure(h, h->d_cont[0], static_cast<size_t>(pcm_bytes) + 16)) != FLACENC_HIP_OK) return rc;
+    d_out = static_cast<uint8_t*>(h->d_cont[0].ptr);
+  }
+  for (uint32_t c = 1; c <= 8; ++c) {
+    if (rslot_lo.lo[c] == rslot_lo.lo[c + 1]) continue;
+    const uint32_t k_lo = static_cast<uint32_t>(r_meta[M_CLASS + c]), k_hi = static_cast<uint32_t>(r_meta[M_CLASS + c + 1]);
+    const uint32_t per_block = 256 / c;
+    // (a class whose ranges touch no frame still counts as a launch of the plan: the plan depends on the classes only)
+    SR_LAUNCH(ranges_decode_kernel, dim3(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1), dim3(per_block * c), 0, st,
+              ix.d_bytes, ix.descs, d_ranges, rperm, ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written,
+              ix.cand_pos, ix.recs, k_lo, k_hi, c, where, d_out);
+  }
+#undef SR_LAUNCH
+  HIP_TRY(h, hipGetLastError());
+  if (host) {
+    // one transfer of the ranges' PCM back to back into pinned staging, then every range to its slot on the host
+    if ((rc = ensure_pinned(h, h->pin_out, &h->pin_out_cap, static_cast<size_t>(pcm_bytes))) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure_copy_pool(h, "decode_ranges")) != FLACENC_HIP_OK) return rc;
+    if (pcm_bytes) HIP_TRY(h, hipMemcpyAsync(h->pin_out[0], d_out, static_cast<size_t>(pcm_bytes), hipMemcpyDeviceToHost, st));
+    ++plan[2];
+  }
+  HIP_TRY(h, hipStreamSynchronize(st));
+  ++plan[1];
+  drain.armed = false;
+  if (host) {
+    const uint8_t* staged = static_cast<const uint8_t*>(h->pin_out[0]);
+    for (size_t q = 0; q < n_ranges; ++q) {
+      const uint64_t n = r_where[q + 1] - r_where[q];
+      if (n) h->copy_pool->copy(out + rtable[p_rperm[q]].out_offset, staged + r_where[q], static_cast<size_t>(n));
+    }
+    std::memcpy(totals, r_totals, n_ranges * 32);
+  }
+  call_totals[0] = r_meta[M_FRAMES];
+  call_totals[1] = r_meta[M_SAMPLES];
+  return FLACENC_HIP_OK;
+}

@@ -16,14 +16,19 @@
 // destination, channel count and width: no intermediate rows.
 // flacenc_hip_decode_streams_md5 is the same call with one more step behind the decode launches: one lane per stream
 // hashes the bytes the stream's lanes just wrote (md5_streams.cpp), on the device, before the PCM is downloaded.
+// The index -- everything up to the two scans over the frame sequence -- is streamindex::build (stream_index.h), which
+// flacenc_hip_decode_ranges (flac_decode_ranges.cpp) runs too; its kernels live here.
 #include "api_internal.h"
 #include "flac_decode.h"
 #include "flac_decode_core.h"
 #include "md5_core.h"
 #include "stream_batch_core.h"
+#include "stream_index.h"
 
 namespace flacenc_hip {
 namespace {
+
+using namespace streamindex;  // the counters' and meta words' names, Request / Index, Drain
 
 using flacdec::FrameRec;
 using Desc = flacenc_hip_stream_desc;
@@ -32,10 +37,6 @@ __constant__ flacdec::CrcTables kCrc = flacdec::make_crc_tables();
 
 constexpr uint32_t kEnd = 0xFFFFFFFEu, kDead = 0xFFFFFFFFu;  // chain sentinels, as in flac_decode.cpp
 constexpr uint32_t kPosPerThread = 16, kPosPerBlock = 256 * kPosPerThread;
-// counters (uint32): the candidates found, -, 1 when the call ends with FLACENC_HIP_INDEX_ERROR, the frames enumerated
-enum : uint32_t { C_CANDS = 0, C_ERR = 2, C_FRAMES = 3 };
-// meta (uint64), what the host reads back: frames, samples, the error flag, chain frames, candidates
-enum : uint32_t { M_FRAMES = 0, M_SAMPLES = 1, M_ERR = 2, M_CHAIN = 3, M_CANDS = 4, M_WORDS = 64 };
 
 inline uint32_t ceil_div(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
 
@@ -411,15 +412,6 @@ __global__ void __launch_bounds__(256) streams_decode_kernel(const uint8_t* __re
   else decode_subframe<4>(fp, flen, start, bs, sbps, ch_tag, c, channels, B, dst);
 }
 
-// the handle's stream is drained before an error hands the handle back
-struct Drain {
-  flacenc_hip_handle* h;
-  bool armed = true;
-  ~Drain() {
-    if (armed) (void)hipStreamSynchronize(h->stream);
-  }
-};
-
 // the digest of the empty string, for the streams of a call that wrote nothing
 void empty_digests(uint8_t* digests, size_t n) {
   uint8_t d[16];
@@ -462,137 +454,41 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t st = h->stream;
 
-  // ---- the table on its way to the device: the descriptors and the slot order (streams sorted by channel count) ----
-  const size_t table_bytes = n_streams * sizeof(Desc) + n_streams * 4;
-  const size_t result_words = M_WORDS + (n_streams + 1) + (host ? 4 * n_streams + (n_streams + 1) : 0);
+  // ---- the segmented index (stream_index.h); behind `base`, host memory: totals | where ----
+  Request rq{};
+  rq.bytes = bytes;
+  rq.n_bytes = n_bytes;
+  rq.table = table;
+  rq.n_streams = n_streams;
+  rq.max_frames = max_frames;
+  rq.host = host;
+  rq.who = "decode_streams";
+  rq.extra_words = host ? 4 * n_streams + (n_streams + 1) : 0;
   // (host memory, md5: the digests come down into the same pinned slot, behind the results)
-  const size_t result_bytes = result_words * 8 + (host && md5 ? n_streams * 16 : 0);
-  if ((rc = ensure_pinned(h, h->pin_meta, &h->pin_meta_cap, table_bytes > result_bytes ? table_bytes : result_bytes)) !=
-      FLACENC_HIP_OK)
-    return rc;
-  Desc* p_desc = static_cast<Desc*>(h->pin_meta[1]);
-  uint32_t* p_perm = reinterpret_cast<uint32_t*>(p_desc + n_streams);
-  std::memcpy(p_desc, table, n_streams * sizeof(Desc));
-  uint32_t slot_lo[10] = {0};  // slots [slot_lo[c], slot_lo[c + 1]) hold the streams of c channels
-  for (size_t s = 0; s < n_streams; ++s) ++slot_lo[p_desc[s].channels + 1];
-  uint32_t classes = 0;
-  for (uint32_t c = 1; c <= 8; ++c) {
-    classes += slot_lo[c + 1] != 0;
-    slot_lo[c + 1] += slot_lo[c];
-  }
-  {
-    uint32_t at[9];
-    for (uint32_t c = 1; c <= 8; ++c) at[c] = slot_lo[c];
-    for (size_t s = 0; s < n_streams; ++s) p_perm[at[p_desc[s].channels]++] = static_cast<uint32_t>(s);
-  }
-  plan[3] = classes;
-
-  // ---- scratch ----
-  const size_t capacity = index_candidate_capacity(max_frames);
-  const uint32_t cap = static_cast<uint32_t>(capacity), levels = index_jump_levels(capacity);
-  const uint32_t n_blocks = ceil_div(n_bytes, kPosPerBlock);
-  const size_t F = max_frames;
-  size_t need = 0;
-  auto take = [&need](size_t bytes_) {
-    const size_t at = need;
-    need += a256(bytes_ + 8);
-    return at;
-  };
-  const size_t o_counters = take(256 + M_WORDS * 8 + result_words * 8);  // counters | meta | base | totals | where
-  const size_t o_table = take(table_bytes);
-  const size_t o_bcount = take(static_cast<size_t>(n_blocks) * 8), o_boff = take((static_cast<size_t>(n_blocks) + 1) * 8);
-  const size_t o_cpos = take(capacity * 8), o_cstream = take(capacity * 4), o_recs = take(capacity * sizeof(FrameRec));
-  const size_t o_jump = take(static_cast<size_t>(levels) * capacity * 4);
-  const size_t o_sframes = take(n_streams * 8), o_sroot = take(n_streams * 4), o_send = take(n_streams * 8);
-  const size_t o_swhy = take(n_streams * 4), o_sacc = take(n_streams * 4), o_sbytes = take(n_streams * 8);
-  const size_t o_fnode = take(F * 4), o_fslot = take(F * 4), o_fpcm = take(F * 8), o_fbad = take(F * 8);
-  const size_t o_pcm = take((F + 1) * 8), o_bad = take((F + 1) * 8);
-  const size_t o_digests = host && md5 ? take(n_streams * 16) : 0;
-  if ((rc = ensure(h, h->d_idx, need)) != FLACENC_HIP_OK) return rc;
-  char* S = static_cast<char*>(h->d_idx.ptr);
-  uint32_t* counters = reinterpret_cast<uint32_t*>(S + o_counters);
-  uint64_t* meta = reinterpret_cast<uint64_t*>(S + o_counters + 256);
-  uint64_t* base = meta + M_WORDS;
-  uint64_t* d_totals = host ? base + (n_streams + 1) : totals;
-  uint64_t* where = host ? base + (n_streams + 1) + 4 * n_streams : nullptr;
-  const Desc* descs = reinterpret_cast<const Desc*>(S + o_table);
-  const uint32_t* perm = reinterpret_cast<const uint32_t*>(S + o_table + n_streams * sizeof(Desc));
-  uint64_t* block_counts = reinterpret_cast<uint64_t*>(S + o_bcount);
-  uint64_t* block_offsets = reinterpret_cast<uint64_t*>(S + o_boff);
-  uint64_t* cand_pos = reinterpret_cast<uint64_t*>(S + o_cpos);
-  uint32_t* cand_stream = reinterpret_cast<uint32_t*>(S + o_cstream);
-  FrameRec* recs = reinterpret_cast<FrameRec*>(S + o_recs);
-  uint32_t* jump = reinterpret_cast<uint32_t*>(S + o_jump);
-  uint64_t* s_frames = reinterpret_cast<uint64_t*>(S + o_sframes);
-  uint32_t* s_root = reinterpret_cast<uint32_t*>(S + o_sroot);
-  uint64_t* s_end = reinterpret_cast<uint64_t*>(S + o_send);
-  uint32_t* s_why = reinterpret_cast<uint32_t*>(S + o_swhy);
-  uint32_t* s_accepted = reinterpret_cast<uint32_t*>(S + o_sacc);
-  uint64_t* s_bytes = reinterpret_cast<uint64_t*>(S + o_sbytes);
-  uint32_t* f_node = reinterpret_cast<uint32_t*>(S + o_fnode);
-  uint32_t* f_slot = reinterpret_cast<uint32_t*>(S + o_fslot);
-  uint64_t* f_pcm = reinterpret_cast<uint64_t*>(S + o_fpcm);
-  uint64_t* f_bad = reinterpret_cast<uint64_t*>(S + o_fbad);
-  uint64_t* pcm = reinterpret_cast<uint64_t*>(S + o_pcm);
-  uint64_t* bad = reinterpret_cast<uint64_t*>(S + o_bad);
-  uint8_t* d_digests = host ? reinterpret_cast<uint8_t*>(S + o_digests) : digests;
-
-  // ---- the input ----
-  const uint8_t* d_bytes = bytes;
-  if (host) {
-    if ((rc = ensure(h, h->d_dec_io, static_cast<size_t>(n_bytes) + 16)) != FLACENC_HIP_OK) return rc;
-    d_bytes = static_cast<const uint8_t*>(h->d_dec_io.ptr);
-  }
+  rq.pinned_tail = host && md5 ? n_streams * 16 : 0;
+  rq.extra_scratch = host && md5 ? n_streams * 16 : 0;
+  Index ix;
   Drain drain{h};
+  if ((rc = build(h, plan, rq, ix)) != FLACENC_HIP_OK) return rc;
+  const size_t result_words = ix.result_words;
+  uint32_t* counters = ix.counters;
+  uint64_t *meta = ix.meta, *base = ix.base;
+  uint64_t* d_totals = host ? ix.extra : totals;
+  uint64_t* where = host ? ix.extra + 4 * n_streams : nullptr;
+  const Desc* descs = ix.descs;
+  const uint32_t* perm = ix.perm;
+  const uint32_t* slot_lo = ix.slot_lo;
+  const uint8_t* d_bytes = ix.d_bytes;
+  uint64_t *cand_pos = ix.cand_pos, *s_end = ix.s_end, *s_bytes = ix.s_bytes, *pcm = ix.pcm, *bad = ix.bad;
+  FrameRec* recs = ix.recs;
+  uint32_t *s_why = ix.s_why, *s_accepted = ix.s_accepted, *f_node = ix.f_node, *f_slot = ix.f_slot;
+  uint8_t* d_digests = host ? reinterpret_cast<uint8_t*>(ix.scratch) : digests;
 #define SB_LAUNCH(...)                 \
   do {                                 \
     hipLaunchKernelGGL(__VA_ARGS__);   \
     ++plan[0];                         \
   } while (0)
-  HIP_TRY(h, hipMemsetAsync(counters, 0, 256 + M_WORDS * 8, st));
-  HIP_TRY(h, hipMemcpyAsync(S + o_table, p_desc, table_bytes, hipMemcpyHostToDevice, st));
-  ++plan[2];
-  if (host && n_bytes) {
-    const void* src = bytes;
-    if (!is_pinned(bytes)) {  // pageable: through pinned staging on the handle's host threads
-      if ((rc = ensure_pinned(h, h->pin_in, &h->pin_in_cap, static_cast<size_t>(n_bytes))) != FLACENC_HIP_OK) return rc;
-      if ((rc = ensure_copy_pool(h, "decode_streams")) != FLACENC_HIP_OK) return rc;
-      h->copy_pool->copy(h->pin_in[0], bytes, static_cast<size_t>(n_bytes));
-      src = h->pin_in[0];
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_dec_io.ptr, src, static_cast<size_t>(n_bytes), hipMemcpyHostToDevice, st));
-    ++plan[2];
-  }
-
-  // ---- the segmented index ----
-  if (n_blocks) {
-    SB_LAUNCH(streams_cand_kernel<false>, dim3(n_blocks), dim3(256), 0, st, d_bytes, n_bytes, descs, ns, block_counts,
-              nullptr, nullptr, nullptr, cap, counters);
-    SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, block_counts, nullptr, nullptr,
-              static_cast<uint64_t>(n_blocks), nullptr, block_offsets, nullptr);
-    SB_LAUNCH(streams_cand_kernel<true>, dim3(n_blocks), dim3(256), 0, st, d_bytes, n_bytes, descs, ns, nullptr,
-              block_offsets, cand_pos, cand_stream, cap, counters);
-    SB_LAUNCH(streams_skim_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, d_bytes, descs, cand_pos, cand_stream,
-              counters, cap, recs);
-    HIP_TRY(h, launch_frame_crc16(d_bytes, cand_pos, cap, counters + C_CANDS, recs, st));
-    ++plan[0];
-    SB_LAUNCH(streams_link_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, descs, cand_pos, cand_stream, recs,
-              counters, cap, jump);
-    HIP_TRY(h, launch_jump_levels(jump, counters + C_CANDS, capacity, st));
-    plan[0] += levels - 1;
-  }
-  SB_LAUNCH(streams_chain_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, ns, cand_pos, recs, jump, levels,
-            counters, cap, s_frames, s_root, s_end, s_why);
-  SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, s_frames, nullptr, perm, static_cast<uint64_t>(ns), nullptr,
-            base, nullptr);
-  SB_LAUNCH(streams_verdict_kernel, dim3(1), dim3(1), 0, st, base, ns, static_cast<uint64_t>(max_frames), cap, counters,
-            meta);
   // ---- the cut ----
-  if (F)
-    SB_LAUNCH(streams_enumerate_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, descs, perm, ns, base, s_root, recs,
-              jump, levels, counters, cap, f_node, f_slot, f_pcm, f_bad);
-  SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, f_pcm, f_bad, nullptr, static_cast<uint64_t>(F),
-            counters + C_FRAMES, pcm, bad);
   SB_LAUNCH(streams_totals_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, perm, ns, base, pcm, bad, f_node,
             cand_pos, s_end, s_why, counters, s_accepted, s_bytes, d_totals, meta);
   if (host)
@@ -676,6 +572,177 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- the index, for both calls (stream_index.h)
+int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq, Index& ix) {
+  const size_t n_streams = rq.n_streams, max_frames = rq.max_frames;
+  const uint64_t n_bytes = rq.n_bytes;
+  const uint32_t ns = static_cast<uint32_t>(n_streams);
+  const bool host = rq.host;
+  hipStream_t st = h->stream;
+  int rc;
+
+  // ---- the table on its way to the device: the descriptors and the slot order (streams sorted by channel count) ----
+  const size_t own_table = (n_streams * sizeof(Desc) + n_streams * 4 + 7) & ~static_cast<size_t>(7);
+  const size_t table_bytes = rq.extra_table_bytes ? own_table + rq.extra_table_bytes : n_streams * sizeof(Desc) + n_streams * 4;
+  const size_t result_words = M_WORDS + (n_streams + 1) + rq.extra_words;
+  const size_t result_bytes = result_words * 8 + rq.pinned_tail;
+  if ((rc = ensure_pinned(h, h->pin_meta, &h->pin_meta_cap, table_bytes > result_bytes ? table_bytes : result_bytes)) !=
+      FLACENC_HIP_OK)
+    return rc;
+  Desc* p_desc = static_cast<Desc*>(h->pin_meta[1]);
+  uint32_t* p_perm = reinterpret_cast<uint32_t*>(p_desc + n_streams);
+  std::memcpy(p_desc, rq.table, n_streams * sizeof(Desc));
+  if (rq.extra_table_bytes) std::memcpy(static_cast<char*>(h->pin_meta[1]) + own_table, rq.extra_table, rq.extra_table_bytes);
+  uint32_t* slot_lo = ix.slot_lo;  // slots [slot_lo[c], slot_lo[c + 1]) hold the streams of c channels
+  for (uint32_t c = 0; c < 10; ++c) slot_lo[c] = 0;
+  for (size_t s = 0; s < n_streams; ++s) ++slot_lo[p_desc[s].channels + 1];
+  uint32_t classes = 0;
+  for (uint32_t c = 1; c <= 8; ++c) {
+    classes += slot_lo[c + 1] != 0;
+    slot_lo[c + 1] += slot_lo[c];
+  }
+  {
+    uint32_t at[9];
+    for (uint32_t c = 1; c <= 8; ++c) at[c] = slot_lo[c];
+    for (size_t s = 0; s < n_streams; ++s) p_perm[at[p_desc[s].channels]++] = static_cast<uint32_t>(s);
+  }
+  ix.classes = classes;
+  plan[3] = classes;
+
+  // ---- scratch ----
+  const size_t capacity = index_candidate_capacity(max_frames);
+  const uint32_t cap = static_cast<uint32_t>(capacity), levels = index_jump_levels(capacity);
+  const uint32_t n_blocks = ceil_div(n_bytes, kPosPerBlock);
+  const size_t F = max_frames;
+  size_t need = 0;
+  auto take = [&need](size_t bytes_) {
+    const size_t at = need;
+    need += a256(bytes_ + 8);
+    return at;
+  };
+  const size_t o_counters = take(256 + M_WORDS * 8 + result_words * 8);  // counters | meta | base | the caller's words
+  const size_t o_table = take(table_bytes);
+  const size_t o_bcount = take(static_cast<size_t>(n_blocks) * 8), o_boff = take((static_cast<size_t>(n_blocks) + 1) * 8);
+  const size_t o_cpos = take(capacity * 8), o_cstream = take(capacity * 4), o_recs = take(capacity * sizeof(FrameRec));
+  const size_t o_jump = take(static_cast<size_t>(levels) * capacity * 4);
+  const size_t o_sframes = take(n_streams * 8), o_sroot = take(n_streams * 4), o_send = take(n_streams * 8);
+  const size_t o_swhy = take(n_streams * 4), o_sacc = take(n_streams * 4), o_sbytes = take(n_streams * 8);
+  const size_t o_fnode = take(F * 4), o_fslot = take(F * 4), o_fpcm = take(F * 8), o_fbad = take(F * 8);
+  const size_t o_pcm = take((F + 1) * 8), o_bad = take((F + 1) * 8);
+  const size_t o_extra = rq.extra_scratch ? take(rq.extra_scratch) : 0;
+  if ((rc = ensure(h, h->d_idx, need)) != FLACENC_HIP_OK) return rc;
+  char* S = static_cast<char*>(h->d_idx.ptr);
+  uint32_t* counters = reinterpret_cast<uint32_t*>(S + o_counters);
+  uint64_t* meta = reinterpret_cast<uint64_t*>(S + o_counters + 256);
+  uint64_t* base = meta + M_WORDS;
+  const Desc* descs = reinterpret_cast<const Desc*>(S + o_table);
+  const uint32_t* perm = reinterpret_cast<const uint32_t*>(S + o_table + n_streams * sizeof(Desc));
+  uint64_t* block_counts = reinterpret_cast<uint64_t*>(S + o_bcount);
+  uint64_t* block_offsets = reinterpret_cast<uint64_t*>(S + o_boff);
+  uint64_t* cand_pos = reinterpret_cast<uint64_t*>(S + o_cpos);
+  uint32_t* cand_stream = reinterpret_cast<uint32_t*>(S + o_cstream);
+  FrameRec* recs = reinterpret_cast<FrameRec*>(S + o_recs);
+  uint32_t* jump = reinterpret_cast<uint32_t*>(S + o_jump);
+  uint64_t* s_frames = reinterpret_cast<uint64_t*>(S + o_sframes);
+  uint32_t* s_root = reinterpret_cast<uint32_t*>(S + o_sroot);
+  uint64_t* s_end = reinterpret_cast<uint64_t*>(S + o_send);
+  uint32_t* s_why = reinterpret_cast<uint32_t*>(S + o_swhy);
+  uint32_t* f_node = reinterpret_cast<uint32_t*>(S + o_fnode);
+  uint32_t* f_slot = reinterpret_cast<uint32_t*>(S + o_fslot);
+  uint64_t* f_pcm = reinterpret_cast<uint64_t*>(S + o_fpcm);
+  uint64_t* f_bad = reinterpret_cast<uint64_t*>(S + o_fbad);
+  uint64_t* pcm = reinterpret_cast<uint64_t*>(S + o_pcm);
+  uint64_t* bad = reinterpret_cast<uint64_t*>(S + o_bad);
+  ix.counters = counters;
+  ix.meta = meta;
+  ix.base = base;
+  ix.extra = base + (n_streams + 1);
+  ix.result_words = result_words;
+  ix.descs = descs;
+  ix.perm = perm;
+  ix.extra_table = S + o_table + own_table;
+  ix.cap = cap;
+  ix.levels = levels;
+  ix.cand_pos = cand_pos;
+  ix.recs = recs;
+  ix.jump = jump;
+  ix.s_root = s_root;
+  ix.s_why = s_why;
+  ix.s_accepted = reinterpret_cast<uint32_t*>(S + o_sacc);
+  ix.s_end = s_end;
+  ix.s_bytes = reinterpret_cast<uint64_t*>(S + o_sbytes);
+  ix.f_node = f_node;
+  ix.f_slot = f_slot;
+  ix.pcm = pcm;
+  ix.bad = bad;
+  ix.scratch = S + o_extra;
+
+  // ---- the input ----
+  const uint8_t* d_bytes = rq.bytes;
+  if (host) {
+    if ((rc = ensure(h, h->d_dec_io, static_cast<size_t>(n_bytes) + 16)) != FLACENC_HIP_OK) return rc;
+    d_bytes = static_cast<const uint8_t*>(h->d_dec_io.ptr);
+  }
+  ix.d_bytes = d_bytes;
+#define SB_LAUNCH(...)                 \
+  do {                                 \
+    hipLaunchKernelGGL(__VA_ARGS__);   \
+    ++plan[0];                         \
+  } while (0)
+  HIP_TRY(h, hipMemsetAsync(counters, 0, 256 + M_WORDS * 8, st));
+  HIP_TRY(h, hipMemcpyAsync(S + o_table, p_desc, table_bytes, hipMemcpyHostToDevice, st));
+  ++plan[2];
+  if (host && n_bytes) {
+    const void* src = rq.bytes;
+    if (!is_pinned(rq.bytes)) {  // pageable: through pinned staging on the handle's host threads
+      if ((rc = ensure_pinned(h, h->pin_in, &h->pin_in_cap, static_cast<size_t>(n_bytes))) != FLACENC_HIP_OK) return rc;
+      if ((rc = ensure_copy_pool(h, rq.who)) != FLACENC_HIP_OK) return rc;
+      h->copy_pool->copy(h->pin_in[0], rq.bytes, static_cast<size_t>(n_bytes));
+      src = h->pin_in[0];
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_dec_io.ptr, src, static_cast<size_t>(n_bytes), hipMemcpyHostToDevice, st));
+    ++plan[2];
+  }
+
+  // ---- the segmented index ----
+  if (n_blocks) {
+    SB_LAUNCH(streams_cand_kernel<false>, dim3(n_blocks), dim3(256), 0, st, d_bytes, n_bytes, descs, ns, block_counts,
+              nullptr, nullptr, nullptr, cap, counters);
+    SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, block_counts, nullptr, nullptr,
+              static_cast<uint64_t>(n_blocks), nullptr, block_offsets, nullptr);
+    SB_LAUNCH(streams_cand_kernel<true>, dim3(n_blocks), dim3(256), 0, st, d_bytes, n_bytes, descs, ns, nullptr,
+              block_offsets, cand_pos, cand_stream, cap, counters);
+    SB_LAUNCH(streams_skim_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, d_bytes, descs, cand_pos, cand_stream,
+              counters, cap, recs);
+    HIP_TRY(h, launch_frame_crc16(d_bytes, cand_pos, cap, counters + C_CANDS, recs, st));
+    ++plan[0];
+    SB_LAUNCH(streams_link_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, descs, cand_pos, cand_stream, recs,
+              counters, cap, jump);
+    HIP_TRY(h, launch_jump_levels(jump, counters + C_CANDS, capacity, st));
+    plan[0] += levels - 1;
+  }
+  SB_LAUNCH(streams_chain_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, ns, cand_pos, recs, jump, levels,
+            counters, cap, s_frames, s_root, s_end, s_why);
+  SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, s_frames, nullptr, perm, static_cast<uint64_t>(ns), nullptr,
+            base, nullptr);
+  SB_LAUNCH(streams_verdict_kernel, dim3(1), dim3(1), 0, st, base, ns, static_cast<uint64_t>(max_frames), cap, counters,
+            meta);
+  // ---- every chain frame, and the scans over the frame sequence ----
+  if (F)
+    SB_LAUNCH(streams_enumerate_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, descs, perm, ns, base, s_root, recs,
+              jump, levels, counters, cap, f_node, f_slot, f_pcm, f_bad);
+  SB_LAUNCH(streams_scan_kernel, dim3(1), dim3(1024), 0, st, f_pcm, f_bad, nullptr, static_cast<uint64_t>(F),
+            counters + C_FRAMES, pcm, bad);
+#undef SB_LAUNCH
+  return FLACENC_HIP_OK;
+}
+
+hipError_t streamindex::launch_scan2(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out_a, uint64_t* out_b,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(streams_scan_kernel, dim3(1), dim3(1024), 0, stream, a, b, nullptr, n, nullptr, out_a, out_b);
+  return hipGetLastError();
+}
 
 // streams_scan_kernel for the batch encoder (encode_streams.cpp): out[i] = the sum of in[j] over j < i, out[n] the total
 hipError_t launch_streams_scan(const uint64_t* in, uint64_t n, uint64_t* out, hipStream_t stream) {

@@ -1091,6 +1091,41 @@ inline std::vector<DecodedPcm> decode_streams(HipContext& gpu, const uint8_t* by
   return r;
 }
 
+// Seeking (flacenc_hip_decode_ranges on host memory): range r asks for samples [first_sample, first_sample + n_samples)
+// of stream `stream`'s span -- positions count from the first sample of the span's first frame -- into out[out_offset ..).
+// Only the frames the ranges touch are decoded.  The streams' out_offset and out_capacity are not looked at.  Throws when
+// the device fails and when the chains or the ranges hold more frames than max_frames (nothing was written then).
+struct DecodedRange {
+  uint64_t samples = 0;      // inter-channel samples written
+  uint32_t stop = 0;         // 0: all of them; the stream's stop reason, or FLACENC_HIP_DECODE_RANGE_END
+  uint64_t seek_offset = 0;  // a seek point: the byte offset in the span, and the position, of the frame that holds
+  uint64_t seek_sample = 0;  // first_sample
+};
+
+inline std::vector<DecodedRange> decode_ranges(HipContext& gpu, const uint8_t* bytes, size_t n_bytes,
+                                               const std::vector<flacenc_hip_stream_desc>& streams,
+                                               const std::vector<flacenc_hip_range_desc>& ranges, size_t max_frames,
+                                               uint8_t* out, size_t out_bytes) {
+  std::vector<uint64_t> totals(4 * ranges.size() + 4, 0);
+  uint64_t call[2] = {0, 0};
+  const flacenc_hip_stream_desc none{};
+  const flacenc_hip_range_desc no_range{};
+  const int rc = flacenc_hip_decode_ranges(gpu.get(), bytes, n_bytes, streams.empty() ? &none : streams.data(),
+                                           streams.size(), ranges.empty() ? &no_range : ranges.data(), ranges.size(),
+                                           max_frames, out, out_bytes, totals.data(), call, FLACENC_HIP_MEM_HOST);
+  if (rc != FLACENC_HIP_OK) throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(gpu.get()));
+  if (call[0] & FLACENC_HIP_INDEX_ERROR)
+    throw error::EncodeError(error::EncodeError::Device, "decode_ranges: more frames than max_frames");
+  std::vector<DecodedRange> r(ranges.size());
+  for (size_t i = 0; i < ranges.size(); ++i) {
+    r[i].samples = totals[4 * i];
+    r[i].stop = static_cast<uint32_t>(totals[4 * i + 1]);
+    r[i].seek_offset = totals[4 * i + 2];
+    r[i].seek_sample = totals[4 * i + 3];
+  }
+  return r;
+}
+
 // The MD5 digests of a batch of spans of host memory in one call (flacenc_hip_md5_spans): span i is bytes[offsets[i],
 // offsets[i] + lengths[i]), its digest the 16 bytes at 16 * i of the result -- what STREAMINFO stores.  One lane of the
 // device hashes one span: the call for the digests of many files, not of one (one span alone is faster on the host).

@@ -1079,6 +1079,56 @@ int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, 
                                    uint64_t* totals, uint64_t call_totals[2], int memory_kind, uint8_t* digests);
 
 /*
+ * Seeking: samples [first_sample, first_sample + n_samples) of streams of a batch, for any number of ranges, in one call
+ * -- the crops a model is fed, the seconds a player previews -- without decoding, storing or moving the rest.  Only the
+ * frames a range touches are decoded, each only up to the last sample wanted, and only the wanted samples are written.
+ *   bytes, n_bytes, streams, n_streams, max_frames, memory_kind   as for flacenc_hip_decode_streams; the call ignores the
+ *                    descriptors' out_offset and out_capacity, so one table serves both calls.  A span starts at a frame
+ *                    boundary: the stream's first frame or a seek point (a frame's byte offset from a SEEKTABLE or from
+ *                    an earlier call).  "Position" counts inter-channel samples from the first sample of the span's first
+ *                    frame; a caller that starts a span at a seek point subtracts the seek point's sample number itself
+ *   ranges           n_ranges descriptors (struct flacenc_hip_range_desc, 32 bytes each), ALWAYS host memory, read before
+ *                    the call returns.  In any order; they may repeat and overlap, and any number may name one stream
+ *   out, out_bytes   range r owns the slot [out_offset, out_offset + n_samples*channels*bytes_per_sample) with its
+ *                    stream's channels and bytes_per_sample, at any byte offset.  Slots must be disjoint; the library does
+ *                    NOT check that (overlapping slots give unspecified bytes in the overlap, never a fault)
+ *   totals           [n_ranges][4], where `out` lives
+ *   call_totals      host memory in both kinds: [0] the frame decodes run, summed over ranges (a frame two ranges touch
+ *                    counts twice), [1] the samples written
+ * With P, S and W the PCM, totals[s][1] and totals[s][3] flacenc_hip_decode_streams gives for the range's stream with
+ * unlimited room: the range gets samples [first_sample, min(first_sample + n_samples, S)) of P at the start of its slot,
+ * byte for byte, and nothing else of `out` is written.  totals[r][0] is the number of samples written.  totals[r][1] is
+ * why it stopped: 0 when all n_samples were written, else W when W is non-zero (FLACENC_HIP_DECODE_CHAIN or a frame's
+ * status bits), else FLACENC_HIP_DECODE_RANGE_END: the span's chain ended exactly at the span's end, before the range
+ * did.  totals[r][2] and [3] are a seek point: the byte offset, from the span's start, of the chain frame that holds
+ * first_sample, and that frame's position; when first_sample >= S, where the chain stopped (totals[s][2] and S).  A
+ * caller may cache them: offset + totals[r][2] as a later span and first_sample - totals[r][3] as a later range give
+ * the same bytes.
+ * max_frames bounds the chain frames of all streams together and, separately, the frame decodes of all ranges together.
+ * FLACENC_HIP_INDEX_ERROR is set in call_totals[0] under the rules of flacenc_hip_decode_streams, or when the ranges
+ * touch more frames than max_frames: then nothing is written, all totals are zero and the caller retries with a larger
+ * max_frames.
+ * n_ranges == 0 is OK.  Errors are those of flacenc_hip_decode_streams (without the checks of the streams' slots), plus
+ * FLACENC_HIP_ERR_BAD_ARGUMENT for a range whose stream >= n_streams, reserved != 0, n_ranges above 2^24, a slot that
+ * reaches past out_bytes, or first_sample + n_samples overflowing.  In every error case nothing is written.  Garbage
+ * gives a stop reason, never a fault, and changes nothing for ranges on other streams.
+ * The call blocks and runs on the handle's stream; its launches, synchronisations and transfers depend on the channel
+ * counts the ranges' streams have and on max_frames, not on n_streams or n_ranges.  There is no stream-taking form yet.
+ */
+#define FLACENC_HIP_DECODE_RANGE_END 1024u
+struct flacenc_hip_range_desc {
+  uint64_t first_sample;     /* position of the range's first sample in its stream's span */
+  uint64_t n_samples;        /* inter-channel samples wanted; 0 is legal */
+  uint64_t out_offset;       /* the range's slot: n_samples*channels*bytes_per_sample bytes of `out` from here */
+  uint32_t stream;           /* index into `streams` */
+  uint32_t reserved;         /* 0 */
+};
+typedef struct flacenc_hip_range_desc flacenc_hip_range_desc;
+int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                              size_t n_streams, const void* ranges, size_t n_ranges, size_t max_frames, uint8_t* out,
+                              uint64_t out_bytes, uint64_t* totals, uint64_t call_totals[2], int memory_kind);
+
+/*
  * The way there in one call: a batch of PCM streams to FLAC frames, what flacenc_hip_encode_pcm does for one stream, for
  * every stream of a table -- a speech corpus, a sample pack, the tracks of an album -- with a number of synchronisations
  * and transfers that does not depend on the number of streams, and a number of launches that depends only on the

@@ -424,6 +424,15 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
         out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int, digests: *mut u8,
     ) -> c_int;
+    /// Sample ranges of a batch of streams in one call: `ranges` points at `n_ranges` `RangeDesc` in host memory, each
+    /// naming a stream of `streams` (whose `out_offset` / `out_capacity` are ignored); `totals` is `[n_ranges][4]` =
+    /// samples written, stop reason (0, the stream's, or `DECODE_RANGE_END`), and a seek point: byte offset in the span
+    /// and position of the frame that holds `first_sample`; `call_totals` = frame decodes (| `INDEX_ERROR`) and samples.
+    pub fn flacenc_hip_decode_ranges(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, ranges: *const c_void,
+        n_ranges: usize, max_frames: usize, out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64,
+        memory_kind: c_int,
+    ) -> c_int;
     /// The sum of `ceil(total_samples / block_size)` over `n_streams` `PcmStreamDesc`: the entries `frame_lengths` needs.
     pub fn flacenc_hip_encode_streams_frames(streams: *const c_void, n_streams: usize, block_size: u32) -> usize;
     /// A batch of PCM streams to frames in one call: `streams` points at `n_streams` `PcmStreamDesc` in host memory; per
@@ -522,6 +531,8 @@ pub const DECODE_MISMATCH: u32 = 128;
 /// `totals[3]` of `flacenc_hip_decode_pcm`: the next frame's samples do not fit / no verified frame starts there.
 pub const DECODE_NO_ROOM: u32 = 256;
 pub const DECODE_CHAIN: u32 = 512;
+/// `totals[r][1]` of `flacenc_hip_decode_ranges`: the span's chain ended at the span's end before the range did.
+pub const DECODE_RANGE_END: u32 = 1024;
 /// Set in `n_frames` by `flacenc_hip_index_frames_async` when the chain of frames does not end at `n_bytes`.
 pub const INDEX_ERROR: u64 = 1 << 63;
 
@@ -623,6 +634,30 @@ pub struct StreamDesc {
     pub bytes_per_sample: u32,
 }
 
+/// `struct flacenc_hip_range_desc` (32 bytes): one range of `flacenc_hip_decode_ranges` -- samples `first_sample..
+/// first_sample + n_samples` of stream `stream`'s span, to `out[out_offset..out_offset + n_samples * channels *
+/// bytes_per_sample]`.
+#[repr(C)]
+#[derive(Clone, Copy, PartialEq, Eq, Debug, Default)]
+pub struct RangeDesc {
+    pub first_sample: u64,
+    pub n_samples: u64,
+    pub out_offset: u64,
+    pub stream: u32,
+    pub reserved: u32,
+}
+
+/// What `Gpu::decode_ranges` gives back per range (`flacenc_hip_decode_ranges`' `totals`).
+#[derive(Clone, Copy, PartialEq, Eq, Debug)]
+pub struct DecodedRange {
+    pub samples: u64,
+    /// 0: every sample asked for was written; the stream's stop reason, or `DECODE_RANGE_END`
+    pub stop: u32,
+    /// a seek point: the byte offset in the span, and the position, of the frame that holds `first_sample`
+    pub seek_offset: u64,
+    pub seek_sample: u64,
+}
+
 /// `struct flacenc_hip_pcm_stream_desc` (48 bytes): one stream of `flacenc_hip_encode_streams` -- its packed PCM is
 /// `pcm[offset..offset + total_samples * channels * bytes_per_sample]`, its slot `out[out_offset..out_offset + out_capacity]`.
 #[repr(C)]
@@ -696,6 +731,33 @@ impl Gpu {
         Ok((0..streams.len())
             .map(|s| DecodedPcm {
                 frames: totals[4 * s], samples: totals[4 * s + 1], consumed: totals[4 * s + 2], stop: totals[4 * s + 3] as u32,
+            })
+            .collect())
+    }
+}
+
+impl Gpu {
+    /// Samples `first_sample..first_sample + n_samples` of streams of a batch with `flacenc_hip_decode_ranges` on host
+    /// memory: only the frames the ranges touch are decoded.  `Err` also on `INDEX_ERROR` (retry with more `max_frames`).
+    pub fn decode_ranges(
+        &mut self, bytes: &[u8], streams: &[StreamDesc], ranges: &[RangeDesc], max_frames: usize, out: &mut [u8],
+    ) -> Result<Vec<DecodedRange>, EncodeError> {
+        let mut totals = vec![0u64; 4 * ranges.len().max(1)];
+        let mut call = [0u64; 2];
+        let rc = unsafe {
+            flacenc_hip_decode_ranges(
+                self.0, bytes.as_ptr(), bytes.len() as u64, streams.as_ptr() as *const c_void, streams.len(),
+                ranges.as_ptr() as *const c_void, ranges.len(), max_frames, out.as_mut_ptr(), out.len() as u64,
+                totals.as_mut_ptr(), call.as_mut_ptr(), MEM_HOST,
+            )
+        };
+        if rc != OK || call[0] & INDEX_ERROR != 0 {
+            return Err(EncodeError::Config(VerifyError::new("gpu", "flacenc_hip_decode_ranges failed")));
+        }
+        Ok((0..ranges.len())
+            .map(|r| DecodedRange {
+                samples: totals[4 * r], stop: totals[4 * r + 1] as u32, seek_offset: totals[4 * r + 2],
+                seek_sample: totals[4 * r + 3],
             })
             .collect())
     }

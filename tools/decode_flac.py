@@ -10,36 +10,20 @@ means "not checked") and writes the WAV (8 / 16 / 24-bit PCM).
 import argparse
 import hashlib
 import os
-import struct
 import sys
 import wave
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from flacenc_rs_amd import _capi  # noqa: E402
+import flac_metadata  # noqa: E402
 
 
 def read_metadata(data: bytes):
     """-> (STREAMINFO fields, byte offset of the first frame)."""
-    if data[:4] != b"fLaC":
-        raise ValueError("not a FLAC stream")
-    pos, info = 4, None
-    while True:
-        head = data[pos]
-        kind, size = head & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
-        body = data[pos + 4:pos + 4 + size]
-        if kind == 0:
-            max_block = struct.unpack(">H", body[2:4])[0]
-            packed = int.from_bytes(body[10:18], "big")
-            info = dict(max_block_size=max_block, sample_rate=packed >> 44, channels=((packed >> 41) & 7) + 1,
-                        bits_per_sample=((packed >> 36) & 31) + 1, total_samples=packed & ((1 << 36) - 1),
-                        md5=bytes(body[18:34]))
-        pos += 4 + size
-        if head & 0x80:
-            break
-    if info is None:
-        raise ValueError("no STREAMINFO block")
+    info, _, pos = flac_metadata.read_blocks(data)
     return info, pos
 
 

@@ -9,6 +9,7 @@ frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
                                   [--window-search] [--order-guess [K]] [--precision-search [FLOOR]] [--rice-escape]
+                                  [--seektable SECONDS]
 
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
@@ -29,6 +30,8 @@ printed.  Composes with the three searches above.
 With --rice-escape (FLACENC_HIP_FLAG_RICE_ESCAPE) a Rice partition is stored escaped -- raw samples of a 5-bit-coded
 width, 9 bits for a partition of digital silence -- where that is strictly shorter; how many partitions and frames
 escaped is printed.  The flag trades the fused kernels for the general path.  tools/decode_flac.py reads the result back.
+With --seektable SECONDS a SEEKTABLE block follows STREAMINFO: one point per SECONDS, from the frame lengths the call
+returned (sample number, byte offset from the first frame, block size).  Without it the file is what it has always been.
 """
 import argparse
 import hashlib
@@ -40,17 +43,25 @@ import wave
 import numpy as np
 
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from flacenc_rs_amd import _capi  # noqa: E402
+import flac_metadata  # noqa: E402
 
 
-def stream_info_block(block_size, min_frame, max_frame, rate, channels, bps, total, md5, min_block=None):
-    """MetadataBlock(StreamInfo)::write, src/component/bitrepr.rs:199-270 (last-block flag set); min_block for a
-    variable-blocking stream (default: block_size, a fixed-blocking one)."""
+def stream_info_block(block_size, min_frame, max_frame, rate, channels, bps, total, md5, min_block=None, last=True):
+    """MetadataBlock(StreamInfo)::write, src/component/bitrepr.rs:199-270 (last-block flag set unless a SEEKTABLE
+    follows); min_block for a variable-blocking stream (default: block_size, a fixed-blocking one)."""
     body = struct.pack(">HH", block_size if min_block is None else min_block, block_size)
     body += min_frame.to_bytes(3, "big") + max_frame.to_bytes(3, "big")
     packed = (rate << 44) | ((channels - 1) << 41) | ((bps - 1) << 36) | total
     body += packed.to_bytes(8, "big") + md5
-    return bytes([0x80]) + len(body).to_bytes(3, "big") + body
+    return bytes([0x80 if last else 0]) + len(body).to_bytes(3, "big") + body
+
+
+def seektable_for(frame_lengths, block_sizes, rate, seconds):
+    """The SEEKTABLE block (the last metadata block) with one point per `seconds`, from what the encoder already has."""
+    points = flac_metadata.seek_points(frame_lengths, block_sizes, max(1, int(round(seconds * rate))))
+    return flac_metadata.seektable_block(points, last=True)
 
 
 def md5_of(frames, bps):
@@ -61,9 +72,10 @@ def md5_of(frames, bps):
     return hashlib.md5(raw.tobytes()).digest()
 
 
-def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_order=8, flags=0):
+def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_order=8, flags=0, seektable=None):
     """pcm int32 [n_samples, 2] -> (.flac bytes, per-frame decision records).  Like
-    encode_with_fixed_block_size (src/coding.rs:645-700): whole blocks, then the shorter last one."""
+    encode_with_fixed_block_size (src/coding.rs:645-700): whole blocks, then the shorter last one.  seektable: seconds
+    between seek points of a SEEKTABLE block behind STREAMINFO (None: none, the file as it has always been)."""
     cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=use_fixed)
     n_full = pcm.shape[0] // block_size
     groups = []
@@ -85,11 +97,15 @@ def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_orde
     md5 = hashlib.md5(inter.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :nbytes].tobytes()).digest()
     sizes = list(map(len, packed))
     # fixed-block streams announce the block size as both min and max (src/coding.rs:676-690)
-    head = b"fLaC" + stream_info_block(block_size, min(sizes), max(sizes), rate, 2, bps, pcm.shape[0], md5)
+    head = b"fLaC" + stream_info_block(block_size, min(sizes), max(sizes), rate, 2, bps, pcm.shape[0], md5,
+                                       last=seektable is None)
+    if seektable is not None:
+        head += seektable_for(sizes, [g.shape[2] for g in groups for _ in range(g.shape[0])], rate, seektable)
     return head + b"".join(packed), np.concatenate(records)
 
 
-def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8, flags=0):
+def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8, flags=0,
+                        seektable=None):
     """pcm int32 [n_samples, channels] -> (.flac bytes, dict of encode_variable's outputs): the block-size search over
     superblocks of block_size samples, written as a variable-blocking stream."""
     cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=use_fixed)
@@ -106,7 +122,9 @@ def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_f
     # RFC 9639 section 8.2: the minimum block size excludes the last block
     min_block = int(blocks[:-1].min()) if len(blocks) > 1 else int(blocks[0])
     head = b"fLaC" + stream_info_block(block_size, int(sizes.min()), int(sizes.max()), rate, channels, bps, total, md5,
-                                       min_block=min_block)
+                                       min_block=min_block, last=seektable is None)
+    if seektable is not None:
+        head += seektable_for(sizes, blocks, rate, seektable)
     return head + v["data"], v
 
 
@@ -140,6 +158,8 @@ def main():
                     help="store a Rice partition escaped (raw samples of a 5-bit-coded width) where that is strictly "
                          "shorter (FLACENC_HIP_FLAG_RICE_ESCAPE: the general path for every shape); composes with every "
                          "other switch")
+    ap.add_argument("--seektable", type=float, default=None, metavar="SECONDS",
+                    help="write a SEEKTABLE block with one seek point per SECONDS (tools/crop_flac.py starts at them)")
     ap.add_argument("--lpc-order", type=int, default=8)
     args = ap.parse_args()
     if args.order_guess and args.order_search:
@@ -174,14 +194,15 @@ def main():
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
     if args.levels:
         data, v = encode_pcm_variable(pcm, bps, rate, handle, block_size=n, levels=args.levels,
-                                      lpc_order=args.lpc_order, flags=flags)
+                                      lpc_order=args.lpc_order, flags=flags, seektable=args.seektable)
         with open(args.paths[-1], "wb") as f:
             f.write(data)
         sizes = np.bincount(v["block_sizes"]).nonzero()[0]
         print(f"{v['frames']} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * bps / 8):.4f} of the PCM "
               f"size; block sizes {dict((int(b), int((v['block_sizes'] == b).sum())) for b in sizes)}")
         return
-    data, res = encode_pcm(pcm, bps, rate, handle, block_size=n, lpc_order=args.lpc_order, flags=flags)
+    data, res = encode_pcm(pcm, bps, rate, handle, block_size=n, lpc_order=args.lpc_order, flags=flags,
+                           seektable=args.seektable)
     nf = len(res)
     with open(args.paths[-1], "wb") as f:
         f.write(data)
