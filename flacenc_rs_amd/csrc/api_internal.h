@@ -327,10 +327,6 @@ hipError_t launch_md5_spans(const uint8_t* bytes, const uint64_t* offsets, uint3
                             const uint64_t* lengths, const uint32_t* slot, uint32_t n_spans, uint8_t* digests,
                             hipStream_t stream);
 
-// ---- flac_decode_streams.cpp ----
-// its single-workgroup scan, for the batch encoder: out[i] = the sum of in[j] over j < i, out[n] the total
-hipError_t launch_streams_scan(const uint64_t* in, uint64_t n, uint64_t* out, hipStream_t stream);
-
 // ---- encode_streams.cpp ----
 // streams_fill_kernel on `stream`: frames table[0 .. n_frames) into rows row0 .. of `rows` (channel-major, `stride` words
 // per row, stride a multiple of 4, rows 16-byte aligned).  All pointers are device memory; one launch.

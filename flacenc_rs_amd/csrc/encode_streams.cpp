@@ -11,10 +11,11 @@
 //                         from the old one, the body moved with destination-aligned dwords
 // Between them the existing frame-level calls run unchanged, once per run of the plan, with first_frame_number = 0 and
 // frame_number_step = 0.  Lengths, offsets and the cut per stream are three small launches (the scan is
-// flac_decode_streams.cpp's, the cut streambatch::accepted_frames).
+// stream_index.cpp's, the cut streambatch::accepted_frames).
 #include "api_internal.h"
 #include "stream_batch_core.h"
 #include "stream_encode_core.h"
+#include "stream_index.h"
 
 namespace flacenc_hip {
 namespace {
@@ -436,7 +437,7 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
     hipLaunchKernelGGL(streams_newlen_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, t_stream, len0, F, newlen, d_flen);
     ++plan[0];
   }
-  HIP_TRY(h, launch_streams_scan(newlen, F, off, st));
+  HIP_TRY(h, streamindex::launch_scan2(newlen, nullptr, F, off, nullptr, st));
   ++plan[0];
   hipLaunchKernelGGL(streams_cut_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, first, ns, off, zeros,
                      s_accepted, s_bytes, d_totals, meta);
@@ -447,7 +448,7 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   uint64_t out_total = 0;
   if (host) {
     // the one thing the host must wait for: how many bytes the accepted frames take, laid back to back
-    HIP_TRY(h, launch_streams_scan(s_bytes, ns, where, st));
+    HIP_TRY(h, streamindex::launch_scan2(s_bytes, nullptr, ns, where, nullptr, st));
     ++plan[0];
     HIP_TRY(h, hipMemcpyAsync(h->pin_meta[0], meta, result_bytes, hipMemcpyDeviceToHost, st));
     ++plan[2];

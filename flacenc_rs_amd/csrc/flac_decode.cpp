@@ -1,4 +1,4 @@
-// flac_decode.cpp -- decode, verify and index FLAC frames on the GPU (flacenc_hip_decode_frames and friends).
+// flac_decode.cpp -- decode and verify FLAC frames on the GPU (flacenc_hip_decode_frames and friends).
 //
 // Frames are independent, so the work spreads over frames; inside a subframe the LPC recurrence is serial and not
 // linear, so a subframe is one lane's work.  Three kernels per launch:
@@ -9,11 +9,13 @@
 //                    samples in registers (MAXP = the wave's largest order bucket); stereo is undone with a lane
 //                    exchange on every sample; 16 samples per lane are staged in LDS so that every store (decode) or
 //                    load of the expected samples (verify) moves 64 bytes of one row
-// Indexing finds candidate headers at every byte, compacts them in order, skims and CRC-checks each, links each to
-// the candidate that starts where it ends and resolves the chain from byte 0 by pointer jumping.
+// The lane setup, the bucket ladder and the sample step are flac_decode_device.h's, shared with the packed-PCM decoders
+// (flac_decode_streams.cpp, flac_decode_ranges.cpp).  The frame index -- flacenc_hip_index_frames included -- is
+// stream_index.cpp; it runs crc16_kernel through launch_frame_crc16 and, for the single stream, skim_kernel in its
+// index mode through launch_frame_skim.
 #include "flac_decode.h"
 
-#include "flac_decode_core.h"
+#include "flac_decode_device.h"
 
 namespace flacenc_hip {
 namespace {
@@ -22,11 +24,7 @@ using flacdec::FrameRec;
 
 __constant__ flacdec::CrcTables kCrc = flacdec::make_crc_tables();
 
-constexpr uint32_t kEnd = 0xFFFFFFFEu, kDead = 0xFFFFFFFFu;  // chain sentinels
-constexpr uint64_t kIndexError = 0x8000000000000000ull;      // FLACENC_HIP_INDEX_ERROR
-constexpr int kStage = 20;                                   // LDS words per lane (16 staged samples, padded)
-
-inline uint32_t ceil_div(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
+constexpr int kStage = 20;  // LDS words per lane (16 staged samples, padded)
 
 // ---------------------------------------------------------------- skim: one lane per frame
 // index mode (lengths == NULL): frame i starts at offsets[i], may run to n_bytes, and its parsed length is recorded
@@ -106,22 +104,12 @@ __device__ bool run_subframe(const uint8_t* fp, uint32_t flen, uint32_t start, u
                              uint32_t ch_tag, uint32_t c, int32_t* row, const int32_t* erow, int32_t* stage) {
   flacdec::SubDecoder<MAXP> d;
   if (bs) d.init(fp, flen, start, bs, sbps);
-  const bool stereo = ch_tag >= 8;
   const int32_t* mem = VERIFY ? erow : row;
   const bool vec = (reinterpret_cast<uintptr_t>(mem) & 15u) == 0;
   bool bad = false;
   for (uint32_t t0 = 0; t0 < bs; t0 += 16) {
     const uint32_t m = min(16u, bs - t0);
-    for (uint32_t i = 0; i < m; ++i) {
-      int32_t v = d.next();
-      if (stereo) {
-        const int32_t o = __shfl_xor(v, 1);
-        int32_t a = c == 0 ? v : o, b = c == 0 ? o : v;
-        flacdec::undo_stereo(ch_tag, a, b);
-        v = c == 0 ? a : b;
-      }
-      stage[i] = v;
-    }
+    for (uint32_t i = 0; i < m; ++i) stage[i] = next_sample(d, ch_tag, c);
     if (vec && m == 16) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -171,26 +159,15 @@ __global__ void __launch_bounds__(256) subframe_kernel(const uint8_t* __restrict
       start = r.sub_bit[c];
     }
   }
-  uint32_t order = 0;
   const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
   const uint8_t* fp = live ? bytes + offsets[f] : bytes;
-  if (bs) {
-    flacdec::BitReader r;
-    r.init(fp, flen, start);
-    flacdec::SubInfo si;
-    flacdec::parse_subframe_header(r, bs, sbps, si);
-    order = si.order;
-  }
-  const int bucket = flacdec::order_bucket(order);
   const size_t row0 = (static_cast<size_t>(f) * channels + c) * stride;
   int32_t* row = (!VERIFY && live) ? out + row0 : nullptr;
   const int32_t* erow = (VERIFY && live) ? expected + row0 : nullptr;
   int32_t* stage = stage_all + threadIdx.x * kStage;
+  const int bucket = lane_bucket(fp, flen, start, bs, sbps);
   bool bad;
-  if (__any(bucket == 32)) bad = run_subframe<32, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage);
-  else if (__any(bucket == 16)) bad = run_subframe<16, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage);
-  else if (__any(bucket == 8)) bad = run_subframe<8, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage);
-  else bad = run_subframe<4, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage);
+  AT_WAVE_BUCKET(bucket, bad = run_subframe<MAXP, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage));
   if (!VERIFY && live)
     for (uint32_t t = bs; t < max_block_size; ++t) row[t] = 0;  // the rest of the row; all of it for a bad frame
   if (bad) atomicOr(&mism[lf], flacdec::MISMATCH);
@@ -201,182 +178,6 @@ __global__ void __launch_bounds__(256) subframe_kernel(const uint8_t* __restrict
     if (block_sizes) block_sizes[f] = s ? 0 : bs;
     if (numbers) numbers[f] = s ? 0 : nums[f];
   }
-}
-
-// ---------------------------------------------------------------- index
-constexpr uint32_t kPosPerThread = 16, kPosPerBlock = 256 * kPosPerThread;
-
-__device__ bool is_candidate(const uint8_t* bytes, uint64_t n_bytes, uint64_t p, uint32_t channels, uint32_t bps) {
-  if (p + 1 >= n_bytes || bytes[p] != 0xFFu || (bytes[p + 1] & 0xFEu) != 0xF8u) return false;
-  const uint64_t left = n_bytes - p;
-  flacdec::Header h;
-  return flacdec::parse_header(bytes + p, left > 64 ? 64u : static_cast<uint32_t>(left), channels, bps, 65536u, kCrc,
-                               h) == 0;
-}
-
-__device__ uint32_t thread_candidates(const uint8_t* bytes, uint64_t n_bytes, uint64_t base, uint32_t channels,
-                                      uint32_t bps, uint32_t* mask) {
-  uint32_t m = 0;
-  for (uint32_t k = 0; k < kPosPerThread; ++k)
-    if (is_candidate(bytes, n_bytes, base + k, channels, bps)) m |= 1u << k;
-  *mask = m;
-  return __popc(m);
-}
-
-// exclusive scan of v over the workgroup (256 threads); returns the exclusive prefix, *total = the sum
-__device__ uint32_t block_scan(uint32_t v, uint32_t* sh, uint32_t* total) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  for (uint32_t d = 1; d < 256; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sh[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  *total = sh[255];
-  const uint32_t incl = sh[threadIdx.x];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ void __launch_bounds__(256) cand_count_kernel(const uint8_t* __restrict__ bytes, uint64_t n_bytes,
-                                                         uint32_t channels, uint32_t bps,
-                                                         uint32_t* __restrict__ block_counts) {
-  __shared__ uint32_t sh[256];
-  uint32_t mask, total;
-  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kPosPerBlock + threadIdx.x * kPosPerThread;
-  block_scan(thread_candidates(bytes, n_bytes, base, channels, bps, &mask), sh, &total);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-
-// one workgroup: block_counts -> exclusive offsets in place; counters[0] = the number of candidates
-__global__ void __launch_bounds__(1024) cand_scan_kernel(uint32_t* __restrict__ block_counts, uint32_t n_blocks,
-                                                         uint32_t* __restrict__ counters) {
-  __shared__ uint32_t sh[1024];
-  const uint32_t per = (n_blocks + 1023) / 1024;
-  const uint32_t lo = min(n_blocks, threadIdx.x * per), hi = min(n_blocks, lo + per);
-  uint32_t sum = 0;
-  for (uint32_t i = lo; i < hi; ++i) sum += block_counts[i];
-  sh[threadIdx.x] = sum;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024; d <<= 1) {
-    const uint32_t x = threadIdx.x >= d ? sh[threadIdx.x - d] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += x;
-    __syncthreads();
-  }
-  uint32_t run = sh[threadIdx.x] - sum;
-  for (uint32_t i = lo; i < hi; ++i) {
-    const uint32_t v = block_counts[i];
-    block_counts[i] = run;
-    run += v;
-  }
-  if (threadIdx.x == 1023) counters[0] = sh[1023];
-}
-
-__global__ void __launch_bounds__(256) cand_write_kernel(const uint8_t* __restrict__ bytes, uint64_t n_bytes,
-                                                         uint32_t channels, uint32_t bps,
-                                                         const uint32_t* __restrict__ block_offsets,
-                                                         uint64_t* __restrict__ cand_pos, uint32_t capacity) {
-  __shared__ uint32_t sh[256];
-  uint32_t mask, total;
-  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kPosPerBlock + threadIdx.x * kPosPerThread;
-  uint32_t at = block_offsets[blockIdx.x] + block_scan(thread_candidates(bytes, n_bytes, base, channels, bps, &mask),
-                                                       sh, &total);
-  for (uint32_t k = 0; k < kPosPerThread; ++k)
-    if ((mask >> k) & 1u) {
-      if (at < capacity) cand_pos[at] = base + k;
-      ++at;
-    }
-}
-
-// jump[0][i]: the valid candidate (skim and CRC-16 passed) that starts where candidate i ends, kEnd at n_bytes, kDead
-// otherwise -- so a chain only ever walks over verified frames, also when candidates were dropped at `capacity`
-__global__ void __launch_bounds__(256) link_kernel(const uint64_t* __restrict__ cand_pos,
-                                                   const FrameRec* __restrict__ recs, const uint32_t* __restrict__ n_dev,
-                                                   uint32_t capacity, uint64_t n_bytes, uint32_t* __restrict__ jump) {
-  const uint32_t n = min(*n_dev, capacity);
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t nx = kDead;
-  if (recs[i].status == 0) {
-    const uint64_t e = cand_pos[i] + recs[i].len;
-    if (e == n_bytes) {
-      nx = kEnd;
-    } else {
-      uint32_t lo = i + 1, hi = n;  // positions ascend
-      while (lo < hi) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (cand_pos[mid] < e) lo = mid + 1;
-        else hi = mid;
-      }
-      if (lo < n && cand_pos[lo] == e && recs[lo].status == 0) nx = lo;
-    }
-  }
-  jump[i] = nx;
-}
-
-__global__ void __launch_bounds__(256) jump_kernel(const uint32_t* __restrict__ prev, uint32_t* __restrict__ next,
-                                                   const uint32_t* __restrict__ n_dev, uint32_t capacity) {
-  const uint32_t n = min(*n_dev, capacity);
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t a = prev[i];
-  next[i] = a >= kEnd ? a : prev[a];
-}
-
-// one thread: the length of the chain from candidate 0 by binary lifting over the jump levels
-__global__ void chain_kernel(const uint64_t* __restrict__ cand_pos, const FrameRec* __restrict__ recs,
-                             const uint32_t* __restrict__ jump, uint32_t levels, uint32_t* __restrict__ counters,
-                             uint32_t capacity, uint64_t n_bytes, uint64_t max_frames,
-                             uint64_t* __restrict__ n_frames) {
-  const uint32_t total = counters[0], n = min(total, capacity);
-  // candidates past `capacity` (the highest positions) were dropped: what the chain reaches is still a verified
-  // prefix, but it may stop early, so the caller is told to come back with a larger max_frames
-  uint64_t err = total > capacity ? kIndexError : 0;
-  uint64_t count = 0;
-  if (n_bytes == 0) {
-    // an empty buffer holds no frame and no error
-  } else if (n == 0 || cand_pos[0] != 0 || recs[0].status != 0) {
-    err = kIndexError;  // no verified frame at byte 0
-  } else {
-    uint32_t cur = 0;
-    count = 1;
-    for (int k = static_cast<int>(levels) - 1; k >= 0; --k) {
-      const uint32_t nx = jump[static_cast<size_t>(k) * capacity + cur];
-      if (nx < kEnd) {
-        cur = nx;
-        count += 1ull << k;
-      }
-    }
-    if (jump[cur] != kEnd) err = kIndexError;
-    if (count > max_frames) {
-      err = kIndexError;
-      count = max_frames;
-    }
-  }
-  counters[1] = static_cast<uint32_t>(count);
-  *n_frames = count | err;
-}
-
-__global__ void __launch_bounds__(256) enumerate_kernel(const uint64_t* __restrict__ cand_pos,
-                                                        const FrameRec* __restrict__ recs,
-                                                        const uint32_t* __restrict__ jump, uint32_t levels,
-                                                        const uint32_t* __restrict__ counters, uint32_t capacity,
-                                                        uint64_t* __restrict__ offsets, uint32_t* __restrict__ lengths) {
-  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= counters[1]) return;
-  uint32_t node = 0;
-  for (uint32_t k = 0; k < levels; ++k)
-    if ((m >> k) & 1u) node = jump[static_cast<size_t>(k) * capacity + node];
-  offsets[m] = cand_pos[node];
-  lengths[m] = recs[node].len;
-}
-
-uint32_t jump_levels(size_t capacity) {
-  uint32_t l = 1;
-  while ((static_cast<size_t>(1) << l) <= capacity) ++l;
-  return l;
 }
 
 size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
@@ -407,70 +208,18 @@ hipError_t launch_decode_frames(const uint8_t* bytes, uint64_t n_bytes, const ui
   return hipGetLastError();
 }
 
-// what the batch index (flac_decode_streams.cpp) shares with this one: neither kernel looks at stream parameters
+// skim_kernel in index mode and crc16_kernel for the frame index (stream_index.cpp)
+hipError_t launch_frame_skim(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets, uint32_t n,
+                             const uint32_t* n_dev, uint32_t channels, uint32_t bps, void* recs, hipStream_t stream) {
+  hipLaunchKernelGGL(skim_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, bytes, n_bytes, offsets, nullptr, n, n_dev,
+                     channels, bps, 65536u, static_cast<FrameRec*>(recs), nullptr);
+  return hipGetLastError();
+}
+
 hipError_t launch_frame_crc16(const uint8_t* bytes, const uint64_t* offsets, uint32_t n, const uint32_t* n_dev,
                               void* recs, hipStream_t stream) {
   hipLaunchKernelGGL(crc16_kernel, dim3(ceil_div(n, 4)), dim3(256), 0, stream, bytes, offsets, n, n_dev,
                      static_cast<FrameRec*>(recs));
-  return hipGetLastError();
-}
-
-hipError_t launch_jump_levels(uint32_t* jump, const uint32_t* n_dev, size_t capacity, hipStream_t stream) {
-  const uint32_t cap = static_cast<uint32_t>(capacity), levels = jump_levels(capacity);
-  for (uint32_t k = 1; k < levels; ++k)
-    hipLaunchKernelGGL(jump_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream,
-                       jump + static_cast<size_t>(k - 1) * cap, jump + static_cast<size_t>(k) * cap, n_dev, cap);
-  return hipGetLastError();
-}
-
-uint32_t index_jump_levels(size_t capacity) { return jump_levels(capacity); }
-
-size_t index_candidate_capacity(size_t max_frames) { return max_frames + max_frames / 4 + 4096; }
-
-size_t index_scratch_bytes(uint64_t n_bytes, size_t capacity) {
-  const size_t n_blocks = (n_bytes + kPosPerBlock - 1) / kPosPerBlock;
-  return align256(n_blocks * 4) + 256 + align256(capacity * 8) + align256(capacity * sizeof(FrameRec)) +
-         static_cast<size_t>(jump_levels(capacity)) * capacity * 4;
-}
-
-hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t channels, uint32_t bps,
-                               size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
-                               void* scratch, size_t capacity, hipStream_t stream) {
-  const uint32_t n_blocks = ceil_div(n_bytes, kPosPerBlock);
-  const uint32_t cap = static_cast<uint32_t>(capacity), levels = jump_levels(capacity);
-  char* s = static_cast<char*>(scratch);
-  uint32_t* block_counts = reinterpret_cast<uint32_t*>(s);
-  s += align256(static_cast<size_t>(n_blocks) * 4);
-  uint32_t* counters = reinterpret_cast<uint32_t*>(s);
-  s += 256;
-  uint64_t* cand_pos = reinterpret_cast<uint64_t*>(s);
-  s += align256(capacity * 8);
-  FrameRec* recs = reinterpret_cast<FrameRec*>(s);
-  s += align256(capacity * sizeof(FrameRec));
-  uint32_t* jump = reinterpret_cast<uint32_t*>(s);
-  hipError_t e = hipMemsetAsync(counters, 0, 256, stream);
-  if (e != hipSuccess) return e;
-  if (n_blocks) {
-    hipLaunchKernelGGL(cand_count_kernel, dim3(n_blocks), dim3(256), 0, stream, bytes, n_bytes, channels, bps,
-                       block_counts);
-    hipLaunchKernelGGL(cand_scan_kernel, dim3(1), dim3(1024), 0, stream, block_counts, n_blocks, counters);
-    hipLaunchKernelGGL(cand_write_kernel, dim3(n_blocks), dim3(256), 0, stream, bytes, n_bytes, channels, bps,
-                       block_counts, cand_pos, cap);
-    hipLaunchKernelGGL(skim_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream, bytes, n_bytes, cand_pos,
-                       nullptr, cap, counters, channels, bps, 65536u, recs, nullptr);
-    hipLaunchKernelGGL(crc16_kernel, dim3(ceil_div(cap, 4)), dim3(256), 0, stream, bytes, cand_pos, cap, counters,
-                       recs);
-    hipLaunchKernelGGL(link_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream, cand_pos, recs, counters, cap,
-                       n_bytes, jump);
-    for (uint32_t k = 1; k < levels; ++k)
-      hipLaunchKernelGGL(jump_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, stream,
-                         jump + static_cast<size_t>(k - 1) * cap, jump + static_cast<size_t>(k) * cap, counters, cap);
-  }
-  hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1), 0, stream, cand_pos, recs, jump, levels, counters, cap,
-                     n_bytes, static_cast<uint64_t>(max_frames), n_frames);
-  if (max_frames)
-    hipLaunchKernelGGL(enumerate_kernel, dim3(ceil_div(max_frames < cap ? max_frames : cap, 256)), dim3(256), 0,
-                       stream, cand_pos, recs, jump, levels, counters, cap, offsets, lengths);
   return hipGetLastError();
 }
 

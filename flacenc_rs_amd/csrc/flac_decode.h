@@ -1,4 +1,5 @@
-// flac_decode.h -- launchers of the frame decoder's kernels (flac_decode.cpp) for api_decode.cpp.
+// flac_decode.h -- launchers of the frame decoder's kernels (flac_decode.cpp) and of the single-stream frame index
+// (stream_index.cpp) for api_decode.cpp and api_decode_stream.cpp.
 #ifndef FLACENC_FLAC_DECODE_H_
 #define FLACENC_FLAC_DECODE_H_
 
@@ -19,7 +20,7 @@ hipError_t launch_decode_frames(const uint8_t* bytes, uint64_t n_bytes, const ui
                                 uint32_t* block_sizes, uint64_t* numbers, uint32_t* status, void* scratch,
                                 hipStream_t stream);
 
-// candidate capacity and scratch of one index launch
+// candidate capacity and scratch of one index launch (stream_index.cpp)
 size_t index_candidate_capacity(size_t max_frames);
 size_t index_scratch_bytes(uint64_t n_bytes, size_t capacity);
 
@@ -27,13 +28,13 @@ hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t 
                                size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
                                void* scratch, size_t capacity, hipStream_t stream);
 
-// Pieces of the index for the batch index of flac_decode_streams.cpp.  The CRC-16 of frames offsets[0 .. min(n, *n_dev))
-// whose skim record (flacdec::FrameRec recs[]) has status 0: FRAME_CRC into the record where it fails.  The jump levels
-// 1 .. index_jump_levels(capacity) - 1 from level 0 (jump[0 .. capacity)), level k at jump + k * capacity.
+// flac_decode.cpp's kernels for the index.  The skim of the single stream [0, n_bytes): frames that start at
+// offsets[0 .. min(n, *n_dev)) and may run to n_bytes, their skim records (flacdec::FrameRec) into recs[].  The CRC-16
+// of the frames whose record has status 0: FRAME_CRC into the record where it fails.
+hipError_t launch_frame_skim(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets, uint32_t n,
+                             const uint32_t* n_dev, uint32_t channels, uint32_t bps, void* recs, hipStream_t stream);
 hipError_t launch_frame_crc16(const uint8_t* bytes, const uint64_t* offsets, uint32_t n, const uint32_t* n_dev,
                               void* recs, hipStream_t stream);
-hipError_t launch_jump_levels(uint32_t* jump, const uint32_t* n_dev, size_t capacity, hipStream_t stream);
-uint32_t index_jump_levels(size_t capacity);
 
 }  // namespace flacenc_hip
 

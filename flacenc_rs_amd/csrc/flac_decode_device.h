@@ -1,0 +1,167 @@
+// flac_decode_device.h -- what the decoder's translation units (flac_decode.cpp, stream_index.cpp, flac_decode_streams.cpp,
+// flac_decode_ranges.cpp) share on the device, each written once: the index's constants, workgroup scan, bisection and
+// chain walks, and a lane's subframe reconstruction -- its setup, the order-bucket ladder, the sample step and the
+// packed-PCM writer.  Included by those four files only.
+#ifndef FLAC_DECODE_DEVICE_H_
+#define FLAC_DECODE_DEVICE_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "flac_decode_core.h"
+
+namespace flacenc_hip {
+
+constexpr uint32_t kEnd = 0xFFFFFFFEu, kDead = 0xFFFFFFFFu;  // chain sentinels
+// the candidate pass: byte positions per lane and per workgroup of 256
+constexpr uint32_t kPosPerThread = 16, kPosPerBlock = 256 * kPosPerThread;
+
+inline uint32_t ceil_div(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
+
+// a kernel launch that counts itself in plan[0]
+#define COUNTED_LAUNCH(plan, ...)      \
+  do {                                 \
+    hipLaunchKernelGGL(__VA_ARGS__);   \
+    ++(plan)[0];                       \
+  } while (0)
+
+// ---------------------------------------------------------------- index
+// exclusive scan of v over the workgroup (256 threads); returns the exclusive prefix, *total = the sum
+__device__ inline uint32_t block_scan(uint32_t v, uint32_t* sh, uint32_t* total) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {
+    const uint32_t x = threadIdx.x >= d ? sh[threadIdx.x - d] : 0u;
+    __syncthreads();
+    sh[threadIdx.x] += x;
+    __syncthreads();
+  }
+  *total = sh[255];
+  const uint32_t incl = sh[threadIdx.x];
+  __syncthreads();
+  return incl - v;
+}
+
+// the first candidate of [lo, n) at or behind byte x; n if there is none (positions ascend)
+__device__ inline uint32_t lower_bound(const uint64_t* cand_pos, uint32_t lo, uint32_t n, uint64_t x) {
+  uint32_t hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (cand_pos[mid] < x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the verified candidate (skim and CRC-16 passed) of [lo, n) that starts at byte x, kDead if there is none
+__device__ inline uint32_t verified_at(const uint64_t* cand_pos, const flacdec::FrameRec* recs, uint32_t lo, uint32_t n,
+                                       uint64_t x) {
+  const uint32_t i = lower_bound(cand_pos, lo, n, x);
+  return i < n && cand_pos[i] == x && recs[i].status == 0 ? i : kDead;
+}
+
+// the chain from `root` by binary lifting over the jump levels (level k at jump + k * capacity): its last node and the
+// number of its nodes
+struct ChainEnd {
+  uint32_t last;
+  uint64_t count;
+};
+__device__ inline ChainEnd walk_chain(const uint32_t* jump, uint32_t levels, uint32_t capacity, uint32_t root) {
+  ChainEnd e{root, 1};
+  for (int k = static_cast<int>(levels) - 1; k >= 0; --k) {
+    const uint32_t nx = jump[static_cast<size_t>(k) * capacity + e.last];
+    if (nx < kEnd) {
+      e.last = nx;
+      e.count += 1ull << k;
+    }
+  }
+  return e;
+}
+
+// the j-th node of the chain from `root`, j below the chain's length
+__device__ inline uint32_t chain_node(const uint32_t* jump, uint32_t levels, uint32_t capacity, uint32_t root,
+                                      uint32_t j) {
+  uint32_t node = root;
+  for (uint32_t k = 0; k < levels; ++k)
+    if ((j >> k) & 1u) node = jump[static_cast<size_t>(k) * capacity + node];
+  return node;
+}
+
+// ---------------------------------------------------------------- reconstruction: one lane per subframe
+// The lane's setup: the order bucket of the subframe that starts at bit `start` of the frame (an idle lane, bs == 0,
+// has order 0).
+__device__ inline int lane_bucket(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t sbps) {
+  uint32_t order = 0;
+  if (bs) {
+    flacdec::BitReader r;
+    r.init(fp, flen, start);
+    flacdec::SubInfo si;
+    flacdec::parse_subframe_header(r, bs, sbps, si);
+    order = si.order;
+  }
+  return flacdec::order_bucket(order);
+}
+
+// The ladder: runs the statement given behind `bucket` once, with MAXP (a constant expression) the largest order
+// bucket of the wave's lanes, so that the whole wave runs one SubDecoder<MAXP>.
+#define AT_WAVE_BUCKET(bucket, ...)   \
+  do {                                \
+    if (__any((bucket) == 32)) {      \
+      constexpr int MAXP = 32;        \
+      __VA_ARGS__;                    \
+    } else if (__any((bucket) == 16)) { \
+      constexpr int MAXP = 16;        \
+      __VA_ARGS__;                    \
+    } else if (__any((bucket) == 8)) { \
+      constexpr int MAXP = 8;         \
+      __VA_ARGS__;                    \
+    } else {                          \
+      constexpr int MAXP = 4;         \
+      __VA_ARGS__;                    \
+    }                                 \
+  } while (0)
+
+// The sample step of channel c: the subframe's next value, exchanged with the pair lane and stereo undone where the
+// frame is a stereo pair (which sits on an even / odd lane pair; both lanes take the step together).
+template <int MAXP>
+__device__ __forceinline__ int32_t next_sample(flacdec::SubDecoder<MAXP>& d, uint32_t ch_tag, uint32_t c) {
+  int32_t v = d.next();
+  if (ch_tag >= 8) {
+    const int32_t o = __shfl_xor(v, 1);
+    int32_t a = c == 0 ? v : o, b = c == 0 ? o : v;
+    flacdec::undo_stereo(ch_tag, a, b);
+    v = c == 0 ? a : b;
+  }
+  return v;
+}
+
+// Samples [skip, skip + take) of channel c of a frame of `bs` samples into packed PCM: sample t at dst + ((t - skip) *
+// channels + c) * B, the low B bytes of its value, little-endian.  The recurrence runs from sample 0 and stops at
+// skip + take.  Whole samples where the address allows, else bytes: a neighbouring sample's bytes are another lane's and
+// are never read back.  Both lanes of a stereo pair have the same bounds, so the exchange stays convergent.
+template <int MAXP>
+__device__ void write_pcm(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
+                          uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t channels, uint32_t B, uint8_t* dst) {
+  flacdec::SubDecoder<MAXP> d;
+  if (bs) d.init(fp, flen, start, bs, sbps);
+  uint8_t* p = dst + static_cast<size_t>(c) * B;
+  const size_t step = static_cast<size_t>(channels) * B;
+  const bool whole = (B == 2 || B == 4) && (reinterpret_cast<uintptr_t>(p) & (B - 1)) == 0;
+  const uint32_t stop = skip + take;
+  for (uint32_t t = 0; t < stop; ++t) {
+    const uint32_t u = static_cast<uint32_t>(next_sample(d, ch_tag, c));
+    if (t < skip) continue;
+    if (whole && B == 2) {
+      *reinterpret_cast<uint16_t*>(p) = static_cast<uint16_t>(u);
+    } else if (whole) {
+      *reinterpret_cast<uint32_t*>(p) = u;
+    } else {
+      for (uint32_t k = 0; k < B; ++k) p[k] = static_cast<uint8_t>(u >> (8u * k));
+    }
+    p += step;
+  }
+}
+
+}  // namespace flacenc_hip
+
+#endif  // FLAC_DECODE_DEVICE_H_

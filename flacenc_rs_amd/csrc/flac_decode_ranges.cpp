@@ -2,9 +2,9 @@
 // call, with a number of launches, synchronisations and transfers that does not depend on the number of streams or of
 // ranges.
 //
-// The segmented index is flacenc_hip_decode_streams' own (stream_index.h): every stream's verified chain, every chain
-// frame enumerated, and the scans of PCM bytes and of frames with a status over the frame sequence.  Positions are read
-// off the scan of PCM bytes (stream_ranges_core.h).  On top of it:
+// The segmented index is flacenc_hip_decode_streams' own (stream_index.h, stream_index.cpp): every stream's verified
+// chain, every chain frame enumerated, and the scans of PCM bytes and of frames with a status over the frame sequence.
+// Positions are read off the scan of PCM bytes (stream_ranges_core.h).  On top of it:
 //   ranges_streams_kernel    one lane per stream: the chain frames that decode, S (its samples), W (why it stops) and
 //                            where the chain stopped
 //   ranges_locate_kernel     one lane per range: bisects its stream's positions for the frame that holds first_sample
@@ -15,12 +15,11 @@
 //   ranges_enumerate_kernel  one lane per range-frame: its range, by bisection, and its chain frame
 //   ranges_decode_kernel     one launch per channel count present among the ranges' streams (ranges are numbered in
 //                            `rslot` order: the range table sorted by their stream's channel count), with the lane rules
-//                            of streams_decode_kernel and a window per frame: the recurrence runs from the frame's first
-//                            sample -- it is serial -- to the last sample wanted, and only samples inside the range are
-//                            stored
+//                            of streams_decode_kernel and its writer (write_pcm, flac_decode_device.h) with a window per
+//                            frame: the recurrence runs from the frame's first sample -- it is serial -- to the last
+//                            sample wanted, and only samples inside the range are stored
 #include "api_internal.h"
-#include "flac_decode.h"
-#include "flac_decode_core.h"
+#include "flac_decode_device.h"
 #include "stream_batch_core.h"
 #include "stream_index.h"
 #include "stream_ranges_core.h"
@@ -32,8 +31,6 @@ using namespace streamindex;
 using flacdec::FrameRec;
 using Desc = flacenc_hip_stream_desc;
 using Range = flacenc_hip_range_desc;
-
-inline uint32_t ceil_div(uint64_t a, uint64_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
 
 // per stream, what the ranges on it share
 struct StreamEnd {
@@ -151,42 +148,6 @@ __global__ void __launch_bounds__(256) ranges_enumerate_kernel(const uint64_t* _
 }
 
 // ---------------------------------------------------------------- reconstruction: one lane per subframe
-// Samples [skip, skip + take) of channel c of a frame of `bs` samples into packed PCM: sample t at dst + ((t - skip) *
-// channels + c) * B, the low B bytes of its value, little-endian.  The recurrence runs from sample 0 and stops at
-// skip + take.  Whole samples where the address allows, else bytes: a neighbouring sample's bytes are another lane's and
-// are never read back.  Both lanes of a stereo pair have the same bounds, so the exchange stays convergent.
-template <int MAXP>
-__device__ void decode_window(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip,
-                              uint32_t take, uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t channels, uint32_t B,
-                              uint8_t* dst) {
-  flacdec::SubDecoder<MAXP> d;
-  if (bs) d.init(fp, flen, start, bs, sbps);
-  const bool stereo = ch_tag >= 8;
-  uint8_t* p = dst + static_cast<size_t>(c) * B;
-  const size_t step = static_cast<size_t>(channels) * B;
-  const bool whole = (B == 2 || B == 4) && (reinterpret_cast<uintptr_t>(p) & (B - 1)) == 0;
-  const uint32_t stop = skip + take;
-  for (uint32_t t = 0; t < stop; ++t) {
-    int32_t v = d.next();
-    if (stereo) {
-      const int32_t o = __shfl_xor(v, 1);
-      int32_t a = c == 0 ? v : o, b = c == 0 ? o : v;
-      flacdec::undo_stereo(ch_tag, a, b);
-      v = c == 0 ? a : b;
-    }
-    if (t < skip) continue;
-    const uint32_t u = static_cast<uint32_t>(v);
-    if (whole && B == 2) {
-      *reinterpret_cast<uint16_t*>(p) = static_cast<uint16_t>(u);
-    } else if (whole) {
-      *reinterpret_cast<uint32_t*>(p) = u;
-    } else {
-      for (uint32_t k = 0; k < B; ++k) p[k] = static_cast<uint8_t>(u >> (8u * k));
-    }
-    p += step;
-  }
-}
-
 // The range-frames [k_lo, k_hi) all belong to streams of `channels` channels; lane (range-frame, c) as in
 // streams_decode_kernel.  A range's PCM starts at out + where[q] (`where` given: the compact staging of the host path)
 // or at out + its out_offset.
@@ -231,20 +192,9 @@ __global__ void __launch_bounds__(256) ranges_decode_kernel(const uint8_t* __res
     fp = bytes + cand_pos[node];
     dst = out + (where ? where[q] : x.out_offset) + w.dst * fb;
   }
-  uint32_t order = 0;
   const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
-  if (bs) {
-    flacdec::BitReader r;
-    r.init(fp, flen, start);
-    flacdec::SubInfo si;
-    flacdec::parse_subframe_header(r, bs, sbps, si);
-    order = si.order;
-  }
-  const int bucket = flacdec::order_bucket(order);
-  if (__any(bucket == 32)) decode_window<32>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
-  else if (__any(bucket == 16)) decode_window<16>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
-  else if (__any(bucket == 8)) decode_window<8>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
-  else decode_window<4>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst);
+  const int bucket = lane_bucket(fp, flen, start, bs, sbps);
+  AT_WAVE_BUCKET(bucket, write_pcm<MAXP>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst));
 }
 
 }  // namespace
@@ -259,9 +209,8 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   uint64_t* plan = h->last_ranges_plan;  // launches, synchronisations, transfers, channel classes of the ranges
   plan[0] = plan[1] = plan[2] = plan[3] = 0;
-  if ((memory_kind != FLACENC_HIP_MEM_HOST && memory_kind != FLACENC_HIP_MEM_DEVICE) || !bytes || !streams || !ranges ||
-      !out || !totals || !call_totals || n_streams > streambatch::MAX_STREAMS || n_ranges > streamranges::MAX_RANGES ||
-      max_frames > streambatch::MAX_FRAMES || n_bytes > (static_cast<uint64_t>(0xFFFFFFFFu) << 12)) {
+  if (!call_limits_ok(memory_kind, n_streams, max_frames, n_bytes) || !bytes || !streams || !ranges || !out || !totals ||
+      !call_totals || n_ranges > streamranges::MAX_RANGES) {
     h->last_error = "decode_ranges: null pointer, unknown memory kind, more than 2^24 streams or ranges, max_frames above "
                     "2^30 or n_bytes >= 16 TiB";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
@@ -295,17 +244,8 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
   std::memcpy(h->ranges_table.data(), rtable, n_ranges * sizeof(Range));
   uint32_t* p_rperm = reinterpret_cast<uint32_t*>(h->ranges_table.data() + n_ranges * sizeof(Range));
   ClassLo rslot_lo{};  // rslots [lo[c], lo[c + 1]) hold the ranges on streams of c channels
-  for (size_t r = 0; r < n_ranges; ++r) ++rslot_lo.lo[table[rtable[r].stream].channels + 1];
-  uint32_t classes = 0;
-  for (uint32_t c = 1; c <= 8; ++c) {
-    classes += rslot_lo.lo[c + 1] != 0;
-    rslot_lo.lo[c + 1] += rslot_lo.lo[c];
-  }
-  {
-    uint32_t at[9];
-    for (uint32_t c = 1; c <= 8; ++c) at[c] = rslot_lo.lo[c];
-    for (size_t r = 0; r < n_ranges; ++r) p_rperm[at[table[rtable[r].stream].channels]++] = static_cast<uint32_t>(r);
-  }
+  const uint32_t classes = sort_by_channels(
+      n_ranges, [table, rtable](size_t r) { return table[rtable[r].stream].channels; }, rslot_lo.lo, p_rperm);
 
   // ---- the index; behind `base`, host memory: where[n_ranges + 1] | totals[n_ranges][4] ----
   const size_t F = max_frames;
@@ -347,23 +287,19 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
   uint64_t* r_base = reinterpret_cast<uint64_t*>(ix.scratch + o_rbase);
   uint32_t* rf_range = reinterpret_cast<uint32_t*>(ix.scratch + o_rfrange);
   uint32_t* rf_frame = reinterpret_cast<uint32_t*>(ix.scratch + o_rfframe);
-#define SR_LAUNCH(...)                 \
-  do {                                 \
-    hipLaunchKernelGGL(__VA_ARGS__);   \
-    ++plan[0];                         \
-  } while (0)
   // ---- which frames every range touches ----
-  SR_LAUNCH(ranges_streams_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, ix.descs, ix.perm, ns, ix.base, ix.pcm,
-            ix.bad, ix.f_node, ix.cand_pos, ix.s_end, ix.s_why, ix.counters, ends);
-  SR_LAUNCH(ranges_locate_kernel, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges, rperm, nr, ends, ix.pcm,
-            ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written, d_totals, ix.meta);
+  COUNTED_LAUNCH(plan, ranges_streams_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, ix.descs, ix.perm, ns, ix.base,
+                 ix.pcm, ix.bad, ix.f_node, ix.cand_pos, ix.s_end, ix.s_why, ix.counters, ends);
+  COUNTED_LAUNCH(plan, ranges_locate_kernel, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges, rperm, nr,
+                 ends, ix.pcm, ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written, d_totals,
+                 ix.meta);
   HIP_TRY(h, launch_scan2(r_frames, host ? r_bytes : nullptr, nr, r_base, where, st));
   ++plan[0];
-  SR_LAUNCH(ranges_verdict_kernel, dim3(1), dim3(1), 0, st, r_base, nr, static_cast<uint64_t>(max_frames), rslot_lo,
-            ix.counters, ix.meta);
+  COUNTED_LAUNCH(plan, ranges_verdict_kernel, dim3(1), dim3(1), 0, st, r_base, nr, static_cast<uint64_t>(max_frames),
+                 rslot_lo, ix.counters, ix.meta);
   if (F)
-    SR_LAUNCH(ranges_enumerate_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, r_base, nr, r_first, ix.counters,
-              rf_range, rf_frame);
+    COUNTED_LAUNCH(plan, ranges_enumerate_kernel, dim3(ceil_div(F, 256)), dim3(256), 0, st, r_base, nr, r_first,
+                   ix.counters, rf_range, rf_frame);
   HIP_TRY(h, hipGetLastError());
   const uint64_t* r_meta = static_cast<const uint64_t*>(h->pin_meta[0]);
   HIP_TRY(h, hipMemcpyAsync(h->pin_meta[0], ix.meta, ix.result_words * 8, hipMemcpyDeviceToHost, st));
@@ -396,19 +332,13 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
     const uint32_t k_lo = static_cast<uint32_t>(r_meta[M_CLASS + c]), k_hi = static_cast<uint32_t>(r_meta[M_CLASS + c + 1]);
     const uint32_t per_block = 256 / c;
     // (a class whose ranges touch no frame still counts as a launch of the plan: the plan depends on the classes only)
-    SR_LAUNCH(ranges_decode_kernel, dim3(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1), dim3(per_block * c), 0, st,
-              ix.d_bytes, ix.descs, d_ranges, rperm, ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written,
-              ix.cand_pos, ix.recs, k_lo, k_hi, c, where, d_out);
+    COUNTED_LAUNCH(plan, ranges_decode_kernel, dim3(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1),
+                   dim3(per_block * c), 0, st, ix.d_bytes, ix.descs, d_ranges, rperm, ix.base, ix.pcm, ix.f_node, ix.f_slot,
+                   rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo, k_hi, c, where, d_out);
   }
-#undef SR_LAUNCH
   HIP_TRY(h, hipGetLastError());
-  if (host) {
-    // one transfer of the ranges' PCM back to back into pinned staging, then every range to its slot on the host
-    if ((rc = ensure_pinned(h, h->pin_out, &h->pin_out_cap, static_cast<size_t>(pcm_bytes))) != FLACENC_HIP_OK) return rc;
-    if ((rc = ensure_copy_pool(h, "decode_ranges")) != FLACENC_HIP_OK) return rc;
-    if (pcm_bytes) HIP_TRY(h, hipMemcpyAsync(h->pin_out[0], d_out, static_cast<size_t>(pcm_bytes), hipMemcpyDeviceToHost, st));
-    ++plan[2];
-  }
+  // host memory: one transfer of the ranges' PCM back to back into pinned staging, then every range to its slot
+  if (host && (rc = download_pcm(h, plan, "decode_ranges", d_out, pcm_bytes)) != FLACENC_HIP_OK) return rc;
   HIP_TRY(h, hipStreamSynchronize(st));
   ++plan[1];
   drain.armed = false;

@@ -1,8 +1,11 @@
-// stream_index.h -- the segmented index of a batch of FLAC streams, as flacenc_hip_decode_streams (flac_decode_streams.cpp,
-// which holds its kernels) and flacenc_hip_decode_ranges (flac_decode_ranges.cpp) share it: candidates, skim, CRC-16,
-// link, jump levels, one chain per stream, the scan of chain lengths, the verdict, every chain frame enumerated and the
-// two scans over the frame sequence (PCM bytes, frames with a status).  build() queues all of it on the handle's stream
-// and synchronises nothing; what it leaves in device scratch (h->d_idx) is described by Index.  Internal to the library.
+// stream_index.h -- the frame index of the decoder (stream_index.cpp holds its kernels).  One pipeline -- candidates, skim,
+// CRC-16, link, jump levels -- serves the single stream of flacenc_hip_index_frames (launch_index_frames, flac_decode.h)
+// and the segmented index of a batch of FLAC streams, as flacenc_hip_decode_streams (flac_decode_streams.cpp) and
+// flacenc_hip_decode_ranges (flac_decode_ranges.cpp) share it: on top of the pipeline one chain per stream, the scan of
+// chain lengths, the verdict, every chain frame enumerated and the two scans over the frame sequence (PCM bytes, frames
+// with a status).  build() queues all of it on the handle's stream and synchronises nothing; what it leaves in device
+// scratch (h->d_idx) is described by Index.  Behind it the header holds what the host sides of those two batch calls
+// share and the index does not need itself: call_limits_ok, sort_by_channels and download_pcm.  Internal to the library.
 #ifndef STREAM_INDEX_H_
 #define STREAM_INDEX_H_
 
@@ -60,10 +63,39 @@ struct Index {
 // plan: launches, synchronisations, transfers, channel classes of the call (plan[3] is set, the others are added to)
 int build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq, Index& ix);
 
-// the index's single-workgroup scan over two arrays of n 64-bit words: out_x[i] = the sum of x[j] over j < i, out_x[n]
-// the total.  One launch.
+// The single-workgroup scan of up to two arrays (b may be null) of n 64-bit words: out_x[i] = the sum of x[j] over
+// j < i, out_x[n] the total.  One launch.  The batch encoder (encode_streams.cpp) uses it too.
 hipError_t launch_scan2(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out_a, uint64_t* out_b,
                         hipStream_t stream);
+
+// What the two batch calls refuse alike, in front of their tables: the memory kind and the stream, frame and n_bytes
+// limits.
+inline bool call_limits_ok(int memory_kind, size_t n_streams, size_t max_frames, uint64_t n_bytes) {
+  return (memory_kind == FLACENC_HIP_MEM_HOST || memory_kind == FLACENC_HIP_MEM_DEVICE) &&
+         n_streams <= streambatch::MAX_STREAMS && max_frames <= streambatch::MAX_FRAMES &&
+         n_bytes <= (static_cast<uint64_t>(0xFFFFFFFFu) << 12);
+}
+
+// n items sorted by their channel count (channels_of(i) in 1..=8), stably: perm[slot] = item, slots [lo[c], lo[c + 1])
+// hold the items of c channels.  Returns the number of channel counts present.
+template <class ChannelsOf>
+uint32_t sort_by_channels(size_t n, ChannelsOf channels_of, uint32_t lo[10], uint32_t* perm) {
+  for (uint32_t c = 0; c < 10; ++c) lo[c] = 0;
+  for (size_t i = 0; i < n; ++i) ++lo[channels_of(i) + 1];
+  uint32_t classes = 0;
+  for (uint32_t c = 1; c <= 8; ++c) {
+    classes += lo[c + 1] != 0;
+    lo[c + 1] += lo[c];
+  }
+  uint32_t at[9];
+  for (uint32_t c = 1; c <= 8; ++c) at[c] = lo[c];
+  for (size_t i = 0; i < n; ++i) perm[at[channels_of(i)]++] = static_cast<uint32_t>(i);
+  return classes;
+}
+
+// The host-memory download of a batch call: pcm_bytes of packed PCM from d_out into pinned staging (h->pin_out[0]) in
+// one transfer, counted in plan[2], with the copy pool ready to scatter it.
+int download_pcm(flacenc_hip_handle* h, uint64_t* plan, const char* who, const uint8_t* d_out, uint64_t pcm_bytes);
 
 // the handle's stream is drained before an error hands the handle back
 struct Drain {

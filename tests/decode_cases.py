@@ -468,7 +468,7 @@ def _stream(name, frames, channels, bps, front=b""):
 
 @functools.lru_cache(None)
 def tiny_stream(variable=False, n_frames=3000):
-    """Mono 8-bit frames of 10..40 bytes (Constant and tiny Verbatim blocks): a lane of cand_count_kernel's 16 positions
+    """Mono 8-bit frames of 10..40 bytes (Constant and tiny Verbatim blocks): a lane of streams_cand_kernel's 16 positions
     holds up to two of them, a workgroup's 4096 positions more than a hundred."""
     rng = np.random.default_rng(0x7177 + variable)
     frames, at = [], 0
@@ -517,7 +517,7 @@ def empty_stream():
 
 
 def candidate_capacity(max_frames):
-    """index_candidate_capacity of flac_decode.cpp, as the header states it."""
+    """index_candidate_capacity of stream_index.cpp, as the header states it."""
     return max_frames + max_frames // 4 + 4096
 
 
@@ -535,7 +535,7 @@ def planted_field_stream(n_planted):
 
 
 def is_candidate(data, p, channels, bps):
-    """flac_decode.cpp's is_candidate, from RFC 9639 section 9.1: a header valid for the stream, CRC-8 included."""
+    """stream_index.cpp's is_candidate, from RFC 9639 section 9.1: a header valid for the stream, CRC-8 included."""
     d = data[p:p + 16]
     if len(d) < 2 or d[0] != 0xFF or (d[1] & 0xFE) != 0xF8:
         return False

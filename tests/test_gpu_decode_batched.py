@@ -1,5 +1,5 @@
-"""The GPU-only parts of the frame decoder and the index (flac_decode.cpp: skim_kernel, crc16_kernel,
-subframe_kernel<VERIFY>, the seven index kernels) on mixed launches, held to the ground truth of tests/decode_cases.py:
+"""The GPU-only parts of the frame decoder (flac_decode.cpp: skim_kernel, crc16_kernel, subframe_kernel<VERIFY>) and
+the single-stream index (stream_index.cpp) on mixed launches, held to the ground truth of tests/decode_cases.py:
 every frame carries the samples it was written from, and tests/test_decode_cases_cpu.py has proved on the CPU that the
 launches hold the alignments, frame lengths, wave compositions and damage they claim.  All comparisons are exact."""
 import numpy as np
