@@ -58,6 +58,7 @@ DECODE_BAD_HEADER, DECODE_HEADER_CRC, DECODE_FRAME_CRC, DECODE_PARSE = 1, 2, 4, 
 DECODE_LENGTH, DECODE_STREAM_MISMATCH, DECODE_UNSUPPORTED, DECODE_MISMATCH = 16, 32, 64, 128
 DECODE_NO_ROOM, DECODE_CHAIN = 256, 512  # totals[3] of flacenc_hip_decode_pcm: why the call stopped
 DECODE_RANGE_END = 1024  # totals[r][1] of flacenc_hip_decode_ranges: the chain ended at the span's end before the range
+SAMPLE_I32, SAMPLE_F32 = 0, 1  # FLACENC_HIP_SAMPLE_*: sample_format of flacenc_hip_decode_ranges_planar
 ENCODE_NO_ROOM = 256  # FLACENC_HIP_ENCODE_NO_ROOM: totals[s][3] of flacenc_hip_encode_streams
 INDEX_ERROR = 1 << 63
 VARIABLE_OVERFLOW = 1 << 63  # FLACENC_HIP_VARIABLE_OVERFLOW: totals[0] of flacenc_hip_encode_variable*
@@ -130,6 +131,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_md5_spans",
     "flacenc_hip_decode_streams_md5",
     "flacenc_hip_decode_ranges",
+    "flacenc_hip_decode_ranges_planar",
     "flacenc_hip_encode_streams_frames",
     "flacenc_hip_encode_streams",
     "flacenc_hip_variable_bytes_bound",
@@ -494,6 +496,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_decode_ranges.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp,
                                             C.c_uint64, vp, vp, C.c_int]
     L.flacenc_hip_decode_ranges.restype = C.c_int
+    L.flacenc_hip_decode_ranges_planar.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp,
+                                                   C.c_uint64, C.c_uint32, vp, vp, C.c_int]
+    L.flacenc_hip_decode_ranges_planar.restype = C.c_int
     L.flacenc_hip_encode_streams_frames.argtypes = [vp, C.c_size_t, C.c_uint32]
     L.flacenc_hip_encode_streams_frames.restype = C.c_size_t
     L.flacenc_hip_encode_streams.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp,
@@ -1254,6 +1259,42 @@ class Handle:
         rc = self._lib.flacenc_hip_decode_ranges(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
                                                  rtable.ctypes.data, len(rtable), max_frames, out_ptr or None, out_bytes,
                                                  totals_ptr or None, call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
+
+    def decode_ranges_planar(self, data, streams, ranges, max_frames: int, out: np.ndarray, sample_format: int,
+                             totals: np.ndarray | None = None, check: bool = True):
+        """flacenc_hip_decode_ranges_planar on host arrays: the arguments of decode_ranges, `out` the caller's
+        C-contiguous buffer of any dtype (uint8, int32, float32 ...) that holds every range's slot -- `channels` rows of
+        n_samples 4-byte elements from out_offset (in bytes, a multiple of 4), samples behind the written ones zero --
+        and `sample_format` SAMPLE_I32 or SAMPLE_F32.  -> (totals, call totals, the call's code) as for decode_ranges."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table, rtable = stream_descs(streams), range_descs(ranges)
+        if totals is None:
+            totals = np.zeros((len(rtable), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(rtable)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_ranges_planar(self._h, buf.ctypes.data, buf.size, table.ctypes.data, len(table),
+                                                        rtable.ctypes.data, len(rtable), max_frames, out.ctypes.data,
+                                                        out.nbytes, sample_format, totals.ctypes.data, call.ctypes.data,
+                                                        MEM_HOST)
+        if check:
+            self._check(rc)
+        return totals, [int(call[0]), int(call[1])], rc
+
+    def decode_ranges_planar_device(self, bytes_ptr: int, n_bytes: int, streams, ranges, max_frames: int, out_ptr: int,
+                                    out_bytes: int, sample_format: int, totals_ptr: int, check: bool = True):
+        """flacenc_hip_decode_ranges_planar on device pointers (both tables stay host memory); blocks on the handle's
+        stream.  -> (call totals, the call's code)."""
+        table, rtable = stream_descs(streams), range_descs(ranges)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_decode_ranges_planar(self._h, bytes_ptr or None, n_bytes, table.ctypes.data,
+                                                        len(table), rtable.ctypes.data, len(rtable), max_frames,
+                                                        out_ptr or None, out_bytes, sample_format, totals_ptr or None,
+                                                        call.ctypes.data, MEM_DEVICE)
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc

@@ -1,7 +1,7 @@
 // flac_decode_device.h -- what the decoder's translation units (flac_decode.cpp, stream_index.cpp, flac_decode_streams.cpp,
 // flac_decode_ranges.cpp) share on the device, each written once: the index's constants, workgroup scan, bisection and
-// chain walks, and a lane's subframe reconstruction -- its setup, the order-bucket ladder, the sample step and the
-// packed-PCM writer.  Included by those four files only.
+// chain walks, and a lane's subframe reconstruction -- its setup, the order-bucket ladder, the sample step, the
+// packed-PCM writer and the planar writer.  Included by those four files only.
 #ifndef FLAC_DECODE_DEVICE_H_
 #define FLAC_DECODE_DEVICE_H_
 
@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "flac_decode_core.h"
+#include "stream_planar_core.h"
 
 namespace flacenc_hip {
 
@@ -160,6 +161,67 @@ __device__ void write_pcm(const uint8_t* fp, uint32_t flen, uint32_t start, uint
     }
     p += step;
   }
+}
+
+// The planar writer.  LDS words per lane: 16 staged elements and up to 3 carried over, padded so that the lanes' 16-byte
+// reads fall on different banks (flac_decode.cpp's run_subframe stages 16 in 20 words the same way).
+constexpr int kPlanarStage = 20;
+
+// A lane's stage: stage[k] is the element that belongs at to[k], `to` 16-byte aligned; the first `lead` of the `fill`
+// staged words are no elements of the lane's (they stand for the row's neighbours in front of a row that does not start
+// at a 16-byte boundary) and are never stored.
+struct PlanarStage {
+  uint32_t* to;
+  uint32_t lead, fill;
+};
+
+// Stores the whole 16-byte vectors staged -- the first one element by element where it holds a lead -- and moves the
+// up to 3 elements behind them to the front of the stage.
+__device__ __forceinline__ void planar_flush(PlanarStage& s, uint32_t* stage) {
+  const uint32_t vectors = s.fill >> 2;
+  if (vectors == 0) return;
+  for (uint32_t g = 0; g < vectors; ++g) {
+    if (g == 0 && s.lead) {
+      for (uint32_t k = s.lead; k < 4; ++k) s.to[k] = stage[k];
+    } else {
+      *reinterpret_cast<uint4*>(s.to + 4 * g) = *reinterpret_cast<const uint4*>(stage + 4 * g);
+    }
+  }
+  const uint32_t rest = s.fill & 3u;
+  for (uint32_t k = 0; k < rest; ++k) stage[k] = stage[4 * vectors + k];
+  s.to += 4 * vectors;
+  s.lead = 0;
+  s.fill = rest;
+}
+
+// Samples [skip, skip + take) of channel c of a frame of `bs` samples as 4-byte elements (streamplanar::element) to
+// row[0 .. take): `row` is 4-byte aligned and nothing more, and the elements on either side of the interval are other
+// lanes' (the range's neighbouring frames), so none of them is touched.  Elements are staged in `stage` (kPlanarStage
+// words of LDS of the lane's own) at the place they have behind the last 16-byte boundary at or in front of them
+// (streamplanar::lead), and the stage is flushed where the FRAME's sample index is 15 mod 16 -- at the same trip of
+// the loop for every lane of the wave, whatever its window, so the wave runs the flush once per 16 samples -- and at the
+// end: the elements up to the first boundary leave one by one (streamplanar::split's head), whole vectors as 16-byte
+// stores, and what is left behind the last boundary one by one.  One loop over the recurrence, as in write_pcm: both
+// lanes of a stereo pair have the same skip and take -- only their rows differ -- so the exchange stays convergent
+// whatever the rows' alignment.
+template <int MAXP>
+__device__ void write_planar(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
+                             uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t sample_format, float scale,
+                             uint32_t* row, uint32_t* stage) {
+  flacdec::SubDecoder<MAXP> d;
+  if (bs) d.init(fp, flen, start, bs, sbps);
+  PlanarStage s;
+  s.lead = streamplanar::lead(reinterpret_cast<uintptr_t>(row));
+  s.fill = s.lead;
+  s.to = row - s.lead;
+  const uint32_t stop = skip + take;
+  for (uint32_t t = 0; t < stop; ++t) {
+    const int32_t v = next_sample(d, ch_tag, c);
+    if (t >= skip) stage[s.fill++] = streamplanar::element(v, sample_format, scale);  // at most 3 + 16 staged
+    if ((t & 15u) == 15u) planar_flush(s, stage);
+  }
+  planar_flush(s, stage);
+  for (uint32_t k = s.lead; k < s.fill; ++k) s.to[k] = stage[k];  // fewer than 4
 }
 
 }  // namespace flacenc_hip

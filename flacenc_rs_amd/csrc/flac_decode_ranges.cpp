@@ -18,6 +18,13 @@
 //                            of streams_decode_kernel and its writer (write_pcm, flac_decode_device.h) with a window per
 //                            frame: the recurrence runs from the frame's first sample -- it is serial -- to the last
 //                            sample wanted, and only samples inside the range are stored
+// flacenc_hip_decode_ranges_planar is the same call with another slot: rows of 4-byte elements,
+// channel after channel (stream_planar_core.h).  It differs in
+//   ranges_decode_planar_kernel  in place of ranges_decode_kernel: the same lanes with the planar writer (write_planar,
+//                            flac_decode_device.h): elements converted in registers, staged in LDS and stored as
+//                            16-byte vectors wherever the row's address allows
+//   ranges_zero_kernel       device memory only, one launch for all ranges: elements [written, n_samples) of every row
+//                            (in host memory the rows come back packed and the host zeroes behind them)
 #include "api_internal.h"
 #include "flac_decode_device.h"
 #include "stream_batch_core.h"
@@ -76,7 +83,9 @@ __global__ void __launch_bounds__(256) ranges_streams_kernel(const Desc* __restr
   ends[s] = e;
 }
 
-// lane q: the range rperm[q]
+// lane q: the range rperm[q].  r_bytes is what the range's samples take in the compact staging of the host path: packed
+// PCM, or (PLANAR) `channels` rows of 4-byte elements
+template <bool PLANAR>
 __global__ void __launch_bounds__(256) ranges_locate_kernel(const Desc* __restrict__ descs,
                                                             const Range* __restrict__ ranges,
                                                             const uint32_t* __restrict__ rperm, uint32_t n_ranges,
@@ -109,7 +118,7 @@ __global__ void __launch_bounds__(256) ranges_locate_kernel(const Desc* __restri
     if (written) atomicAdd(reinterpret_cast<unsigned long long*>(meta + M_SAMPLES), static_cast<unsigned long long>(written));
   }
   r_frames[q] = frames;
-  r_bytes[q] = written * fb;
+  r_bytes[q] = PLANAR ? streamplanar::slot_bytes(d.channels, written) : written * fb;
   r_first[q] = first_frame;
   r_written[q] = written;
   totals[4 * static_cast<size_t>(r) + 0] = written;
@@ -197,39 +206,131 @@ __global__ void __launch_bounds__(256) ranges_decode_kernel(const uint8_t* __res
   AT_WAVE_BUCKET(bucket, write_pcm<MAXP>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst));
 }
 
-}  // namespace
-}  // namespace flacenc_hip
+// The planar form: the same lanes under the same rules, each with its row of the range's slot -- channel c's n_samples
+// elements (`where` given: its `written` elements, the rows packed back to back in compact staging) -- and the planar
+// writer (write_planar, flac_decode_device.h) in place of write_pcm.
+__global__ void __launch_bounds__(256) ranges_decode_planar_kernel(const uint8_t* __restrict__ bytes,
+                                                                   const Desc* __restrict__ descs,
+                                                                   const Range* __restrict__ ranges,
+                                                                   const uint32_t* __restrict__ rperm,
+                                                                   const uint64_t* __restrict__ base,
+                                                                   const uint64_t* __restrict__ pcm,
+                                                                   const uint32_t* __restrict__ f_node,
+                                                                   const uint32_t* __restrict__ f_slot,
+                                                                   const uint32_t* __restrict__ rf_range,
+                                                                   const uint32_t* __restrict__ rf_frame,
+                                                                   const uint64_t* __restrict__ r_written,
+                                                                   const uint64_t* __restrict__ cand_pos,
+                                                                   const FrameRec* __restrict__ recs, uint32_t k_lo,
+                                                                   uint32_t k_hi, uint32_t channels,
+                                                                   const uint64_t* __restrict__ where,
+                                                                   uint32_t sample_format, uint8_t* __restrict__ out) {
+  __shared__ __attribute__((aligned(16))) uint32_t stage_all[256 * kPlanarStage];
+  const uint32_t per_block = blockDim.x / channels;  // frames never straddle workgroups
+  const uint32_t lf = threadIdx.x / channels, c = threadIdx.x % channels;
+  const uint64_t k = static_cast<uint64_t>(k_lo) + static_cast<uint64_t>(blockIdx.x) * per_block + lf;
+  uint32_t bs = 0, skip = 0, take = 0, ch_tag = 0, flen = 0, start = 0, bps = 1;
+  const uint8_t* fp = bytes;
+  uint8_t* dst = out;
+  if (lf < per_block && k < k_hi) {
+    const uint32_t q = rf_range[k], m = rf_frame[k];
+    const Range& x = ranges[rperm[q]];
+    const Desc& d = descs[x.stream];
+    const uint32_t node = f_node[m];
+    const FrameRec& r = recs[node];
+    const uint64_t fb = static_cast<uint64_t>(d.channels) * d.bytes_per_sample;
+    const uint64_t pos = (pcm[m] - pcm[base[f_slot[m]]]) / fb;
+    const uint64_t written = r_written[q];
+    const streamranges::Window w = streamranges::window(pos, r.block_size, x.first_sample, x.first_sample + written);
+    bs = r.block_size;
+    skip = w.skip;
+    take = w.take;
+    ch_tag = (r.info >> 4) & 15u;
+    flen = r.len;
+    start = r.sub_bit[c];
+    bps = d.bits_per_sample;
+    fp = bytes + cand_pos[node];
+    dst = out + (where ? streamplanar::element_offset(where[q], written, c, w.dst)
+                       : streamplanar::element_offset(x.out_offset, x.n_samples, c, w.dst));
+  }
+  const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
+  const float scale = streamplanar::scale_of(bps);
+  uint32_t* stage = stage_all + threadIdx.x * kPlanarStage;
+  const int bucket = lane_bucket(fp, flen, start, bs, sbps);
+  AT_WAVE_BUCKET(bucket, write_planar<MAXP>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, sample_format, scale,
+                                            reinterpret_cast<uint32_t*>(dst), stage));
+}
 
-using namespace flacenc_hip;
+// The zero pass of the planar form in device memory: elements [written, n_samples) of every row of every range.  Rows
+// are numbered in rslot order (the ranges of c channels have c rows each); workgroup (x, y) takes rows x, x + gridDim.x,
+// ... and of each row's interval the y-th share of its 16-byte vectors, lane after lane (streamplanar::split: scalar
+// elements up to the first 16-byte boundary and behind the last).
+__global__ void __launch_bounds__(256) ranges_zero_kernel(const Range* __restrict__ ranges,
+                                                          const uint32_t* __restrict__ rperm,
+                                                          const uint64_t* __restrict__ r_written, ClassLo rslot_lo,
+                                                          uint32_t n_rows, uint8_t* __restrict__ out) {
+  const uint32_t lane = blockIdx.y * blockDim.x + threadIdx.x, lanes = gridDim.y * blockDim.x;
+  for (uint32_t row = blockIdx.x; row < n_rows; row += gridDim.x) {
+    uint32_t channels = 1, row0 = 0, q0 = 0, seen = 0;
+#pragma unroll
+    for (uint32_t c = 1; c <= 8; ++c) {
+      const uint32_t rows = c * (rslot_lo.lo[c + 1] - rslot_lo.lo[c]);
+      if (row >= seen && row - seen < rows) {
+        channels = c;
+        row0 = seen;
+        q0 = rslot_lo.lo[c];
+      }
+      seen += rows;
+    }
+    const uint32_t q = q0 + (row - row0) / channels, c = (row - row0) % channels;
+    const Range& x = ranges[rperm[q]];
+    const streamplanar::Interval z = streamplanar::zero_interval(r_written[q], x.n_samples);
+    if (!z.count) continue;
+    uint32_t* p = reinterpret_cast<uint32_t*>(out + streamplanar::element_offset(x.out_offset, x.n_samples, c, z.first));
+    const streamplanar::Split s = streamplanar::split(reinterpret_cast<uintptr_t>(p), z.count);
+    if (lane < s.head) p[lane] = 0u;
+    uint4* body = reinterpret_cast<uint4*>(p + s.head);
+    for (uint64_t v = lane; v < s.body / 4; v += lanes) body[v] = make_uint4(0u, 0u, 0u, 0u);
+    if (lane < s.tail) p[s.head + s.body + lane] = 0u;
+  }
+}
 
-extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
-                                         const void* streams, size_t n_streams, const void* ranges, size_t n_ranges,
-                                         size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
-                                         uint64_t call_totals[2], int memory_kind) {
+// Both calls.  `planar`: the slots are rows of 4-byte elements in `sample_format`, else packed PCM.
+int decode_ranges_call(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                       size_t n_streams, const void* ranges, size_t n_ranges, size_t max_frames, uint8_t* out,
+                       uint64_t out_bytes, bool planar, uint32_t sample_format, uint64_t* totals,
+                       uint64_t call_totals[2], int memory_kind) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  const std::string who = planar ? "decode_ranges_planar" : "decode_ranges";
   uint64_t* plan = h->last_ranges_plan;  // launches, synchronisations, transfers, channel classes of the ranges
   plan[0] = plan[1] = plan[2] = plan[3] = 0;
   if (!call_limits_ok(memory_kind, n_streams, max_frames, n_bytes) || !bytes || !streams || !ranges || !out || !totals ||
       !call_totals || n_ranges > streamranges::MAX_RANGES) {
-    h->last_error = "decode_ranges: null pointer, unknown memory kind, more than 2^24 streams or ranges, max_frames above "
-                    "2^30 or n_bytes >= 16 TiB";
+    h->last_error = who + ": null pointer, unknown memory kind, more than 2^24 streams or ranges, max_frames above "
+                          "2^30 or n_bytes >= 16 TiB";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  if (planar && sample_format != FLACENC_HIP_SAMPLE_I32 && sample_format != FLACENC_HIP_SAMPLE_F32) {
+    h->last_error = who + ": unknown sample_format";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   const Desc* table = static_cast<const Desc*>(streams);
   const Range* rtable = static_cast<const Range*>(ranges);
   int rc = streamranges::check_spans(table, n_streams, n_bytes);
   if (rc == FLACENC_HIP_ERR_UNSUPPORTED) {
-    h->last_error = "decode_ranges: a stream's bits_per_sample not in 4..=24";
+    h->last_error = who + ": a stream's bits_per_sample not in 4..=24";
     return rc;
   }
   if (rc != FLACENC_HIP_OK) {
-    h->last_error = "decode_ranges: spans not ascending, overlapping or past n_bytes, channels not in 1..=8, "
-                    "max_block_size not in 1..=65536 or bytes_per_sample not in ceil(bits / 8)..=4";
+    h->last_error = who + ": spans not ascending, overlapping or past n_bytes, channels not in 1..=8, "
+                          "max_block_size not in 1..=65536 or bytes_per_sample not in ceil(bits / 8)..=4";
     return rc;
   }
-  if ((rc = streamranges::check_ranges(rtable, n_ranges, table, n_streams, out_bytes)) != FLACENC_HIP_OK) {
-    h->last_error = "decode_ranges: a range's stream >= n_streams, reserved != 0, first_sample + n_samples overflows or "
-                    "its slot reaches past out_bytes";
+  rc = planar ? streamplanar::check_ranges(rtable, n_ranges, table, n_streams, out_bytes)
+              : streamranges::check_ranges(rtable, n_ranges, table, n_streams, out_bytes);
+  if (rc != FLACENC_HIP_OK) {
+    h->last_error = who + ": a range's stream >= n_streams, reserved != 0, first_sample + n_samples overflows, its slot "
+                          "reaches past out_bytes or (planar) its out_offset is not a multiple of 4";
     return rc;
   }
   call_totals[0] = call_totals[1] = 0;
@@ -266,7 +367,7 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
   rq.n_streams = n_streams;
   rq.max_frames = max_frames;
   rq.host = host;
-  rq.who = "decode_ranges";
+  rq.who = planar ? "decode_ranges_planar" : "decode_ranges";
   rq.extra_words = host ? (n_ranges + 1) + 4 * n_ranges : 0;
   rq.extra_table = h->ranges_table.data();
   rq.extra_table_bytes = h->ranges_table.size();
@@ -290,9 +391,14 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
   // ---- which frames every range touches ----
   COUNTED_LAUNCH(plan, ranges_streams_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, ix.descs, ix.perm, ns, ix.base,
                  ix.pcm, ix.bad, ix.f_node, ix.cand_pos, ix.s_end, ix.s_why, ix.counters, ends);
-  COUNTED_LAUNCH(plan, ranges_locate_kernel, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges, rperm, nr,
-                 ends, ix.pcm, ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written, d_totals,
-                 ix.meta);
+  if (planar)
+    COUNTED_LAUNCH(plan, ranges_locate_kernel<true>, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges, rperm,
+                   nr, ends, ix.pcm, ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written, d_totals,
+                   ix.meta);
+  else
+    COUNTED_LAUNCH(plan, ranges_locate_kernel<false>, dim3(ceil_div(nr, 256)), dim3(256), 0, st, ix.descs, d_ranges,
+                   rperm, nr, ends, ix.pcm, ix.f_node, ix.cand_pos, ix.counters, r_frames, r_bytes, r_first, r_written,
+                   d_totals, ix.meta);
   HIP_TRY(h, launch_scan2(r_frames, host ? r_bytes : nullptr, nr, r_base, where, st));
   ++plan[0];
   COUNTED_LAUNCH(plan, ranges_verdict_kernel, dim3(1), dim3(1), 0, st, r_base, nr, static_cast<uint64_t>(max_frames),
@@ -332,13 +438,29 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
     const uint32_t k_lo = static_cast<uint32_t>(r_meta[M_CLASS + c]), k_hi = static_cast<uint32_t>(r_meta[M_CLASS + c + 1]);
     const uint32_t per_block = 256 / c;
     // (a class whose ranges touch no frame still counts as a launch of the plan: the plan depends on the classes only)
-    COUNTED_LAUNCH(plan, ranges_decode_kernel, dim3(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1),
-                   dim3(per_block * c), 0, st, ix.d_bytes, ix.descs, d_ranges, rperm, ix.base, ix.pcm, ix.f_node, ix.f_slot,
-                   rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo, k_hi, c, where, d_out);
+    const dim3 grid(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1), block(per_block * c);
+    if (planar)
+      COUNTED_LAUNCH(plan, ranges_decode_planar_kernel, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
+                     ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo,
+                     k_hi, c, where, sample_format, d_out);
+    else
+      COUNTED_LAUNCH(plan, ranges_decode_kernel, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm, ix.base,
+                     ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo, k_hi, c,
+                     where, d_out);
+  }
+  if (planar && !host) {  // the rows' tails, all ranges in one launch (host memory: the host threads zero them below)
+    uint64_t longest = 0;
+    for (size_t r = 0; r < n_ranges; ++r) longest = std::max<uint64_t>(longest, rtable[r].n_samples);
+    uint32_t n_rows = 0;
+    for (uint32_t c = 1; c <= 8; ++c) n_rows += c * (rslot_lo.lo[c + 1] - rslot_lo.lo[c]);
+    // a share of 4096 vectors (16 per lane) of the longest row per workgroup, 64 shares at the most
+    const uint32_t shares = static_cast<uint32_t>(std::min<uint64_t>(64, std::max<uint64_t>(1, (longest + 16383) / 16384)));
+    COUNTED_LAUNCH(plan, ranges_zero_kernel, dim3(std::min<uint32_t>(n_rows, 32768), shares), dim3(256), 0, st, d_ranges,
+                   rperm, r_written, rslot_lo, n_rows, d_out);
   }
   HIP_TRY(h, hipGetLastError());
   // host memory: one transfer of the ranges' PCM back to back into pinned staging, then every range to its slot
-  if (host && (rc = download_pcm(h, plan, "decode_ranges", d_out, pcm_bytes)) != FLACENC_HIP_OK) return rc;
+  if (host && (rc = download_pcm(h, plan, rq.who, d_out, pcm_bytes)) != FLACENC_HIP_OK) return rc;
   HIP_TRY(h, hipStreamSynchronize(st));
   ++plan[1];
   drain.armed = false;
@@ -346,11 +468,48 @@ extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* b
     const uint8_t* staged = static_cast<const uint8_t*>(h->pin_out[0]);
     for (size_t q = 0; q < n_ranges; ++q) {
       const uint64_t n = r_where[q + 1] - r_where[q];
-      if (n) h->copy_pool->copy(out + rtable[p_rperm[q]].out_offset, staged + r_where[q], static_cast<size_t>(n));
+      const Range& x = rtable[p_rperm[q]];
+      if (!planar) {
+        if (n) h->copy_pool->copy(out + x.out_offset, staged + r_where[q], static_cast<size_t>(n));
+        continue;
+      }
+      // staged: the range's rows of `written` elements back to back; each to the front of its row of the slot, zeros
+      // behind it
+      const uint32_t channels = table[x.stream].channels;
+      const uint64_t written = n / (static_cast<uint64_t>(channels) * streamplanar::ELEM);
+      const streamplanar::Interval z = streamplanar::zero_interval(written, x.n_samples);
+      for (uint32_t c = 0; c < channels; ++c) {
+        uint8_t* row = out + streamplanar::element_offset(x.out_offset, x.n_samples, c, 0);
+        if (written)
+          h->copy_pool->copy(row, staged + streamplanar::element_offset(r_where[q], written, c, 0),
+                             static_cast<size_t>(written * streamplanar::ELEM));
+        if (z.count) std::memset(row + z.first * streamplanar::ELEM, 0, static_cast<size_t>(z.count * streamplanar::ELEM));
+      }
     }
     std::memcpy(totals, r_totals, n_ranges * 32);
   }
   call_totals[0] = r_meta[M_FRAMES];
   call_totals[1] = r_meta[M_SAMPLES];
   return FLACENC_HIP_OK;
+}
+
+}  // namespace
+}  // namespace flacenc_hip
+
+extern "C" int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
+                                         const void* streams, size_t n_streams, const void* ranges, size_t n_ranges,
+                                         size_t max_frames, uint8_t* out, uint64_t out_bytes, uint64_t* totals,
+                                         uint64_t call_totals[2], int memory_kind) {
+  return flacenc_hip::decode_ranges_call(h, bytes, n_bytes, streams, n_streams, ranges, n_ranges, max_frames, out,
+                                         out_bytes, false, 0, totals, call_totals, memory_kind);
+}
+
+extern "C" int flacenc_hip_decode_ranges_planar(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes,
+                                                const void* streams, size_t n_streams, const void* ranges,
+                                                size_t n_ranges, size_t max_frames, void* out, uint64_t out_bytes,
+                                                uint32_t sample_format, uint64_t* totals, uint64_t call_totals[2],
+                                                int memory_kind) {
+  return flacenc_hip::decode_ranges_call(h, bytes, n_bytes, streams, n_streams, ranges, n_ranges, max_frames,
+                                         static_cast<uint8_t*>(out), out_bytes, true, sample_format, totals, call_totals,
+                                         memory_kind);
 }

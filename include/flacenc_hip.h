@@ -1114,6 +1114,7 @@ int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, 
  * gives a stop reason, never a fault, and changes nothing for ranges on other streams.
  * The call blocks and runs on the handle's stream; its launches, synchronisations and transfers depend on the channel
  * counts the ranges' streams have and on max_frames, not on n_streams or n_ranges.  There is no stream-taking form yet.
+ * The same ranges as planar int32 / float32 rows, a [B, C, T] tensor in place: flacenc_hip_decode_ranges_planar below.
  */
 #define FLACENC_HIP_DECODE_RANGE_END 1024u
 struct flacenc_hip_range_desc {
@@ -1127,6 +1128,41 @@ typedef struct flacenc_hip_range_desc flacenc_hip_range_desc;
 int flacenc_hip_decode_ranges(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
                               size_t n_streams, const void* ranges, size_t n_ranges, size_t max_frames, uint8_t* out,
                               uint64_t out_bytes, uint64_t* totals, uint64_t call_totals[2], int memory_kind);
+
+/*
+ * flacenc_hip_decode_ranges with the output a model reads: every range's samples as planar 4-byte elements, so that a
+ * batch of crops is a [B, C, T] int32 or float32 tensor when the call returns, with no pass over the data behind it.
+ * bytes, n_bytes, streams, n_streams, ranges, n_ranges, max_frames, totals, call_totals and memory_kind are those of
+ * flacenc_hip_decode_ranges -- one pair of tables serves both calls -- and so are totals[r][0..3], call_totals, the
+ * FLACENC_HIP_INDEX_ERROR rule (nothing is written, all totals are zero), every error return, "nothing is written on
+ * error" and the behaviour on garbage (a stop reason, never a fault, nothing changes for ranges on other streams).  A
+ * stream's bytes_per_sample is validated as before and otherwise plays no part in the layout.  What differs is the slot:
+ *   out, out_bytes   range r on a stream of C channels owns C * n_samples * 4 bytes from out_offset, a multiple of 4:
+ *                    C rows of n_samples elements, element (channel c, sample i) the 4-byte value at out_offset +
+ *                    (c * n_samples + i) * 4.  With w = totals[r][0], elements i < w of every row are the decoded
+ *                    samples first_sample + i; elements w <= i < n_samples are zero (0, resp. +0.0f).  When the call
+ *                    returns FLACENC_HIP_OK without FLACENC_HIP_INDEX_ERROR the whole of every slot is defined; bytes of
+ *                    `out` in no slot are untouched.  Slots must be disjoint, unchecked as for flacenc_hip_decode_ranges.
+ *                    A batch [B, C, T] is n_samples = T and out_offset = b * C * T * 4
+ *   sample_format    FLACENC_HIP_SAMPLE_I32 or FLACENC_HIP_SAMPLE_F32
+ * The value rule, for every input -- hand-built frames whose predictions wrap included: the value is the int32 the
+ * decoder reconstructs, exactly what flacenc_hip_decode_ranges stores when the stream's bytes_per_sample is 4.
+ * FLACENC_HIP_SAMPLE_I32 stores it; FLACENC_HIP_SAMPLE_F32 stores that int32 converted to float with round-to-nearest-
+ * even, multiplied by 2^-(bits_per_sample - 1).  For every value that fits the stream's bit depth (at most 24 bits) both
+ * steps are exact: the element is the rational value / 2^(bits_per_sample - 1), in [-1, 1).
+ * Further FLACENC_HIP_ERR_BAD_ARGUMENT cases, nothing written: an out_offset that is not a multiple of 4, a slot of this
+ * size that reaches past out_bytes, an unknown sample_format.
+ * Host memory: the ranges' elements come back in one transfer into pinned staging, and the handle's host threads place
+ * the rows and zero their tails; the number of transfers does not depend on n_ranges.  Device memory: one launch more
+ * than flacenc_hip_decode_ranges (the zero pass over all ranges), whatever n_ranges is.  There is no stream-taking form,
+ * as for flacenc_hip_decode_ranges.
+ */
+#define FLACENC_HIP_SAMPLE_I32 0u   /* the decoded value */
+#define FLACENC_HIP_SAMPLE_F32 1u   /* (float)value * 2^-(bits_per_sample - 1) */
+int flacenc_hip_decode_ranges_planar(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                                     size_t n_streams, const void* ranges, size_t n_ranges, size_t max_frames, void* out,
+                                     uint64_t out_bytes, uint32_t sample_format, uint64_t* totals,
+                                     uint64_t call_totals[2], int memory_kind);
 
 /*
  * The way there in one call: a batch of PCM streams to FLAC frames, what flacenc_hip_encode_pcm does for one stream, for

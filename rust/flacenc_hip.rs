@@ -433,6 +433,16 @@ extern "C" {
         n_ranges: usize, max_frames: usize, out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64,
         memory_kind: c_int,
     ) -> c_int;
+    /// `flacenc_hip_decode_ranges` with planar slots: range `r` on a stream of `C` channels owns `C * n_samples * 4`
+    /// bytes from `out_offset` (a multiple of 4), element (channel `c`, sample `i`) at `out_offset + (c * n_samples + i)
+    /// * 4`; `sample_format` is `SAMPLE_I32` (the decoded value) or `SAMPLE_F32` (that value as `f32` times
+    /// `2^-(bits_per_sample - 1)`); elements behind the `totals[r][0]` written ones are zero.  Tables, `totals` and
+    /// `call_totals` as for `flacenc_hip_decode_ranges`.
+    pub fn flacenc_hip_decode_ranges_planar(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, ranges: *const c_void,
+        n_ranges: usize, max_frames: usize, out: *mut c_void, out_bytes: u64, sample_format: u32, totals: *mut u64,
+        call_totals: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     /// The sum of `ceil(total_samples / block_size)` over `n_streams` `PcmStreamDesc`: the entries `frame_lengths` needs.
     pub fn flacenc_hip_encode_streams_frames(streams: *const c_void, n_streams: usize, block_size: u32) -> usize;
     /// A batch of PCM streams to frames in one call: `streams` points at `n_streams` `PcmStreamDesc` in host memory; per
@@ -533,6 +543,9 @@ pub const DECODE_NO_ROOM: u32 = 256;
 pub const DECODE_CHAIN: u32 = 512;
 /// `totals[r][1]` of `flacenc_hip_decode_ranges`: the span's chain ended at the span's end before the range did.
 pub const DECODE_RANGE_END: u32 = 1024;
+/// `sample_format` of `flacenc_hip_decode_ranges_planar`: the decoded `i32` / that value as `f32` in [-1, 1).
+pub const SAMPLE_I32: u32 = 0;
+pub const SAMPLE_F32: u32 = 1;
 /// Set in `n_frames` by `flacenc_hip_index_frames_async` when the chain of frames does not end at `n_bytes`.
 pub const INDEX_ERROR: u64 = 1 << 63;
 
