@@ -72,7 +72,8 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan",
                  "flacenc_hip_debug_last_decode_streams_plan", "flacenc_hip_debug_last_decode_ranges_plan",
                  "flacenc_hip_debug_set_encode_streams_chunk",
-                 "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill")
+                 "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill",
+                 "flacenc_hip_debug_set_planar_fill_form")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -134,6 +135,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_ranges_planar",
     "flacenc_hip_encode_streams_frames",
     "flacenc_hip_encode_streams",
+    "flacenc_hip_encode_streams_planar",
     "flacenc_hip_variable_bytes_bound",
     "flacenc_hip_variable_max_frames",
     "flacenc_hip_encode_variable_async",
@@ -378,6 +380,7 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
         L.flacenc_hip_debug_last_stream_buffers.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(L, "flacenc_hip_debug_set_encode_streams_chunk"):
         L.flacenc_hip_debug_set_encode_streams_chunk.argtypes = [vp, C.c_size_t]
+        L.flacenc_hip_debug_set_planar_fill_form.argtypes = [vp, C.c_int]
         L.flacenc_hip_debug_streams_fill.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32,
                                                      vp, C.c_size_t]
     if hasattr(L, "flacenc_hip_debug_set_decode_plan"):
@@ -504,6 +507,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_encode_streams.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, vp, C.c_size_t, C.c_uint32, vp,
                                              C.c_uint64, vp, C.c_size_t, vp, vp, C.c_int]
     L.flacenc_hip_encode_streams.restype = C.c_int
+    L.flacenc_hip_encode_streams_planar.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_uint64, C.c_uint32, C.c_uint64, vp,
+                                                    C.c_size_t, C.c_uint32, vp, C.c_uint64, vp, C.c_size_t, vp, vp, vp, vp,
+                                                    C.c_int]
+    L.flacenc_hip_encode_streams_planar.restype = C.c_int
     L.flacenc_hip_variable_bytes_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64]
     L.flacenc_hip_variable_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_variable_max_frames.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64]
@@ -789,6 +796,19 @@ class Handle:
         self._check(self._hook("flacenc_hip_debug_last_encode_streams_plan")(self._h, plan.ctypes.data))
         names = ("launches", "syncs", "transfers", "classes", "full_runs", "tail_runs", "calls")
         return {k: int(v) for k, v in zip(names, plan)}
+
+    def debug_last_encode_streams_planar_plan(self):
+        """debug_last_encode_streams_plan after an encode_streams_planar call, with `digest_launches`: how many of
+        `launches` the digests cost."""
+        plan = np.zeros(8, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_last_encode_streams_plan")(self._h, plan.ctypes.data))
+        names = ("launches", "syncs", "transfers", "classes", "full_runs", "tail_runs", "calls", "digest_launches")
+        return {k: int(v) for k, v in zip(names, plan)}
+
+    def debug_set_planar_fill_form(self, form: int):
+        """How encode_streams_planar's fill kernel loads in the calls that follow: 1 aligned 16-byte loads brought into
+        place (the product's form), 0 dword loads (flacenc_hip_debug.h).  The bytes do not depend on it."""
+        self._check(self._hook("flacenc_hip_debug_set_planar_fill_form")(self._h, int(form)))
 
     def debug_streams_fill(self, bytes_ptr: int, total_samples: int, channels: int, bytes_per_sample: int, n_frames: int,
                            block_size: int, frames_ptr: int, stride: int, check: bool = True) -> int:
@@ -1412,6 +1432,55 @@ class Handle:
                                                   len(table), block_size, out_ptr or None, out_bytes,
                                                   frame_lengths_ptr or None, max_frames, totals_ptr or None,
                                                   call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(call[0]), int(call[1])], rc
+
+    def encode_streams_planar(self, samples: np.ndarray, sample_format: int, row_pitch: int, streams, cfg: FrameConfig,
+                              block_size: int, out: np.ndarray, frame_lengths: np.ndarray | None = None,
+                              totals: np.ndarray | None = None, max_frames: int | None = None, digests: bool = True,
+                              clipped: bool = True, samples_bytes: int | None = None, check: bool = True):
+        """flacenc_hip_encode_streams_planar on host arrays: `samples` is a C-contiguous array of 4-byte elements (int32
+        for SAMPLE_I32, float32 for SAMPLE_F32; any shape: the table's offsets are bytes into it), `streams` the table of
+        encode_streams, `out` the caller's uint8 buffer (written in place).  -> (frame lengths, totals, call totals,
+        digests uint8 [n_streams, 16] or None, clipped uint64 [n_streams] or None, the call's code)."""
+        assert samples.dtype.itemsize == 4 and samples.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table = pcm_stream_descs(streams)
+        n_frames = int(self._lib.flacenc_hip_encode_streams_frames(table.ctypes.data, len(table), block_size))
+        if frame_lengths is None:
+            frame_lengths = np.zeros(max(1, min(n_frames, 1 << 31)), np.uint32)
+        assert frame_lengths.dtype == np.uint32 and frame_lengths.flags["C_CONTIGUOUS"]
+        if totals is None:
+            totals = np.zeros((max(1, len(table)), 4), np.uint64)
+        assert totals.dtype == np.uint64 and totals.flags["C_CONTIGUOUS"] and totals.size >= 4 * len(table)
+        call = np.zeros(2, np.uint64)
+        dig = np.zeros((max(1, len(table)), 16), np.uint8) if digests else None
+        clip = np.zeros(max(1, len(table)), np.uint64) if clipped else None
+        base = samples if samples.size else np.zeros(1, np.int32)
+        obase = out if out.size else np.zeros(1, np.uint8)
+        rc = self._lib.flacenc_hip_encode_streams_planar(
+            self._h, C.byref(cfg), base.ctypes.data, samples.nbytes if samples_bytes is None else samples_bytes,
+            sample_format, row_pitch, table.ctypes.data, len(table), block_size, obase.ctypes.data, out.size,
+            frame_lengths.ctypes.data, frame_lengths.size if max_frames is None else max_frames, totals.ctypes.data,
+            call.ctypes.data, dig.ctypes.data if digests else None, clip.ctypes.data if clipped else None, MEM_HOST)
+        if check:
+            self._check(rc)
+        return (frame_lengths[:n_frames] if rc == OK else frame_lengths, totals[:len(table)], [int(call[0]), int(call[1])],
+                dig[:len(table)] if digests else None, clip[:len(table)] if clipped else None, rc)
+
+    def encode_streams_planar_device(self, samples_ptr: int, samples_bytes: int, sample_format: int, row_pitch: int, streams,
+                                     cfg: FrameConfig, block_size: int, out_ptr: int, out_bytes: int,
+                                     frame_lengths_ptr: int, max_frames: int, totals_ptr: int, digests_ptr: int = 0,
+                                     clipped_ptr: int = 0, check: bool = True):
+        """flacenc_hip_encode_streams_planar on device pointers (the table stays host memory; digests_ptr / clipped_ptr 0:
+        not asked for); blocks on the handle's stream.  -> (call totals, the call's code)."""
+        table = pcm_stream_descs(streams)
+        call = np.zeros(2, np.uint64)
+        rc = self._lib.flacenc_hip_encode_streams_planar(
+            self._h, C.byref(cfg), samples_ptr or None, samples_bytes, sample_format, row_pitch, table.ctypes.data,
+            len(table), block_size, out_ptr or None, out_bytes, frame_lengths_ptr or None, max_frames, totals_ptr or None,
+            call.ctypes.data, digests_ptr or None, clipped_ptr or None, MEM_DEVICE)
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc

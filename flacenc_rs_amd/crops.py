@@ -1,11 +1,12 @@
 """A batch of crops of FLAC streams as one torch tensor: flacenc_hip_decode_ranges_planar writes every crop's samples as
 planar float32 (or int32) rows straight into a [B, C, T] tensor, so nothing touches the data between the decoder and the
-model -- no widening, no transpose, no scaling, no padding, no per-crop copy."""
+model -- no widening, no transpose, no scaling, no padding, no per-crop copy.  encode_crops is the way back:
+flacenc_hip_encode_streams_planar reads such a tensor as it lies and gives frames, digests and clip counts."""
 import numpy as np
 
 from . import _capi
 
-__all__ = ["decode_crops"]
+__all__ = ["decode_crops", "encode_crops"]
 
 
 def decode_crops(handle, d_bytes, streams, crops, T, dtype=None, max_frames=None):
@@ -65,3 +66,69 @@ def decode_crops(handle, d_bytes, streams, crops, T, dtype=None, max_frames=None
     if call[0] & _capi.INDEX_ERROR:
         raise RuntimeError("decode_crops: the streams or the crops hold more frames than max_frames = %d" % max_frames)
     return out, totals
+
+
+def encode_crops(handle, x, lengths, bits_per_sample, sample_rate, cfg, block_size, bytes_per_sample=None, md5=True):
+    """A [B, C, T] tensor, item b valid up to lengths[b] samples -> one FLAC frame sequence per item.
+
+    handle            a _capi.Handle
+    x                 contiguous torch.float32 (samples in [-1, 1), quantised as the inverse of decode_crops's scaling:
+                      times 2^(bits_per_sample - 1), round to nearest even, clamp; NaN is 0) or torch.int32 (the samples)
+                      tensor on the handle's GPU (the call runs in device memory) or on the CPU (host memory)
+    lengths           B sample counts <= T, or None for T everywhere
+    cfg               a _capi.FrameConfig (flags included)
+    bytes_per_sample  the sample width of the packed PCM the digests are taken over; default ceil(bits_per_sample / 8),
+                      which makes them the STREAMINFO digests
+    md5               False: no digest is computed (and no packed image of the samples is ever built)
+
+    -> dict(frames, items, frame_lengths, digests, clipped), every tensor on x's device: `frames` the uint8 buffer that
+    holds every item's frames, items int64 [B, 3] = (offset into frames, bytes, frames) per item, frame_lengths int32
+    over all items in order (item b's start at the sum of the items' frame counts before it), digests uint8 [B, 16] (None
+    with md5=False), clipped int64 [B]: the elements of the item that clamped or were NaN (0 for int32).  Slots are sized
+    from the frame-bytes bounds, so every frame of every item is there.  The tables are built with array arithmetic; no
+    Python work is done per item on the data."""
+    import torch
+
+    if x.dtype not in (torch.float32, torch.int32) or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("encode_crops: x must be a contiguous [B, C, T] float32 or int32 tensor")
+    B, C, T = (int(v) for v in x.shape)
+    n = np.full(B, T, np.int64) if lengths is None else np.asarray(lengths, np.int64).reshape(-1)
+    if len(n) != B or (B and (n.min() < 0 or n.max() > T)) or not 1 <= C <= 8:
+        raise ValueError("encode_crops: one length in 0..T per item, 1..8 channels")
+    bps = (bits_per_sample + 7) // 8 if bytes_per_sample is None else int(bytes_per_sample)
+    bound = handle.frame_bytes_bound(block_size, bits_per_sample) if C == 2 else \
+        handle.frame_bytes_bound_channels(C, block_size, bits_per_sample)
+    n_frames = -(-n // block_size)
+    room = (n_frames * (bound + 8) + 15) // 16 * 16       # (+ 8: a frame number takes up to 5 bytes more than number 0)
+    table = np.zeros(B, _capi.PCM_STREAM_DESC_DTYPE)
+    table["offset"] = np.arange(B, dtype=np.uint64) * np.uint64(C * T * 4)
+    table["total_samples"] = n
+    table["out_offset"] = np.cumsum(room) - room
+    table["out_capacity"] = room
+    table["channels"], table["bits_per_sample"], table["bytes_per_sample"], table["sample_rate"] = C, bits_per_sample, bps, sample_rate
+    total_frames, out_bytes = int(n_frames.sum()), int(room.sum())
+    dev = x.device
+    frames = torch.zeros(max(out_bytes, 1), dtype=torch.uint8, device=dev)
+    flen = torch.zeros(max(total_frames, 1), dtype=torch.int32, device=dev)
+    totals = torch.zeros((max(B, 1), 4), dtype=torch.int64, device=dev)
+    digests = torch.zeros((max(B, 1), 16), dtype=torch.uint8, device=dev) if md5 else None
+    clipped = torch.zeros(max(B, 1), dtype=torch.int64, device=dev)
+    fmt = _capi.SAMPLE_F32 if x.dtype == torch.float32 else _capi.SAMPLE_I32
+    if B:
+        src = x if x.numel() else torch.zeros(1, dtype=x.dtype, device=dev)   # (T == 0: never a null pointer)
+        if x.is_cuda:
+            torch.cuda.synchronize(dev)   # the call runs on the handle's own stream
+            handle.encode_streams_planar_device(src.data_ptr(), x.numel() * 4, fmt, T, table, cfg, block_size,
+                                                frames.data_ptr(), out_bytes, flen.data_ptr(), max(total_frames, 1),
+                                                totals.data_ptr(), digests.data_ptr() if md5 else 0, clipped.data_ptr())
+        else:
+            _, _, _, dig, clip, _ = handle.encode_streams_planar(
+                src.numpy(), fmt, T, table, cfg, block_size, frames.numpy()[:out_bytes],
+                flen.numpy().view(np.uint32), totals.numpy().view(np.uint64), digests=md5, samples_bytes=x.numel() * 4)
+            if md5:
+                digests.numpy()[:B] = dig
+            clipped.numpy()[:B] = clip.astype(np.int64)
+    items = torch.stack([torch.from_numpy(table["out_offset"].astype(np.int64)).to(dev), totals[:B, 1], totals[:B, 0]], 1) \
+        if B else torch.zeros((0, 3), dtype=torch.int64, device=dev)
+    return dict(frames=frames[:out_bytes], items=items, frame_lengths=flen[:total_frames],
+                digests=digests[:B] if md5 else None, clipped=clipped[:B])

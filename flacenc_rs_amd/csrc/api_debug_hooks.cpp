@@ -118,6 +118,12 @@ int flacenc_hip_debug_last_encode_streams_plan(flacenc_hip_handle* h, uint64_t p
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_set_planar_fill_form(flacenc_hip_handle* h, int form) {
+  if (!h || (form != 0 && form != 1)) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  h->planar_fill_form = form;
+  return FLACENC_HIP_OK;
+}
+
 int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t total_samples, uint32_t channels,
                                    uint32_t bytes_per_sample, size_t n_frames, uint32_t block_size, int32_t* frames,
                                    size_t stride) {

@@ -224,6 +224,9 @@ struct flacenc_hip_handle {
   // frame-level call of flacenc_hip_encode_streams in place of its rule (0: the rule), and what the last call did
   size_t encode_streams_chunk_override = 0;
   uint64_t last_encode_streams_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // measurement hook, see flacenc_hip_debug_set_planar_fill_form: how planar_fill_kernel loads (1 aligned 16-byte loads
+  // brought into place, the product's form: the faster one; 0 dwords)
+  int planar_fill_form = 1;
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
   // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
   // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch
@@ -244,6 +247,11 @@ struct flacenc_hip_handle {
       return FLACENC_HIP_ERR_DEVICE;              \
     }                                             \
   } while (0)
+
+namespace planarenc {
+struct Frame;
+struct Stream;
+}  // namespace planarenc
 
 namespace flacenc_hip {
 
@@ -333,6 +341,33 @@ hipError_t launch_md5_spans(const uint8_t* bytes, const uint64_t* offsets, uint3
 hipError_t launch_streams_fill(const uint8_t* pcm, const streamenc::LaunchFrame* table, uint32_t n_frames,
                                uint32_t channels, uint32_t bytes_per_sample, uint32_t row0, size_t stride, int32_t* rows,
                                hipStream_t stream);
+
+// Both flacenc_hip_encode_streams (planar null) and flacenc_hip_encode_streams_planar (pcm null): the one body.
+struct PlanarSource {
+  const void* samples;
+  uint64_t samples_bytes;
+  uint32_t sample_format;
+  uint64_t row_pitch;
+  uint8_t* digests;   // null: no packed image is built
+  uint64_t* clipped;  // null: not counted
+};
+int encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const uint8_t* pcm, uint64_t pcm_bytes,
+                          const PlanarSource* planar, const void* streams, size_t n_streams, uint32_t block_size,
+                          uint8_t* out, uint64_t out_bytes, uint32_t* frame_lengths, size_t max_frames, uint64_t* totals,
+                          uint64_t call_totals[2], int memory_kind);
+
+// ---- encode_streams_planar.cpp ----
+// planar_fill_kernel on `stream`: what launch_streams_fill does, from rows of 4-byte elements (`elems` + Frame::elem0 +
+// c * Frame::pitch) of format `sample_format`, float32 quantised to `bits` bits; clipped (null: not counted) gets the
+// elements per stream that clamped or were NaN.  One launch.
+hipError_t launch_planar_fill(const uint32_t* elems, const planarenc::Frame* table, uint32_t n_frames, uint32_t channels,
+                              uint32_t sample_format, uint32_t bits, uint32_t row0, size_t stride, int32_t* rows,
+                              unsigned long long* clipped, int form, hipStream_t stream);
+// planar_pack_kernel: the packed interleaved little-endian PCM of every stream of the table, at Stream::packed_base of
+// `image`; `per` is the most dwords a frame starts.  One launch for all classes.
+hipError_t launch_planar_pack(const uint32_t* elems, const planarenc::Frame* table, uint32_t n_frames,
+                              const planarenc::Stream* streams, const flacenc_hip_pcm_stream_desc* descs, uint32_t per,
+                              uint32_t sample_format, uint8_t* image, hipStream_t stream);
 
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);

@@ -16,6 +16,7 @@
 #include "stream_batch_core.h"
 #include "stream_encode_core.h"
 #include "stream_index.h"
+#include "stream_planar_encode_core.h"
 
 namespace flacenc_hip {
 namespace {
@@ -267,18 +268,50 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
                                           uint64_t pcm_bytes, const void* streams, size_t n_streams, uint32_t block_size,
                                           uint8_t* out, uint64_t out_bytes, uint32_t* frame_lengths, size_t max_frames,
                                           uint64_t* totals, uint64_t call_totals[2], int memory_kind) {
+  return encode_streams_common(h, cfg, pcm, pcm_bytes, nullptr, streams, n_streams, block_size, out, out_bytes,
+                               frame_lengths, max_frames, totals, call_totals, memory_kind);
+}
+
+// Both entry points.  `planar` null: the packed PCM of flacenc_hip_encode_streams.  Else pcm is null and the samples are
+// the rows `planar` describes; everything behind the fill -- plan, scratch, runs, scan, cut, place, host staging -- is
+// the same code, and the digests and clip counts ride in the result transfer that is there anyway.
+int flacenc_hip::encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const uint8_t* pcm,
+                                       uint64_t pcm_bytes, const PlanarSource* planar, const void* streams,
+                                       size_t n_streams, uint32_t block_size, uint8_t* out, uint64_t out_bytes,
+                                       uint32_t* frame_lengths, size_t max_frames, uint64_t* totals,
+                                       uint64_t call_totals[2], int memory_kind) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  // [0] launches of this file's kernels, [1] host synchronisations, [2] host-device transfers, [3] classes,
-  // [4] full-frame runs, [5] tail runs, [6] frame-level calls (= [4] + [5]), [7] 0
+  // [0] launches of this file's kernels (and, planar, of encode_streams_planar.cpp's and the digests'), [1] host
+  // synchronisations, [2] host-device transfers, [3] classes, [4] full-frame runs, [5] tail runs, [6] frame-level calls
+  // (= [4] + [5]), [7] the launches among [0] that the digests cost (0 for flacenc_hip_encode_streams)
   uint64_t* plan = h->last_encode_streams_plan;
   for (int i = 0; i < 8; ++i) plan[i] = 0;
-  if ((memory_kind != FLACENC_HIP_MEM_HOST && memory_kind != FLACENC_HIP_MEM_DEVICE) || !cfg || !pcm || !streams || !out ||
+  const void* input = planar ? planar->samples : pcm;
+  if ((memory_kind != FLACENC_HIP_MEM_HOST && memory_kind != FLACENC_HIP_MEM_DEVICE) || !cfg || !input || !streams || !out ||
       !frame_lengths || !totals || !call_totals || n_streams > streamenc::MAX_STREAMS) {
-    h->last_error = "encode_streams: null pointer, unknown memory kind or more than 2^24 streams";
+    h->last_error = planar ? "encode_streams_planar: null pointer, unknown memory kind or more than 2^24 streams"
+                           : "encode_streams: null pointer, unknown memory kind or more than 2^24 streams";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   const Desc* table = static_cast<const Desc*>(streams);
-  int rc = streamenc::check_streams(table, n_streams, pcm_bytes, out_bytes, block_size);
+  if (planar) {
+    // the rows against `samples`; a device pointer must be aligned as its elements are
+    if (planarenc::check_rows(table, n_streams, planar->sample_format, planar->row_pitch, planar->samples_bytes) !=
+            FLACENC_HIP_OK ||
+        (memory_kind == FLACENC_HIP_MEM_DEVICE && (reinterpret_cast<uintptr_t>(planar->samples) & 3u))) {
+      h->last_error = "encode_streams_planar: unknown sample_format, an offset that is no multiple of 4, a row_pitch below "
+                      "a stream's total_samples, rows past samples_bytes, or device samples not 4-byte aligned";
+      return FLACENC_HIP_ERR_BAD_ARGUMENT;
+    }
+  }
+  int rc = streamenc::check_streams(table, planar ? 0 : n_streams, pcm_bytes, out_bytes, block_size);
+  for (size_t s = 0; planar && rc == FLACENC_HIP_OK && s < n_streams; ++s) {
+    // the packed PCM exists nowhere: every other rule holds, the span is held against a buffer without end
+    Desc x = table[s];
+    x.offset = 0;
+    if (x.total_samples >= (streamenc::MAX_FRAMES << 15)) rc = FLACENC_HIP_ERR_BAD_ARGUMENT;  // 2^31 frames at any block size
+    if (rc == FLACENC_HIP_OK) rc = streamenc::check_streams(&x, 1, UINT64_MAX, out_bytes, block_size);
+  }
   const uint64_t F64 = rc == FLACENC_HIP_OK ? streamenc::count_frames(table, n_streams, block_size) : 0;
   if (rc != FLACENC_HIP_OK || F64 >= streamenc::MAX_FRAMES || F64 > max_frames) {
     h->last_error = "encode_streams: block_size not in 64..=32767, channels not in 1..=8, bytes_per_sample not in 1..=4, "
@@ -322,9 +355,15 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   // ---- pinned staging of the tables; the results come down into the other slot ----
   const size_t o_tdesc = 0, o_tfirst = a256(o_tdesc + n_streams * sizeof(Desc));
   const size_t o_tlaunch = a256(o_tfirst + (n_streams + 1) * 4), o_tstream = a256(o_tlaunch + static_cast<size_t>(F) * sizeof(LaunchFrame));
-  const size_t table_bytes = a256(o_tstream + static_cast<size_t>(F) * sizeof(StreamFrame));
-  // results, one transfer: meta | totals | where | frame lengths (host memory; device memory: meta alone)
-  const size_t result_words = M_WORDS + 4 * n_streams + (n_streams + 1);
+  // planar: its frames in launch order in place of the LaunchFrames, its streams, the lengths of their packed PCM
+  const size_t o_tpframe = a256(o_tstream + static_cast<size_t>(F) * sizeof(StreamFrame));
+  const size_t o_tpstream = a256(o_tpframe + (planar ? static_cast<size_t>(F) * sizeof(planarenc::Frame) : 0));
+  const size_t o_tplen = a256(o_tpstream + (planar ? n_streams * sizeof(planarenc::Stream) : 0));
+  const size_t table_bytes = a256(o_tplen + (planar ? n_streams * 8 : 0));
+  // results, one transfer: meta | totals | where | (planar: digests | clip counts) | frame lengths (host memory; device
+  // memory: meta alone)
+  const size_t w_digests = M_WORDS + 4 * n_streams + (n_streams + 1), w_clipped = w_digests + (planar ? 2 * n_streams : 0);
+  const size_t result_words = w_clipped + (planar ? n_streams : 0);
   const size_t result_bytes = result_words * 8 + static_cast<size_t>(F) * 4;
   if ((rc = ensure_pinned(h, h->pin_meta, &h->pin_meta_cap, table_bytes > result_bytes ? table_bytes : result_bytes)) !=
       FLACENC_HIP_OK)
@@ -333,8 +372,33 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   std::memcpy(p_table + o_tdesc, table, n_streams * sizeof(Desc));
   std::memcpy(p_table + o_tfirst, pl.stream_first.data(), (n_streams + 1) * 4);
   if (F) {
-    std::memcpy(p_table + o_tlaunch, pl.launch.data(), static_cast<size_t>(F) * sizeof(LaunchFrame));
+    if (!planar) std::memcpy(p_table + o_tlaunch, pl.launch.data(), static_cast<size_t>(F) * sizeof(LaunchFrame));
     std::memcpy(p_table + o_tstream, pl.stream.data(), static_cast<size_t>(F) * sizeof(StreamFrame));
+  }
+  // planar: elements are counted from the first byte that holds one (host memory: only those bytes go up)
+  const bool want_digests = planar && planar->digests, want_clipped = planar && planar->clipped;
+  planarenc::Extent ext = {0, 0};
+  uint64_t image_bytes = 0;
+  uint32_t pack_per = 0;  // the most dwords of packed PCM a frame of the table starts
+  if (planar) {
+    if (host) ext = planarenc::extent(table, n_streams, planar->row_pitch);
+    planarenc::Stream* ps = reinterpret_cast<planarenc::Stream*>(p_table + o_tpstream);
+    uint64_t* plen = reinterpret_cast<uint64_t*>(p_table + o_tplen);
+    for (size_t s = 0; s < n_streams; ++s) {
+      const Desc& d = table[s];
+      plen[s] = planarenc::packed_bytes(d.total_samples, d.channels, d.bytes_per_sample);
+      ps[s] = {d.total_samples ? (d.offset - ext.first) / 4 : 0, planarenc::pitch_of(planar->row_pitch, d.total_samples),
+               image_bytes, d.total_samples};
+      if (want_digests) image_bytes += planarenc::packed_room(plen[s]);
+      const uint32_t per = static_cast<uint32_t>((static_cast<uint64_t>(block_size) * d.channels * d.bytes_per_sample + 3) / 4);
+      if (per > pack_per) pack_per = per;
+    }
+    planarenc::Frame* pf = reinterpret_cast<planarenc::Frame*>(p_table + o_tpframe);
+    for (uint32_t p = 0; p < F; ++p) {
+      const StreamFrame& q = pl.stream[pl.launch[p].stream_pos];
+      const uint64_t t = static_cast<uint64_t>(q.index) * block_size;
+      pf[p] = {ps[q.stream].elem0 + t, ps[q.stream].pitch, pl.launch[p].valid, q.stream, t};
+    }
   }
 
   // ---- device scratch: everything is sized before anything is enqueued (ensure does not keep contents) ----
@@ -361,7 +425,9 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   if ((rc = ensure(h, h->d_samples, static_cast<size_t>(pl.max_class_rows) * stride * 4 + 16)) != FLACENC_HIP_OK) return rc;
   if ((rc = ensure(h, h->d_results, max_record)) != FLACENC_HIP_OK) return rc;
   if ((rc = ensure(h, h->d_pack[0], static_cast<size_t>(pl.pack_bytes) + 16)) != FLACENC_HIP_OK) return rc;
-  const uint8_t* d_pcm = pcm;
+  const uint8_t* d_pcm = planar ? static_cast<const uint8_t*>(planar->samples) : pcm;
+  if (planar) pcm_bytes = ext.end - ext.first;  // what a host call sends up
+  if (want_digests && (rc = ensure(h, h->d_pcm[1], static_cast<size_t>(image_bytes) + 16)) != FLACENC_HIP_OK) return rc;
   if (host) {
     if ((rc = ensure(h, h->d_pcm[0], static_cast<size_t>(pcm_bytes) + 16)) != FLACENC_HIP_OK) return rc;
     d_pcm = static_cast<const uint8_t*>(h->d_pcm[0].ptr);
@@ -372,6 +438,13 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   uint64_t* d_totals = host ? meta + M_WORDS : totals;
   uint64_t* where = host ? meta + M_WORDS + 4 * n_streams : nullptr;
   uint32_t* d_flen = host ? reinterpret_cast<uint32_t*>(meta + result_words) : frame_lengths;
+  uint8_t* d_digests = !want_digests ? nullptr : host ? reinterpret_cast<uint8_t*>(meta + w_digests) : planar->digests;
+  unsigned long long* d_clipped =
+      reinterpret_cast<unsigned long long*>(!want_clipped ? nullptr : host ? meta + w_clipped : planar->clipped);
+  const uint32_t* elems = reinterpret_cast<const uint32_t*>(d_pcm);
+  const planarenc::Frame* t_pframe = reinterpret_cast<const planarenc::Frame*>(S + o_table + o_tpframe);
+  const planarenc::Stream* t_pstream = reinterpret_cast<const planarenc::Stream*>(S + o_table + o_tpstream);
+  const uint64_t* t_plen = reinterpret_cast<const uint64_t*>(S + o_table + o_tplen);
   const Desc* descs = reinterpret_cast<const Desc*>(S + o_table + o_tdesc);
   const uint32_t* first = reinterpret_cast<const uint32_t*>(S + o_table + o_tfirst);
   const LaunchFrame* t_launch = reinterpret_cast<const LaunchFrame*>(S + o_table + o_tlaunch);
@@ -391,7 +464,9 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   HIP_TRY(h, hipMemsetAsync(zeros, 0, (static_cast<size_t>(F) + 1) * 8, st));
   HIP_TRY(h, hipMemcpyAsync(S + o_table, p_table, table_bytes, hipMemcpyHostToDevice, st));
   ++plan[2];
+  if (d_clipped) HIP_TRY(h, hipMemsetAsync(d_clipped, 0, n_streams * 8, st));
   if (host && pcm_bytes) {
+    if (planar) pcm = static_cast<const uint8_t*>(planar->samples) + ext.first;
     const void* src = pcm;
     if (!is_pinned(pcm)) {  // pageable: through pinned staging on the handle's host threads
       if ((rc = ensure_pinned(h, h->pin_in, &h->pin_in_cap, static_cast<size_t>(pcm_bytes))) != FLACENC_HIP_OK) return rc;
@@ -407,12 +482,20 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
   for (size_t c = 0; c < pl.classes.size(); ++c) {
     const streamenc::Class& k = pl.classes[c];
     if (k.full) {
-      HIP_TRY(h, launch_streams_fill(d_pcm, t_launch + k.first, k.full, k.channels, k.bytes_per_sample, 0, stride, rows, st));
+      if (planar)
+        HIP_TRY(h, launch_planar_fill(elems, t_pframe + k.first, k.full, k.channels, planar->sample_format, k.bits_per_sample,
+                                      0, stride, rows, d_clipped, h->planar_fill_form, st));
+      else
+        HIP_TRY(h, launch_streams_fill(d_pcm, t_launch + k.first, k.full, k.channels, k.bytes_per_sample, 0, stride, rows, st));
       ++plan[0];
     }
     if (k.tails) {
-      HIP_TRY(h, launch_streams_fill(d_pcm, t_launch + k.first + k.full, k.tails, k.channels, k.bytes_per_sample, k.full,
-                                     stride, rows, st));
+      if (planar)
+        HIP_TRY(h, launch_planar_fill(elems, t_pframe + k.first + k.full, k.tails, k.channels, planar->sample_format,
+                                      k.bits_per_sample, k.full, stride, rows, d_clipped, h->planar_fill_form, st));
+      else
+        HIP_TRY(h, launch_streams_fill(d_pcm, t_launch + k.first + k.full, k.tails, k.channels, k.bytes_per_sample, k.full,
+                                       stride, rows, st));
       ++plan[0];
     }
     for (; next_run < pl.runs.size() && pl.runs[next_run].cls == c; ++next_run) {
@@ -430,6 +513,20 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
       }
       if (rc != FLACENC_HIP_OK) return rc;
     }
+  }
+
+  // ---- planar: the packed PCM of every stream, written once for the digests, and the digests ----
+  if (want_digests) {
+    uint8_t* image = static_cast<uint8_t*>(h->d_pcm[1].ptr);
+    if (F) {
+      HIP_TRY(h, launch_planar_pack(elems, t_pframe, F, t_pstream, descs, pack_per, planar->sample_format, image, st));
+      ++plan[0];
+      ++plan[7];
+    }
+    HIP_TRY(h, launch_md5_spans(image, &t_pstream->packed_base, static_cast<uint32_t>(sizeof(planarenc::Stream) / 8), t_plen,
+                                nullptr, ns, d_digests, st));
+    ++plan[0];
+    ++plan[7];
   }
 
   // ---- lengths, offsets in stream order, the cut ----
@@ -488,6 +585,8 @@ extern "C" int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_h
       if (n) h->copy_pool->copy(out + table[s].out_offset, staged + r_where[s], static_cast<size_t>(n));
     }
     std::memcpy(totals, r_totals, n_streams * 32);
+    if (want_digests) std::memcpy(planar->digests, r_meta + w_digests, n_streams * 16);
+    if (want_clipped) std::memcpy(planar->clipped, r_meta + w_clipped, n_streams * 8);
     if (F) std::memcpy(frame_lengths, r_meta + result_words, static_cast<size_t>(F) * 4);
   }
   call_totals[0] = r_meta[M_FRAMES];

@@ -99,8 +99,14 @@ int flacenc_hip_debug_set_encode_streams_chunk(flacenc_hip_handle* h, size_t fra
  * its table, plan[4] full-frame runs, plan[5] tail runs, plan[6] frame-level calls (= plan[4] + plan[5]; each enqueues
  * what flacenc_hip_encode_pack_stereo_frames_async resp. flacenc_hip_encode_pack_frames_async enqueues for its shape),
  * plan[7] 0.  plan[1] and plan[2] do not depend on the number of streams; plan[0] depends on the classes only.  Zeros
- * after a call that was rejected or had no stream. */
+ * after a call that was rejected or had no stream.  flacenc_hip_encode_streams_planar reports here too: the same words
+ * for the same table, but that plan[0] also counts the launches its digests cost and plan[7] is their number (2: the
+ * packed image and the hash; 1 where the table holds no frame; 0 with digests == NULL). */
 int flacenc_hip_debug_last_encode_streams_plan(flacenc_hip_handle* h, uint64_t plan[8]);
+/* Measurement hook (no reference counterpart): how the fill kernel of flacenc_hip_encode_streams_planar loads its
+ * elements in the calls that follow: 1 (a fresh handle; what the product library always does) aligned 16-byte loads
+ * brought into place, 0 four dword loads per channel.  The bytes a call returns do not depend on it. */
+int flacenc_hip_debug_set_planar_fill_form(flacenc_hip_handle* h, int form);
 /* Test and profiling hook (no reference counterpart): the fill kernel of flacenc_hip_encode_streams on its own, with the
  * arguments and the result of flacenc_hip_fill_le_bytes on device pointers -- `bytes` (any byte alignment) holds
  * total_samples inter-channel samples of one stream, frame f gets samples [f*block_size, (f+1)*block_size) and zeros

@@ -1233,6 +1233,51 @@ int flacenc_hip_encode_streams(flacenc_hip_handle* h, const flacenc_hip_frame_co
                                uint8_t* out, uint64_t out_bytes, uint32_t* frame_lengths, size_t max_frames,
                                uint64_t* totals, uint64_t call_totals[2], int memory_kind);
 
+/*
+ * The same call on a tensor: planar rows of 4-byte elements in place of packed PCM -- a [B, C, T] int32 or float32
+ * tensor as it lies, the slots flacenc_hip_decode_ranges_planar writes -- with the digests of the PCM the frames stand
+ * for.  No scale, round, clamp, convert or interleave pass runs in front of the encoder and no packed image of the
+ * samples exists anywhere (but where digests are asked for: one, in handle scratch, written once and hashed once).
+ * `streams`, out, out_bytes, frame_lengths, max_frames, totals, call_totals, memory_kind and
+ * flacenc_hip_encode_streams_frames are flacenc_hip_encode_streams's; one table serves both calls.
+ *   samples, samples_bytes, row_pitch
+ *                    stream s is `channels` rows: row c starts at byte offset + c * pitch * 4 of `samples` (offset a
+ *                    multiple of 4; device memory: `samples` 4-byte aligned), its elements [0, total_samples) are its
+ *                    samples.  pitch is row_pitch where that is non-zero (it must then be at least every stream's
+ *                    total_samples) and the stream's own total_samples where it is 0 (tight rows).  A [B, C, T] tensor
+ *                    with a length per item: row_pitch = T, offset = b*C*T*4, total_samples = length[b].  Streams may
+ *                    share, overlap or repeat rows.  No element outside the valid elements of a stream's rows has any
+ *                    influence on any output; on the device none is read (host memory: the bytes between the first and
+ *                    the last valid element go to the device in one transfer)
+ *   sample_format    FLACENC_HIP_SAMPLE_I32: the element is the sample.  FLACENC_HIP_SAMPLE_F32: the sample is
+ *                    q(x) = clamp(rne(x * 2^(bits_per_sample-1)), -2^(bits_per_sample-1), 2^(bits_per_sample-1) - 1),
+ *                    the product formed in float32 (exact short of overflow), rne round-to-nearest-even, +-inf clamped,
+ *                    every NaN 0: the inverse of the decoder's FLACENC_HIP_SAMPLE_F32 rule, q((float)v * 2^-(bits-1)) == v
+ *                    for every v of the depth
+ *   bytes_per_sample (of the descriptor) is checked as in flacenc_hip_encode_streams and plays no part in reading
+ *                    `samples`: it is the sample width of the packed PCM P_s the rules below are stated over
+ *   digests          NULL, or [n_streams][16] where totals lives: the MD5 of all of P_s, whether or not the slot had
+ *                    room for every frame -- the STREAMINFO digest when bytes_per_sample == ceil(bits_per_sample/8); a
+ *                    stream of 0 samples gets the digest of the empty string
+ *   clipped          NULL, or [n_streams] where totals lives: F32: the elements, over all channels, where q clamped or
+ *                    met a NaN; I32: 0
+ * Equivalence: let P_s be the packed interleaved little-endian PCM, bytes_per_sample bytes a sample, of stream s's
+ * samples.  out, frame_lengths, totals, call_totals, the FLACENC_HIP_ENCODE_NO_ROOM rule, what stays untouched and every
+ * error return are byte for byte what flacenc_hip_encode_streams gives on a buffer holding the P_s with the same table,
+ * cfg, flags, block_size and slots.  I32 elements that do not fit bits_per_sample: as flacenc_hip_encode_streams on those
+ * int32 values stored at bytes_per_sample = 4 (P_s, and so the digest, keeps their low bytes_per_sample bytes).
+ * FLACENC_HIP_ERR_BAD_ARGUMENT, with nothing written, also for: an offset that is no multiple of 4, an unknown
+ * sample_format, a non-zero row_pitch below some stream's total_samples, rows that reach past samples_bytes.
+ * Cost: the synchronisations, transfers and launches of flacenc_hip_encode_streams for the same table (this call's fill
+ * in place of that call's), plus two launches where digests are asked for (one where the table holds no frame); digests
+ * and clip counts come down in the result transfer that is there anyway.
+ */
+int flacenc_hip_encode_streams_planar(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const void* samples,
+                                      uint64_t samples_bytes, uint32_t sample_format, uint64_t row_pitch,
+                                      const void* streams, size_t n_streams, uint32_t block_size, uint8_t* out,
+                                      uint64_t out_bytes, uint32_t* frame_lengths, size_t max_frames, uint64_t* totals,
+                                      uint64_t call_totals[2], uint8_t* digests, uint64_t* clipped, int memory_kind);
+
 /* ---- block-size search: variable-blocking streams ------------------------------------------------------------ */
 /*
  * Each region coded at the block size that compresses it best (BASELINE config 5's "beat-search block sizing"; the

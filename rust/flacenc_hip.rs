@@ -454,6 +454,18 @@ extern "C" {
         n_streams: usize, block_size: u32, out: *mut u8, out_bytes: u64, frame_lengths: *mut u32, max_frames: usize,
         totals: *mut u64, call_totals: *mut u64, memory_kind: c_int,
     ) -> c_int;
+    /// `flacenc_hip_encode_streams` on a tensor: stream `s` is `channels` rows of 4-byte elements, row `c` at byte
+    /// `offset + c * pitch * 4` of `samples` (`pitch` = `row_pitch`, or the stream's `total_samples` where that is 0);
+    /// `sample_format` is `SAMPLE_I32` (the element is the sample) or `SAMPLE_F32` (the sample is the element times
+    /// `2^(bits_per_sample - 1)`, rounded to nearest even and clamped; NaN is 0).  `digests` (null, or `[n_streams][16]`)
+    /// gets the MD5 of every stream's packed PCM at the descriptor's `bytes_per_sample`, `clipped` (null, or
+    /// `[n_streams]`) the elements that clamped or were NaN.  Everything else as `flacenc_hip_encode_streams`.
+    pub fn flacenc_hip_encode_streams_planar(
+        h: *mut Handle, cfg: *const FrameConfig, samples: *const c_void, samples_bytes: u64, sample_format: u32,
+        row_pitch: u64, streams: *const c_void, n_streams: usize, block_size: u32, out: *mut u8, out_bytes: u64,
+        frame_lengths: *mut u32, max_frames: usize, totals: *mut u64, call_totals: *mut u64, digests: *mut u8,
+        clipped: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     /// Block-size search (extension: BASELINE config 5's beat-search block sizing): each superblock of `block_size`
     /// samples coded as the dyadic tiling into blocks down to `block_size >> (levels - 1)` that is shortest, written as
     /// variable-blocking frames; `totals[0]` carries `VARIABLE_OVERFLOW` when `out` / `max_frames` had too little room.

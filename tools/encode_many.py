@@ -8,6 +8,13 @@ recentred), lays their samples back to back in one buffer, encodes all of them w
 their STREAMINFO digests from flacenc_hip_md5_spans over the same spans.  Each .flac is "fLaC" + the 42-byte STREAMINFO
 tools/encode_flac.py writes + the stream's frames; tools/decode_flac.py reads it back and checks the MD5.  Files may
 differ in channels, width and rate: streams of one (channels, bits, bytes, rate) share their launches.
+
+    python tools/encode_many.py --npy FILE [--lengths FILE] --bits N --rate R --out-dir DIR [the options above]
+
+A [B, C, T] float32 (samples in [-1, 1)) or int32 array from a .npy file, item b valid up to lengths[b] samples (a .npy
+of B integers; default T), to DIR/item00000.flac ...: ONE flacenc_hip_encode_streams_planar call
+(flacenc_rs_amd.crops.encode_crops) reads the array as it lies and gives the frames and the STREAMINFO digests; no
+packed copy of the samples is made on the way.  Prints how many elements clipped.
 """
 import argparse
 import os
@@ -63,9 +70,33 @@ def encode_many(handle, wavs, block_size=4096, lpc_order=8, flags=0):
     return files, call
 
 
+def encode_array(handle, x, lengths, bits, rate, block_size=4096, lpc_order=8, flags=0):
+    """x: [B, C, T] float32 / int32 numpy array -> (one .flac byte string per item, clip counts [B])."""
+    import torch
+    from flacenc_rs_amd import crops
+
+    cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=True)
+    B, C, T = x.shape
+    n = np.full(B, T, np.int64) if lengths is None else np.asarray(lengths, np.int64).reshape(-1)
+    r = crops.encode_crops(handle, torch.from_numpy(np.ascontiguousarray(x)), n, bits, rate, cfg, block_size)
+    frames, items, sizes = r["frames"].numpy(), r["items"].numpy(), r["frame_lengths"].numpy()
+    first = np.concatenate([[0], np.cumsum(items[:, 2])])
+    files = []
+    for b in range(B):
+        mine = sizes[first[b]:first[b + 1]]
+        head = stream_info_block(block_size, int(mine.min()) if len(mine) else 0, int(mine.max()) if len(mine) else 0, rate,
+                                 C, bits, int(n[b]), r["digests"][b].numpy().tobytes())
+        files.append(b"fLaC" + head + frames[int(items[b, 0]):int(items[b, 0]) + int(items[b, 1])].tobytes())
+    return files, r["clipped"].numpy()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("wavs", nargs="+")
+    ap.add_argument("wavs", nargs="*")
+    ap.add_argument("--npy", help="a [B, C, T] float32 or int32 array in place of WAV files")
+    ap.add_argument("--lengths", help="with --npy: a .npy of B valid lengths")
+    ap.add_argument("--bits", type=int, help="with --npy: bits per sample, 8..24")
+    ap.add_argument("--rate", type=int, help="with --npy: the sample rate")
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--block-size", type=int, default=4096)
     ap.add_argument("--lpc-order", type=int, default=8)
@@ -75,8 +106,26 @@ def main():
     args = ap.parse_args()
     flags = (_capi.FLAG_WASTED_BITS if args.wasted_bits else 0) | (_capi.FLAG_RICE_ESCAPE if args.rice_escape else 0)
     flags |= _capi.FLAG_ORDER_GUESS if args.order_guess else 0
-    wavs = [read_wav(p) for p in args.wavs]
     os.makedirs(args.out_dir, exist_ok=True)
+    if args.npy:
+        if args.wavs or args.bits is None or args.rate is None:
+            raise SystemExit("--npy takes --bits and --rate and no WAV file")
+        x = np.load(args.npy)
+        if x.ndim != 3 or x.dtype not in (np.float32, np.int32):
+            raise SystemExit(f"{args.npy}: a [B, C, T] float32 or int32 array is needed, not {x.dtype} {x.shape}")
+        lengths = np.load(args.lengths) if args.lengths else None
+        with _capi.Handle(0) as h:
+            if args.order_guess:
+                h.set_order_guesses(args.order_guess)
+            files, clipped = encode_array(h, x, lengths, args.bits, args.rate, args.block_size, args.lpc_order, flags)
+        for b, data in enumerate(files):
+            with open(os.path.join(args.out_dir, "item%05d.flac" % b), "wb") as f:
+                f.write(data)
+        print(f"{len(files)} files, {sum(len(d) for d in files)} bytes, {int(clipped.sum())} elements clipped, one call")
+        return
+    if not args.wavs:
+        raise SystemExit("WAV files or --npy are needed")
+    wavs = [read_wav(p) for p in args.wavs]
     with _capi.Handle(0) as h:
         if args.order_guess:
             h.set_order_guesses(args.order_guess)
