@@ -159,11 +159,12 @@ def _candidate(kind, w, order, precision, residual, rice_order, rice_params, cod
     return c
 
 
-def subframe(x, w, fc, escape=True):
+def subframe(x, w, fc, escape=True, analyse=None):
     """encode_subframe (coding.rs:384-418) on the oracle's candidates with the flag's bit counts: Constant first, the
     LPC candidate if it beats min(fixed, verbatim), the fixed candidate if its selector key and its count are below
     Verbatim, else Verbatim.  -> dict(kind 0..3, bits, cand: the kept candidate or None, x, w, status: the LPC
-    analysis's)."""
+    analysis's).  `analyse(x, w, qlpc config)`: what states the LPC candidate in place of oracle.estimated_qlpc, with
+    its keys (a search flag's winner, chosen unescaped: the escape pass runs on the winner alone)."""
     x = np.ascontiguousarray(x, np.int32)
     n = len(x)
     verbatim = orc.verbatim_count_bits(n, w)
@@ -171,7 +172,7 @@ def subframe(x, w, fc, escape=True):
     max_p = fc.qlpc.max_rice_parameter
     lpc = fixed = None
     if n >= 64 and fc.use_lpc:
-        r = orc.estimated_qlpc(x, w, fc.qlpc)
+        r = (analyse or orc.estimated_qlpc)(x, w, fc.qlpc)
         out["status"] = int(r["status"])
         if r["status"] == 0:
             lpc = _candidate("lpc", w, int(r["order"]), int(r["precision"]), r["residual"], int(r["rice_order"]),
@@ -198,9 +199,9 @@ def roles(l, r):
     return [l, r, (l + r) >> 1, l - r]
 
 
-def stereo_decision(l, r, bps, fc, escape=True):
+def stereo_decision(l, r, bps, fc, escape=True, analyse=None):
     """-> (assignment, [subframe of L, R, M, S])"""
-    subs = [subframe(x, bps + (1 if i == 3 else 0), fc, escape) for i, x in enumerate(roles(l, r))]
+    subs = [subframe(x, bps + (1 if i == 3 else 0), fc, escape, analyse) for i, x in enumerate(roles(l, r))]
     b = [s["bits"] for s in subs]
     best, assignment = b[0] + b[1], 0
     if fc.use_leftside and b[0] + b[3] < best:
@@ -226,13 +227,13 @@ def write_args(s, wasted=0):
     return kw
 
 
-def stereo_frame_bytes(l, r, bps, fc, number=0, escape=True):
-    a, subs = stereo_decision(l, r, bps, fc, escape)
+def stereo_frame_bytes(l, r, bps, fc, number=0, escape=True, analyse=None):
+    a, subs = stereo_decision(l, r, bps, fc, escape, analyse)
     return fw.frame([l, r], STEREO_TAGS[a], bps, [write_args(subs[i]) for i in STEREO_ROLES[a]], number=number)
 
 
-def channel_frame_bytes(xs, bps, fc, number=0, escape=True):
-    subs = [subframe(x, bps, fc, escape) for x in xs]
+def channel_frame_bytes(xs, bps, fc, number=0, escape=True, analyse=None):
+    subs = [subframe(x, bps, fc, escape, analyse) for x in xs]
     return fw.frame(xs, len(xs) - 1, bps, [write_args(s) for s in subs], number=number)
 
 
