@@ -233,10 +233,7 @@ inline uint32_t next_seq(uint32_t seq) { return ((seq + 1u) & 0xFFFu) ? ((seq + 
 
 int launch_adaptive(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, const flacenc_hip::QlpcLaunchPlan& plan,
                     hipStream_t stream) {
-  const bool order_ok = a.reference_order == 0u || (a.reference_order == 1u && a.integer_parity_only != 0u);
-  const bool fused_certified = a.certify != 0u && flacenc_hip::cert_shape(a) && order_ok && !a.direct_mse && a.fixed_mode == 0 &&
-                               a.lpc_stage == 0 && a.acorr_in == nullptr && !a.only_marked && a.pack_out == nullptr &&
-                               flacenc_hip::wave_kernel_eligible(a);
+  const bool fused_certified = flacenc_hip::plan_qlpc_route(a).order == flacenc_hip::QlpcRoute::kCertifiedFused;
   const bool watch = fused_certified && h->adaptive_order != 0 && h->cert_stats == nullptr && a.autocorr == nullptr &&
                      a.lpc_coefs == nullptr && a.n_subframes < kFeedbackMaxSubframes;
   if (!watch) {

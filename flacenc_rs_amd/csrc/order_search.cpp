@@ -666,11 +666,6 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
   }
   // 5. records and residual rows by the unflagged stage-3 kernels (as behind direct_mse_kernel)
   QlpcKernelArgs s3 = a;
-  s3.lpc_stage = 3;
-  s3.pred = pred;
-  s3.autocorr = nullptr;
-  s3.lpc_coefs = nullptr;
-  s3.acorr_in = nullptr;
   s3.reference_order = 0;
   s3.certify = 0;
   s3.cert_subwave = 0;
@@ -678,15 +673,7 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
   s3.direct_mse = 0;
   s3.sumabs_in = nullptr;
   s3.sumabs_scratch = nullptr;
-  if (bigblock_shape_eligible(a)) {
-    if ((err = launch_bigblock_residual(s3, stream)) != hipSuccess) return err;
-    s3.only_marked = 1;  // residuals of 2^26 and more: redone by the generic kernel
-  }
-#define FLACENC_HIP_OS3(MP, BG) \
-  if (plan.maxp == MP && plan.big == (BG != 0)) return launch_qlpc_##MP##_##BG(s3, plan.threads, plan.smem_bytes, stream);
-  FLACENC_HIP_FOR_EACH_INSTANCE(FLACENC_HIP_OS3)
-#undef FLACENC_HIP_OS3
-  return hipErrorInvalidValue;
+  return launch_stage3(s3, pred, bigblock_shape_eligible(a), plan, stream);
 }
 
 }  // namespace flacenc_hip

@@ -471,23 +471,6 @@ hipError_t launch_acorr(const QlpcKernelArgs& a, hipStream_t stream) {
 
 }  // namespace
 
-// fixed_lpc with OrderSel::ApproxEnt on the same shapes: estimator partitions that are whole groups of lanes
-bool bigblock_fixed_eligible(const QlpcKernelArgs& a) {
-  if (a.fixed_mode != 1u || a.lpc_stage != 0 || a.force_generic) return false;
-  if (a.block_size != 4096 && a.block_size != 8192 && a.block_size != 16384) return false;
-  const uint32_t parts = a.fixed_partitions;
-  if (parts == 0 || (parts & (parts - 1)) != 0) return false;
-  const uint32_t psize = a.block_size / parts;
-  if (psize < 64 || psize > 4096) return false;
-  if (a.fixed_max_order > 4) return false;
-  if (a.frame_results || a.chan_results || a.pack_out) return false;
-  if ((reinterpret_cast<uintptr_t>(a.samples) & 15) || (a.stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.residual) & 15) || (a.residual_stride & 3)) return false;
-  if (a.stereo && (a.n_subframes & 3)) return false;
-  if (a.split_scratch == nullptr) return false;
-  return true;
-}
-
 hipError_t launch_bigblock_fixed_select(const QlpcKernelArgs& a, hipStream_t stream) {
   static DynamicLdsOptIn opt_s, opt_p;
   if (a.stereo) return launch_big(bigblock_fixed_select_kernel<true>, opt_s, a, 2 * kBufDwords * 4, stream);
@@ -496,27 +479,6 @@ hipError_t launch_bigblock_fixed_select(const QlpcKernelArgs& a, hipStream_t str
 
 hipError_t launch_bigblock_fixed_residual(const QlpcKernelArgs& a, hipStream_t stream) {
   return launch_bigblock_residual(a, stream);  // (FIXED_LPC_COEFS with shift 0 is a predictor like any other)
-}
-
-bool bigblock_eligible(const QlpcKernelArgs& a) {
-  // (4096 at orders 13..32 too: below 13 the fused 4096 kernel has it, above it would fall to the generic one;
-  // 8192 / 16384 at every order -- round 2 left orders up to 12 on those blocks to the generic kernel, 88 G
-  // samples/s where order 24 ran at 146)
-  if (a.lpc_order < 1 || a.lpc_order > 32) return false;
-  if (a.lpc_order < 13 && a.block_size == 4096) return false;
-  return bigblock_shape_eligible(a);
-}
-
-bool bigblock_shape_eligible(const QlpcKernelArgs& a) {
-  if (a.block_size != 4096 && a.block_size != 8192 && a.block_size != 16384) return false;
-  if (a.lpc_order < 1 || a.lpc_order > 32) return false;
-  if (a.fixed_mode != 0 || a.lpc_stage != 0 || a.force_generic) return false;
-  if (a.frame_results || a.chan_results || a.pack_out) return false;
-  if ((reinterpret_cast<uintptr_t>(a.samples) & 15) || (a.stride & 3)) return false;
-  if ((reinterpret_cast<uintptr_t>(a.residual) & 15) || (a.residual_stride & 3)) return false;
-  if (a.stereo && (a.n_subframes & 3)) return false;
-  if (a.split_scratch == nullptr) return false;
-  return true;
 }
 
 // R[] (unless `have_r`: already in `racc`, e.g. from the reference-order kernel) into racc

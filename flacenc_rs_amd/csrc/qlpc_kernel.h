@@ -173,7 +173,50 @@ QlpcLaunchPlan plan_qlpc_launch(uint32_t block_size, uint32_t lpc_order);
 bool wave_kernel_eligible(const QlpcKernelArgs& args);
 // blocks of 4096 / 4608 samples at orders up to 12: the shapes whose unflagged order is certified (QlpcKernelArgs::certify)
 bool cert_shape(const QlpcKernelArgs& args);
+// rows every kernel but the generic one can take: 16-byte aligned, strides of whole dwordx4, stereo frames complete
+bool rows_aligned(const QlpcKernelArgs& args);
+// What one launch_qlpc call launches ("The route of a launch"): decided by plan_qlpc_route from the record
+// alone -- no HIP call, nothing allocated -- and run by launch_qlpc as a straight sequence in the order of the fields.
+struct QlpcRoute {
+  // how the summation order of R[] is settled: as the record asks (reference_order, canonical when 0) / certified inside
+  // the fused kernel / the reference's by its chains in front, because `certify` asks and the launch cannot certify /
+  // the same on the shapes whose unflagged order is the stable build's by default
+  enum Order : uint8_t { kAsAsked, kCertifiedFused, kReferencePass, kStableByDefault };
+  // the ApproxEnt selector's sums of |e|: the kernels' exact sums / the fused kernel walks the reference's chains where
+  // they can differ (sumabs_mode) / sumabs_reference_kernel in front (sumabs_in)
+  enum SumAbs : uint8_t { kExactSums, kFusedWalk, kSumAbsChains };
+  enum Family : uint8_t {
+    kNothing,        // no subframes
+    kUnsupported,    // a decision on the device asked of a launch the fused kernel cannot take
+    kFused,          // blocks of 4096 / 4608 samples: instance (bucket, variant)
+    kSubwave,        // blocks of 256 .. 2304 samples: instance (bucket, variant 0 / 1), then the marked clean-up
+    kBigBlock,       // R[] -> levinson_batch_kernel -> stage 3
+    kBigBlockFixed,  // fixed_lpc on the big-block shapes: selection, residual kernel, the marked clean-up
+    kStage3,         // the predictor record is there (direct_mse): stage 3 alone
+    kSplit,          // the generic kernel's three-launch split at orders from 16
+    kGeneric
+  };
+  Order order;
+  bool certify;              // QlpcKernelArgs::certify reaches the kernels (else cleared)
+  uint32_t reference_order;  // QlpcKernelArgs::reference_order as the launches see it
+  // the pre-passes, in launch order
+  SumAbs sumabs;
+  bool direct_mse;      // direct_mse_kernel -> the predictor record
+  bool chains_marked;   // the reference's chains of the records marked -2 -> acorr_marked
+  bool chains_all;      // the reference's chains of every subframe -> acorr_in
+  bool bigblock_acorr;  // kBigBlock without R[] from a pass in front: bigblock_acorr_kernel
+  Family family;
+  int bucket, variant;  // kFused / kSubwave: the instance
+  bool bigblock;        // kBigBlock / kStage3: stage 3 by bigblock_residual_kernel + the marked clean-up, else the generic kernel
+  bool cleanup;         // a clean-up launch of the generic kernel (only_marked) ends the sequence
+};
+QlpcRoute plan_qlpc_route(const QlpcKernelArgs& args);
 hipError_t launch_qlpc(const QlpcKernelArgs& args, const QlpcLaunchPlan& plan, hipStream_t stream);
+// Stage 3 behind a predictor record (`pred`, [n][36]): records and residual rows by bigblock_residual_kernel with the
+// generic kernel's marked clean-up (`bigblock`), else by the generic kernel.  `args`: the launch's record; the stage's
+// own fields are set here.
+hipError_t launch_stage3(QlpcKernelArgs args, const int32_t* pred, bool bigblock, const QlpcLaunchPlan& plan,
+                         hipStream_t stream);
 // blocks of 8192 / 16384 samples at order 13..32 (qlpc_bigblock.cpp): autocorrelation and residual + Rice
 // search as two pass-structured kernels either side of levinson_batch_kernel
 bool bigblock_eligible(const QlpcKernelArgs& args);

@@ -23,7 +23,7 @@ SUBWAVE = (256, 288, 512, 576, 1024, 1152, 2048, 2304)
 def route(block, order):
     """The kernel family a frame-level launch of `block` samples at LPC order `order` takes, by its shape alone (aligned
     rows, no flag that forces the general path): wave_kernel_eligible, subwave_*_eligible and bigblock_eligible of
-    csrc/qlpc_dispatch.cpp and csrc/qlpc_bigblock.cpp.  The fused and the sub-wave kernels stop at order 12."""
+    csrc/qlpc_dispatch.cpp.  The fused and the sub-wave kernels stop at order 12."""
     if block < 64:
         return "generic"
     if block in (8192, 16384) or (block == 4096 and order >= 13):
