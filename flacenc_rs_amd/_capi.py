@@ -71,6 +71,7 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_last_stream_plan", "flacenc_hip_debug_last_stream_buffers",
                  "flacenc_hip_debug_set_decode_plan", "flacenc_hip_debug_last_decode_plan",
                  "flacenc_hip_debug_last_decode_streams_plan", "flacenc_hip_debug_last_decode_ranges_plan",
+                 "flacenc_hip_debug_last_recover_plan",
                  "flacenc_hip_debug_set_encode_streams_chunk",
                  "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill",
                  "flacenc_hip_debug_set_planar_fill_form")
@@ -131,6 +132,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_decode_streams",
     "flacenc_hip_md5_spans",
     "flacenc_hip_decode_streams_md5",
+    "flacenc_hip_recover_streams",
     "flacenc_hip_decode_ranges",
     "flacenc_hip_decode_ranges_planar",
     "flacenc_hip_encode_streams_frames",
@@ -496,6 +498,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_md5_spans.restype = C.c_int
     L.flacenc_hip_decode_streams_md5.argtypes = L.flacenc_hip_decode_streams.argtypes + [vp]
     L.flacenc_hip_decode_streams_md5.restype = C.c_int
+    L.flacenc_hip_recover_streams.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint64, vp, vp,
+                                              C.c_size_t, vp, C.c_int]
+    L.flacenc_hip_recover_streams.restype = C.c_int
     L.flacenc_hip_decode_ranges.argtypes = [vp, vp, C.c_uint64, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, vp,
                                             C.c_uint64, vp, vp, C.c_int]
     L.flacenc_hip_decode_ranges.restype = C.c_int
@@ -775,6 +780,13 @@ class Handle:
         decode_streams call on this handle."""
         plan = np.zeros(4, np.uint64)
         self._check(self._hook("flacenc_hip_debug_last_decode_streams_plan")(self._h, plan.ctypes.data))
+        return tuple(int(x) for x in plan)
+
+    def debug_last_recover_plan(self):
+        """(kernel launches, host synchronisations, host-device transfers, channel counts present) of the last
+        recover_streams call on this handle."""
+        plan = np.zeros(4, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_last_recover_plan")(self._h, plan.ctypes.data))
         return tuple(int(x) for x in plan)
 
     def debug_set_encode_streams_chunk(self, frames: int):
@@ -1247,6 +1259,52 @@ class Handle:
         if check:
             self._check(rc)
         return [int(call[0]), int(call[1])], rc
+
+    def recover_streams(self, data, streams, max_frames: int, out: np.ndarray, origins=None, max_gaps: int = 0,
+                        gaps: np.ndarray | None = None, check: bool = True):
+        """flacenc_hip_recover_streams on host arrays: decode_streams' `data`, `streams` and `out` (written in place),
+        `origins` one sample number per stream (None: all zero), `gaps` a uint64 [max_gaps, 3] array (None: one is made
+        when max_gaps > 0).  -> (out, totals uint64 [n_streams, 8], gaps -- the records written: min(call totals[2],
+        max_gaps) rows of (stream, first sample, samples) --, call totals [frames | INDEX_ERROR, samples, gaps, frames
+        dropped]); with check=False a failure's code is appended instead of raised."""
+        buf = data if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        assert buf.dtype == np.uint8 and buf.flags["C_CONTIGUOUS"]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        table = stream_descs(streams)
+        totals = np.zeros((len(table), 8), np.uint64)
+        org = None if origins is None else np.ascontiguousarray(origins, np.uint64)
+        assert org is None or org.size == len(table)
+        if gaps is None and max_gaps:
+            gaps = np.zeros((max_gaps, 3), np.uint64)
+        assert gaps is None or (gaps.dtype == np.uint64 and gaps.flags["C_CONTIGUOUS"] and gaps.size >= 3 * max_gaps)
+        call = np.zeros(4, np.uint64)
+        rc = self._lib.flacenc_hip_recover_streams(self._h, buf.ctypes.data, buf.size, table.ctypes.data, len(table),
+                                                   None if org is None else org.ctypes.data, max_frames,
+                                                   out.ctypes.data, out.size, totals.ctypes.data,
+                                                   None if gaps is None else gaps.ctypes.data, max_gaps,
+                                                   call.ctypes.data, MEM_HOST)
+        if check:
+            self._check(rc)
+        n = min(int(call[2]), max_gaps) if rc == 0 else 0
+        written = np.zeros((0, 3), np.uint64) if gaps is None else gaps.reshape(-1, 3)[:n]
+        result = (out, totals, written, [int(v) for v in call])
+        return result if check else result + (rc,)
+
+    def recover_streams_device(self, bytes_ptr: int, n_bytes: int, streams, max_frames: int, out_ptr: int,
+                               out_bytes: int, totals_ptr: int, origins=None, gaps_ptr: int = 0, max_gaps: int = 0,
+                               check: bool = True):
+        """flacenc_hip_recover_streams on device pointers (the table and the origins stay host memory); blocks on the
+        handle's stream.  -> (call totals, the call's code)."""
+        table = stream_descs(streams)
+        org = None if origins is None else np.ascontiguousarray(origins, np.uint64)
+        call = np.zeros(4, np.uint64)
+        rc = self._lib.flacenc_hip_recover_streams(self._h, bytes_ptr or None, n_bytes, table.ctypes.data, len(table),
+                                                   None if org is None else org.ctypes.data, max_frames,
+                                                   out_ptr or None, out_bytes, totals_ptr or None, gaps_ptr or None,
+                                                   max_gaps, call.ctypes.data, MEM_DEVICE)
+        if check:
+            self._check(rc)
+        return [int(v) for v in call], rc
 
     def decode_ranges(self, data, streams, ranges, max_frames: int, out: np.ndarray, totals: np.ndarray | None = None,
                       check: bool = True):

@@ -102,6 +102,12 @@ int flacenc_hip_debug_last_decode_ranges_plan(flacenc_hip_handle* h, uint64_t pl
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_debug_last_recover_plan(flacenc_hip_handle* h, uint64_t plan[4]) {
+  if (!h || !plan) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  for (int i = 0; i < 4; ++i) plan[i] = h->last_recover_plan[i];
+  return FLACENC_HIP_OK;
+}
+
 int flacenc_hip_debug_set_encode_streams_chunk(flacenc_hip_handle* h, size_t frames) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   if (frames > 8192) {  // the rule's own upper end

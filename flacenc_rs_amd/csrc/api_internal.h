@@ -16,6 +16,7 @@
 //   api_decode_stream.cpp  rows to packed PCM (flacenc_hip_pack_le_bytes), the streaming way back (flacenc_hip_decode_pcm)
 //   flac_decode_ranges.cpp   sample ranges of a batch of streams (flacenc_hip_decode_ranges) on the index of stream_index.h
 //   flac_decode_streams.cpp  a batch of streams to packed PCM (flacenc_hip_decode_streams, _md5): its kernels and the call
+//   flac_recover_streams.cpp  a batch of damaged streams decoded through their errors (flacenc_hip_recover_streams)
 //   md5_streams.cpp      MD5 digests of a batch of spans (flacenc_hip_md5_spans): its kernel, launcher and the call
 //   encode_streams.cpp   a batch of PCM streams to frames (flacenc_hip_encode_streams): its kernels and the call
 //   api_variable.cpp     the block-size search
@@ -220,6 +221,8 @@ struct flacenc_hip_handle {
   // flacenc_hip_debug_last_decode_ranges_plan) launches, synchronisations, transfers and the ranges' channel classes
   std::vector<char> ranges_table;
   uint64_t last_ranges_plan[4] = {0, 0, 0, 0};
+  // test hook, see flacenc_hip_debug_last_recover_plan: the same four words of the last flacenc_hip_recover_streams call
+  uint64_t last_recover_plan[4] = {0, 0, 0, 0};
   // test hooks, see flacenc_hip_debug_set_encode_streams_chunk / flacenc_hip_debug_last_encode_streams_plan: frames per
   // frame-level call of flacenc_hip_encode_streams in place of its rule (0: the rule), and what the last call did
   size_t encode_streams_chunk_override = 0;

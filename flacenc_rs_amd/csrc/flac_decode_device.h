@@ -1,7 +1,7 @@
 // flac_decode_device.h -- what the decoder's translation units (flac_decode.cpp, stream_index.cpp, flac_decode_streams.cpp,
-// flac_decode_ranges.cpp) share on the device, each written once: the index's constants, workgroup scan, bisection and
+// flac_decode_ranges.cpp, flac_recover_streams.cpp) share on the device, each written once: the index's constants, workgroup scan, bisection and
 // chain walks, and a lane's subframe reconstruction -- its setup, the order-bucket ladder, the sample step, the
-// packed-PCM writer and the planar writer.  Included by those four files only.
+// packed-PCM writer and the planar writer.  Included by those five files only.
 #ifndef FLAC_DECODE_DEVICE_H_
 #define FLAC_DECODE_DEVICE_H_
 

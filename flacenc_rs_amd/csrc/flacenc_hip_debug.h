@@ -87,6 +87,10 @@ int flacenc_hip_debug_last_decode_streams_plan(flacenc_hip_handle* h, uint64_t p
  * three depends on the number of streams or of ranges; every further channel count adds one launch.  Zeros after a call
  * that was rejected or had no range. */
 int flacenc_hip_debug_last_decode_ranges_plan(flacenc_hip_handle* h, uint64_t plan[4]);
+/* What the last flacenc_hip_recover_streams call on the handle did: plan[0] kernel launches, plan[1] host
+ * synchronisations, plan[2] host-device transfers, plan[3] channel counts present in its table.  None of the first three
+ * depends on the number of streams or on the damage they hold.  Zeros after a call that was rejected or had no stream. */
+int flacenc_hip_debug_last_recover_plan(flacenc_hip_handle* h, uint64_t plan[4]);
 
 /* Test hook (no reference counterpart): the plan of flacenc_hip_encode_streams.  `frames` != 0: the calls that follow cut
  * every run of a class -- its full blocks, and the last blocks of one length -- into frame-level calls of at most `frames`

@@ -155,32 +155,40 @@ __global__ void __launch_bounds__(1024) streams_scan_kernel(const uint64_t* __re
 }
 
 // ---------------------------------------------------------------- skim and link, per candidate with its span
-// candidate i may run to its stream's end; its parsed length is recorded
+// candidate i may run to its stream's end; its parsed length is recorded.  NUMBERS: its coded number and blocking bit
+// (bit 0 of the header's second byte) too, numbers[i] = number << 1 | bit
+template <bool NUMBERS>
 __global__ void __launch_bounds__(256) streams_skim_kernel(const uint8_t* __restrict__ bytes, TableSpans spans,
                                                            const uint64_t* __restrict__ cand_pos,
                                                            const uint32_t* __restrict__ counters, uint32_t capacity,
-                                                           FrameRec* __restrict__ recs) {
+                                                           FrameRec* __restrict__ recs, uint64_t* __restrict__ numbers) {
   const uint32_t n = min(counters[C_CANDS], capacity);
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Span x = spans.of_candidate(i);
   const uint64_t off = cand_pos[i], left = x.end - off;  // a candidate lies inside its span
   FrameRec rec;
+  uint64_t number = 0;
   flacdec::skim_frame(bytes + off, left > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(left), x.channels, x.bps,
-                      65536u, false, kCrc, rec, nullptr);
+                      65536u, false, kCrc, rec, NUMBERS ? &number : nullptr);
   recs[i] = rec;
+  if (NUMBERS) numbers[i] = number << 1 | (bytes[off + 1] & 1u);
 }
 
 // The skim of a table takes each candidate's parameters from its stream.  The single stream keeps skim_kernel's index
 // mode (flac_decode.cpp), whose parameters are the launch's: that kernel is measurably faster there (about 1.5 % of a
 // skim that is 70 % of flacenc_hip_index_frames) than this one compiled for one span.
 void launch_skim(const uint8_t* bytes, uint64_t, const TableSpans& spans, const uint64_t* cand_pos,
-                 const uint32_t* counters, uint32_t cap, FrameRec* recs, hipStream_t st) {
-  hipLaunchKernelGGL(streams_skim_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, bytes, spans, cand_pos, counters,
-                     cap, recs);
+                 const uint32_t* counters, uint32_t cap, FrameRec* recs, uint64_t* numbers, hipStream_t st) {
+  if (numbers)
+    hipLaunchKernelGGL(streams_skim_kernel<true>, dim3(ceil_div(cap, 256)), dim3(256), 0, st, bytes, spans, cand_pos,
+                       counters, cap, recs, numbers);
+  else
+    hipLaunchKernelGGL(streams_skim_kernel<false>, dim3(ceil_div(cap, 256)), dim3(256), 0, st, bytes, spans, cand_pos,
+                       counters, cap, recs, numbers);
 }
 void launch_skim(const uint8_t* bytes, uint64_t n_bytes, const OneSpan& spans, const uint64_t* cand_pos,
-                 const uint32_t* counters, uint32_t cap, FrameRec* recs, hipStream_t st) {
+                 const uint32_t* counters, uint32_t cap, FrameRec* recs, uint64_t*, hipStream_t st) {
   (void)launch_frame_skim(bytes, n_bytes, cand_pos, cap, counters + C_CANDS, spans.channels, spans.bps, recs, st);
 }
 
@@ -203,6 +211,56 @@ __global__ void __launch_bounds__(256) streams_link_kernel(Spans spans, const ui
   jump[i] = nx;
 }
 
+// The resynchronising forms (Request::resync).  The verified candidates are ranked first: v_flag[i] = 1 for a verified
+// candidate, v_rank its exclusive scan (streams_scan_kernel), v_list[v_rank[i]] = i -- so the first verified candidate at
+// or behind candidate j is v_list[v_rank[j]], whatever lies unverified between them.
+__global__ void __launch_bounds__(256) resync_flag_kernel(const FrameRec* __restrict__ recs,
+                                                          const uint32_t* __restrict__ counters, uint32_t capacity,
+                                                          uint64_t* __restrict__ v_flag) {
+  const uint32_t n = min(counters[C_CANDS], capacity);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) v_flag[i] = recs[i].status == 0 ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256) resync_list_kernel(const FrameRec* __restrict__ recs,
+                                                          const uint64_t* __restrict__ v_rank,
+                                                          const uint32_t* __restrict__ counters, uint32_t capacity,
+                                                          uint32_t* __restrict__ v_list) {
+  const uint32_t n = min(counters[C_CANDS], capacity);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && recs[i].status == 0) v_list[v_rank[i]] = i;
+}
+
+// the first verified candidate of [lo, n) at or behind byte x and in front of byte `end`; kDead if there is none
+__device__ inline uint32_t resync_at(const uint64_t* cand_pos, const uint64_t* v_rank, const uint32_t* v_list,
+                                     uint32_t lo, uint32_t n, uint64_t x, uint64_t end) {
+  const uint32_t j = lower_bound(cand_pos, lo, n, x);
+  const uint64_t r = v_rank[j];  // v_rank has n + 1 words
+  if (r >= v_rank[n]) return kDead;
+  const uint32_t k = v_list[r];
+  return cand_pos[k] < end ? k : kDead;
+}
+
+// jump[0][i] of the resynchronising chain: the first verified candidate at or behind the end of verified candidate i
+// inside its span, kEnd when the span holds none; kDead for an unverified candidate.  The candidate found starts at or
+// behind a byte of the span and in front of the span's end, so it belongs to the same span.
+__global__ void __launch_bounds__(256) streams_resync_link_kernel(TableSpans spans, const uint64_t* __restrict__ cand_pos,
+                                                                  const FrameRec* __restrict__ recs,
+                                                                  const uint64_t* __restrict__ v_rank,
+                                                                  const uint32_t* __restrict__ v_list,
+                                                                  const uint32_t* __restrict__ counters,
+                                                                  uint32_t capacity, uint32_t* __restrict__ jump) {
+  const uint32_t n = min(counters[C_CANDS], capacity);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t nx = kDead;
+  if (recs[i].status == 0) {
+    nx = resync_at(cand_pos, v_rank, v_list, i + 1, n, cand_pos[i] + recs[i].len, spans.of_candidate(i).end);
+    if (nx == kDead) nx = kEnd;
+  }
+  jump[i] = nx;
+}
+
 __global__ void __launch_bounds__(256) jump_kernel(const uint32_t* __restrict__ prev, uint32_t* __restrict__ next,
                                                    const uint32_t* __restrict__ n_dev, uint32_t capacity) {
   const uint32_t n = min(*n_dev, capacity);
@@ -218,12 +276,25 @@ uint32_t jump_levels(size_t capacity) {
   return l;
 }
 
+// what the resynchronising index adds to the pipeline: the candidates' numbers and the ranking of the verified ones
+struct Resync {
+  uint64_t *numbers, *v_flag, *v_rank;  // [capacity], [capacity], [capacity + 1]
+  uint32_t* v_list;                     // [capacity]
+  void link(const TableSpans& spans, const uint64_t* cand_pos, const FrameRec* recs, const uint32_t* counters,
+            uint32_t cap, uint32_t* jump, hipStream_t st) const {
+    hipLaunchKernelGGL(streams_resync_link_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, spans, cand_pos, recs,
+                       v_rank, v_list, counters, cap, jump);
+  }
+  void link(const OneSpan&, const uint64_t*, const FrameRec*, const uint32_t*, uint32_t, uint32_t*, hipStream_t) const {}
+};
+
 // The pipeline both indexes queue on `stream`: n_blocks > 0 workgroups of candidates into cand_pos[capacity], their skim
 // records and the jump levels.  Every launch is added to plan[0] when a plan is given.
 template <class Spans>
 hipError_t launch_links(const uint8_t* bytes, uint64_t n_bytes, const Spans& spans, uint32_t n_blocks,
                         uint64_t* block_counts, uint64_t* block_offsets, uint64_t* cand_pos, FrameRec* recs,
-                        uint32_t* jump, uint32_t* counters, size_t capacity, uint64_t* plan, hipStream_t st) {
+                        uint32_t* jump, uint32_t* counters, size_t capacity, uint64_t* plan, hipStream_t st,
+                        const Resync* resync = nullptr) {
   const uint32_t cap = static_cast<uint32_t>(capacity), levels = jump_levels(capacity);
   uint64_t uncounted[1];
   uint64_t* count = plan ? plan : uncounted;
@@ -233,13 +304,24 @@ hipError_t launch_links(const uint8_t* bytes, uint64_t n_bytes, const Spans& spa
                  static_cast<uint64_t>(n_blocks), nullptr, block_offsets, nullptr);
   COUNTED_LAUNCH(count, (streams_cand_kernel<Spans, true>), dim3(n_blocks), dim3(256), 0, st, bytes, n_bytes, spans,
                  nullptr, block_offsets, cand_pos, cap, counters);
-  launch_skim(bytes, n_bytes, spans, cand_pos, counters, cap, recs, st);
+  launch_skim(bytes, n_bytes, spans, cand_pos, counters, cap, recs, resync ? resync->numbers : nullptr, st);
   ++count[0];
   hipError_t e = launch_frame_crc16(bytes, cand_pos, cap, counters + C_CANDS, recs, st);
   if (e != hipSuccess) return e;
   ++count[0];
-  COUNTED_LAUNCH(count, streams_link_kernel<Spans>, dim3(ceil_div(cap, 256)), dim3(256), 0, st, spans, cand_pos, recs,
-                 counters, cap, jump);
+  if (resync) {
+    COUNTED_LAUNCH(count, resync_flag_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, recs, counters, cap,
+                   resync->v_flag);
+    COUNTED_LAUNCH(count, streams_scan_kernel, dim3(1), dim3(1024), 0, st, resync->v_flag, nullptr, nullptr,
+                   static_cast<uint64_t>(cap), counters + C_CANDS, resync->v_rank, nullptr);
+    COUNTED_LAUNCH(count, resync_list_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st, recs, resync->v_rank, counters,
+                   cap, resync->v_list);
+    resync->link(spans, cand_pos, recs, counters, cap, jump, st);
+    ++count[0];
+  } else {
+    COUNTED_LAUNCH(count, streams_link_kernel<Spans>, dim3(ceil_div(cap, 256)), dim3(256), 0, st, spans, cand_pos, recs,
+                   counters, cap, jump);
+  }
   for (uint32_t k = 1; k < levels; ++k)
     COUNTED_LAUNCH(count, jump_kernel, dim3(ceil_div(cap, 256)), dim3(256), 0, st,
                    jump + static_cast<size_t>(k - 1) * cap, jump + static_cast<size_t>(k) * cap, counters + C_CANDS, cap);
@@ -287,13 +369,18 @@ __global__ void __launch_bounds__(256) enumerate_kernel(const uint64_t* __restri
 }
 
 // ---------------------------------------------------------------- a batch: one lane per stream
+// RESYNC: the root is the first verified candidate of the span (v_rank, v_list: see resync_flag_kernel) and the chain
+// never ends with a reason.
+template <bool RESYNC>
 __global__ void __launch_bounds__(256) streams_chain_kernel(const Desc* __restrict__ descs, uint32_t n_streams,
                                                             const uint64_t* __restrict__ cand_pos,
                                                             const FrameRec* __restrict__ recs,
                                                             const uint32_t* __restrict__ jump, uint32_t levels,
                                                             const uint32_t* __restrict__ counters, uint32_t capacity,
                                                             uint64_t* __restrict__ s_frames, uint32_t* __restrict__ s_root,
-                                                            uint64_t* __restrict__ s_end, uint32_t* __restrict__ s_why) {
+                                                            uint64_t* __restrict__ s_end, uint32_t* __restrict__ s_why,
+                                                            const uint64_t* __restrict__ v_rank,
+                                                            const uint32_t* __restrict__ v_list) {
   const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n_streams) return;
   const Desc& d = descs[s];
@@ -301,14 +388,16 @@ __global__ void __launch_bounds__(256) streams_chain_kernel(const Desc* __restri
   uint64_t count = 0, end = d.offset;
   uint32_t root = kDead, why = 0;
   if (d.n_bytes != 0) {
-    root = verified_at(cand_pos, recs, 0, n, d.offset);  // the verified candidate at the stream's first byte
+    // the verified candidate at the stream's first byte
+    root = RESYNC ? resync_at(cand_pos, v_rank, v_list, 0, n, d.offset, d.offset + d.n_bytes)
+                  : verified_at(cand_pos, recs, 0, n, d.offset);
     if (root == kDead) {
-      why = FLACENC_HIP_DECODE_CHAIN;
+      why = RESYNC ? 0u : static_cast<uint32_t>(FLACENC_HIP_DECODE_CHAIN);
     } else {
       const ChainEnd c = walk_chain(jump, levels, capacity, root);
       count = c.count;
       end = cand_pos[c.last] + recs[c.last].len;
-      if (jump[c.last] != kEnd) why = FLACENC_HIP_DECODE_CHAIN;
+      if (!RESYNC && jump[c.last] != kEnd) why = FLACENC_HIP_DECODE_CHAIN;
     }
   }
   s_frames[s] = count;
@@ -442,6 +531,9 @@ int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq,
   const size_t o_fnode = take(F * 4), o_fslot = take(F * 4), o_fpcm = take(F * 8), o_fbad = take(F * 8);
   const size_t o_pcm = take((F + 1) * 8), o_bad = take((F + 1) * 8);
   const size_t o_extra = rq.extra_scratch ? take(rq.extra_scratch) : 0;
+  // (behind everything the other calls lay out, so that their layout is what it was)
+  const size_t o_num = rq.resync ? take(capacity * 8) : 0, o_vflag = rq.resync ? take(capacity * 8) : 0;
+  const size_t o_vrank = rq.resync ? take((capacity + 1) * 8) : 0, o_vlist = rq.resync ? take(capacity * 4) : 0;
   if ((rc = ensure(h, h->d_idx, need)) != FLACENC_HIP_OK) return rc;
   char* S = static_cast<char*>(h->d_idx.ptr);
   uint32_t* counters = reinterpret_cast<uint32_t*>(S + o_counters);
@@ -485,6 +577,9 @@ int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq,
   ix.pcm = pcm;
   ix.bad = bad;
   ix.scratch = S + o_extra;
+  const Resync resync{reinterpret_cast<uint64_t*>(S + o_num), reinterpret_cast<uint64_t*>(S + o_vflag),
+                      reinterpret_cast<uint64_t*>(S + o_vrank), reinterpret_cast<uint32_t*>(S + o_vlist)};
+  ix.cand_number = rq.resync ? resync.numbers : nullptr;
 
   // ---- the input ----
   const uint8_t* d_bytes = rq.bytes;
@@ -512,9 +607,16 @@ int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq,
   if (n_blocks)
     HIP_TRY(h, launch_links(d_bytes, n_bytes, TableSpans{descs, ns, reinterpret_cast<uint32_t*>(S + o_cstream)}, n_blocks,
                             reinterpret_cast<uint64_t*>(S + o_bcount), reinterpret_cast<uint64_t*>(S + o_boff), cand_pos,
-                            recs, jump, counters, capacity, plan, st));
-  COUNTED_LAUNCH(plan, streams_chain_kernel, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, ns, cand_pos, recs, jump,
-                 levels, counters, cap, s_frames, s_root, s_end, s_why);
+                            recs, jump, counters, capacity, plan, st, rq.resync ? &resync : nullptr));
+  if (rq.resync) {
+    // (no candidate pass ran on an input of 0 bytes: the ranking the root choice reads is then the empty one)
+    if (!n_blocks) HIP_TRY(h, hipMemsetAsync(resync.v_rank, 0, 8, st));
+    COUNTED_LAUNCH(plan, streams_chain_kernel<true>, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, ns, cand_pos, recs,
+                   jump, levels, counters, cap, s_frames, s_root, s_end, s_why, resync.v_rank, resync.v_list);
+  } else {
+    COUNTED_LAUNCH(plan, streams_chain_kernel<false>, dim3(ceil_div(ns, 256)), dim3(256), 0, st, descs, ns, cand_pos, recs,
+                   jump, levels, counters, cap, s_frames, s_root, s_end, s_why, nullptr, nullptr);
+  }
   COUNTED_LAUNCH(plan, streams_scan_kernel, dim3(1), dim3(1024), 0, st, s_frames, nullptr, perm,
                  static_cast<uint64_t>(ns), nullptr, base, nullptr);
   COUNTED_LAUNCH(plan, streams_verdict_kernel, dim3(1), dim3(1), 0, st, base, ns, static_cast<uint64_t>(max_frames), cap,
@@ -531,6 +633,12 @@ int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq,
 hipError_t streamindex::launch_scan2(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out_a, uint64_t* out_b,
                                      hipStream_t stream) {
   hipLaunchKernelGGL(streams_scan_kernel, dim3(1), dim3(1024), 0, stream, a, b, nullptr, n, nullptr, out_a, out_b);
+  return hipGetLastError();
+}
+
+hipError_t streamindex::launch_scan2_dev(const uint64_t* a, const uint64_t* b, uint64_t n, const uint32_t* n_dev,
+                                         uint64_t* out_a, uint64_t* out_b, hipStream_t stream) {
+  hipLaunchKernelGGL(streams_scan_kernel, dim3(1), dim3(1024), 0, stream, a, b, nullptr, n, n_dev, out_a, out_b);
   return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // and the segmented index of a batch of FLAC streams, as flacenc_hip_decode_streams (flac_decode_streams.cpp) and
 // flacenc_hip_decode_ranges (flac_decode_ranges.cpp) share it: on top of the pipeline one chain per stream, the scan of
 // chain lengths, the verdict, every chain frame enumerated and the two scans over the frame sequence (PCM bytes, frames
-// with a status).  build() queues all of it on the handle's stream and synchronises nothing; what it leaves in device
+// with a status).  flacenc_hip_recover_streams (flac_recover_streams.cpp) asks for the resynchronising form of the same
+// index (Request::resync).  build() queues all of it on the handle's stream and synchronises nothing; what it leaves in device
 // scratch (h->d_idx) is described by Index.  Behind it the header holds what the host sides of those two batch calls
 // share and the index does not need itself: call_limits_ok, sort_by_channels and download_pcm.  Internal to the library.
 #ifndef STREAM_INDEX_H_
@@ -35,6 +36,10 @@ struct Request {
   const void* extra_table;    // goes up with the descriptors in the same transfer (may be null)
   size_t extra_table_bytes;
   size_t extra_scratch;       // bytes of device scratch of the caller's own
+  // flacenc_hip_recover_streams: every candidate's coded number is kept (Index::cand_number), and a stream's chain
+  // resynchronises -- its root is the first verified candidate of the span, the frame behind a frame the first verified
+  // candidate at or behind its end.  false: the verified chain from the span's first byte, the index as it has always been
+  bool resync;
 };
 
 struct Index {
@@ -58,6 +63,7 @@ struct Index {
   uint32_t *f_node, *f_slot;  // per chain frame m < counters[C_FRAMES]: its candidate, its slot
   uint64_t *pcm, *bad;        // exclusive scans over the frame sequence, [max_frames + 1]
   char* scratch;              // extra_scratch bytes, 256-byte aligned
+  const uint64_t* cand_number;  // Request::resync only: per candidate, coded number << 1 | blocking bit
 };
 
 // plan: launches, synchronisations, transfers, channel classes of the call (plan[3] is set, the others are added to)
@@ -67,6 +73,9 @@ int build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq, Index& ix);
 // j < i, out_x[n] the total.  One launch.  The batch encoder (encode_streams.cpp) uses it too.
 hipError_t launch_scan2(const uint64_t* a, const uint64_t* b, uint64_t n, uint64_t* out_a, uint64_t* out_b,
                         hipStream_t stream);
+// the same over min(n, *n_dev) words, n_dev device memory
+hipError_t launch_scan2_dev(const uint64_t* a, const uint64_t* b, uint64_t n, const uint32_t* n_dev, uint64_t* out_a,
+                            uint64_t* out_b, hipStream_t stream);
 
 // What the two batch calls refuse alike, in front of their tables: the memory kind and the stream, frame and n_bytes
 // limits.

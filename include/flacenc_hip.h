@@ -1079,6 +1079,61 @@ int flacenc_hip_decode_streams_md5(flacenc_hip_handle* h, const uint8_t* bytes, 
                                    uint64_t* totals, uint64_t call_totals[2], int memory_kind, uint8_t* digests);
 
 /*
+ * Decoding through errors (what `flac -F` does for one file): flacenc_hip_decode_streams stops a stream at the first
+ * byte where no verified frame starts; this call resynchronises on the next verified frame, places every frame where
+ * its header says it belongs and puts silence where samples are lost.  bytes, n_bytes, streams, n_streams, max_frames,
+ * out, out_bytes and memory_kind, the argument checks, "nothing is written on error" and FLACENC_HIP_INDEX_ERROR (set in
+ * call_totals[0], nothing written, all totals zero) are exactly those of flacenc_hip_decode_streams.
+ *   origins       host memory, n_streams entries, or NULL for all zeros: the absolute inter-channel sample number that
+ *                 byte 0 of the stream's slot stands for (0 for a whole file, a seek point's sample number for a span
+ *                 that starts there)
+ *   totals        [n_streams][8], where `out` lives; gaps: [max_gaps][3], where `out` lives, may be NULL (then max_gaps
+ *                 must be 0); call_totals: [4], host memory
+ * The rule, every step a function of the span's bytes, the descriptor and the origin only:
+ * 1. The verified candidates of a stream are the byte positions of its span where a header valid for the stream's
+ *    channels and bits_per_sample starts whose CRC-8 matches, whose subframes all parse, whose frame lies wholly inside
+ *    the span and whose CRC-16 matches.
+ * 2. The resynchronising chain: its first frame is the verified candidate at the lowest position of the span; the frame
+ *    after frame i is the verified candidate at the lowest position at or behind end(i) = pos(i) + len(i).  (A header
+ *    planted inside a chain frame is therefore never a frame.)  A break is every place where the next chain frame does
+ *    not start exactly where the one before ended, the bytes in front of the first chain frame and the bytes behind
+ *    the last one up to the span's end included.
+ * 3. Coded position: P(k) = number(k) * max_block_size under a fixed-blocking header (the descriptor's max_block_size:
+ *    STREAMINFO's block size of such a stream), P(k) = number(k) under a variable-blocking header; E(k) = P(k) +
+ *    block_size(k).  64-bit arithmetic.
+ * 4. Placement: chain frame k is placed when block_size(k) <= max_block_size, P(k) >= origin and P(k) >= the maximum of
+ *    E(j) over ALL earlier chain frames j < k, placed or not (the empty maximum is the origin).  Otherwise it is dropped
+ *    (a repeated frame, a frame from before the origin, frames in descending order, a block above the maximum).  E does
+ *    not decrease over placed frames.
+ * 5. Room: with W = channels * bytes_per_sample the placed frames are cut at the first one with (E(k) - origin) * W >
+ *    out_capacity: it and every placed frame behind it are not written, and the stop reason is
+ *    FLACENC_HIP_DECODE_NO_ROOM.
+ * 6. Output: with L = E(last written frame) - origin (0 if none is written) the first L * W bytes of the slot are
+ *    defined: sample t of a written frame at slot offset (P - origin + t) * W + c * bytes_per_sample in the
+ *    flacenc_hip_pack_le_bytes layout, the value flacenc_hip_decode_streams writes; every byte of [0, L * W) in no
+ *    written frame is 0.  Slot bytes from L * W on and bytes of `out` in no slot are untouched.
+ * 7. totals[s]: [0] frames written, [1] L, [2] samples of silence inside [0, L), [3] chain frames dropped by 4,
+ *    [4] bytes of the span in no chain frame, [5] breaks, [6] the stop reason (0 or NO_ROOM), [7] 0.  A span of 0 bytes
+ *    gives all zeros, a span without a verified candidate [4] = n_bytes, [5] = 1 and the rest 0.
+ * 8. gaps: every maximal run of silence inside [0, L) of every stream is a record {stream, first_sample, n_samples},
+ *    first_sample relative to the slot; ordered by stream index, then position.  The first min(total, max_gaps) records
+ *    are written and nothing beyond them; call_totals[2] is the total, so a caller can come back with a larger table.
+ * 9. call_totals: [0] frames written over all streams (FLACENC_HIP_INDEX_ERROR in its top bit), [1] the sum of L,
+ *    [2] gaps, [3] frames dropped.
+ * Consequence: for a stream on which flacenc_hip_decode_streams ends with stop reason 0 and whose frames are numbered
+ * consecutively from origin / max_block_size (fixed blocking) or origin (variable blocking), the slot bytes, [0] and [1]
+ * are that call's, and [2..6] are 0.  Garbage gives counts, never a fault; no byte outside a span is read as a frame and
+ * damage in one stream changes nothing for any other.  Errors: those of flacenc_hip_decode_streams, and
+ * FLACENC_HIP_ERR_BAD_ARGUMENT for a NULL gaps with max_gaps > 0.  Launches, synchronisations and transfers do not
+ * depend on n_streams or on the damage.  The call blocks and runs on the handle's stream.
+ */
+int flacenc_hip_recover_streams(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
+                                size_t n_streams, const uint64_t* origins, size_t max_frames, uint8_t* out,
+                                uint64_t out_bytes, uint64_t* totals /* [n_streams][8] */,
+                                uint64_t* gaps /* [max_gaps][3], may be NULL */, size_t max_gaps, uint64_t call_totals[4],
+                                int memory_kind);
+
+/*
  * Seeking: samples [first_sample, first_sample + n_samples) of streams of a batch, for any number of ranges, in one call
  * -- the crops a model is fed, the seconds a player previews -- without decoding, storing or moving the rest.  Only the
  * frames a range touches are decoded, each only up to the last sample wanted, and only the wanted samples are written.

@@ -424,6 +424,16 @@ extern "C" {
         h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, max_frames: usize,
         out: *mut u8, out_bytes: u64, totals: *mut u64, call_totals: *mut u64, memory_kind: c_int, digests: *mut u8,
     ) -> c_int;
+    /// `flacenc_hip_decode_streams` through errors: every stream's chain resynchronises on the next verified frame, frames
+    /// go where their coded numbers place them from `origins[s]` on (null: all zero) and lost samples are silence.
+    /// `totals` is `[n_streams][8]` = frames written, defined samples, silence, frames dropped, bytes in no frame, breaks,
+    /// stop reason (0 or `DECODE_NO_ROOM`), 0; `gaps` (`[max_gaps][3]` = stream, first sample, samples; may be null with
+    /// `max_gaps == 0`) lives where `out` lives; `call_totals` = frames (| `INDEX_ERROR`), samples, gaps, frames dropped.
+    pub fn flacenc_hip_recover_streams(
+        h: *mut Handle, bytes: *const u8, n_bytes: u64, streams: *const c_void, n_streams: usize, origins: *const u64,
+        max_frames: usize, out: *mut u8, out_bytes: u64, totals: *mut u64, gaps: *mut u64, max_gaps: usize,
+        call_totals: *mut u64, memory_kind: c_int,
+    ) -> c_int;
     /// Sample ranges of a batch of streams in one call: `ranges` points at `n_ranges` `RangeDesc` in host memory, each
     /// naming a stream of `streams` (whose `out_offset` / `out_capacity` are ignored); `totals` is `[n_ranges][4]` =
     /// samples written, stop reason (0, the stream's, or `DECODE_RANGE_END`), and a seek point: byte offset in the span

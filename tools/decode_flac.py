@@ -6,6 +6,10 @@ little-endian PCM -- the byte string the STREAMINFO MD5 is defined over.  The ho
 means "not checked") and writes the WAV (8 / 16 / 24-bit PCM).
 
     python tools/decode_flac.py in.flac out.wav
+
+With --through-errors a damaged file is decoded through its errors (flacenc_hip_recover_streams, tools/decode_many.py's
+recover_all on the one file): silence where samples are lost, the damage printed, and "damaged" where the MD5 of a
+file that lost anything could only mismatch.
 """
 import argparse
 import hashlib
@@ -84,8 +88,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("input")
     ap.add_argument("output")
+    ap.add_argument("--through-errors", action="store_true",
+                    help="resynchronise behind damage and write silence where samples are lost")
     args = ap.parse_args()
     data = open(args.input, "rb").read()
+    if args.through_errors:
+        import decode_many
+        with _capi.Handle(0) as h:
+            pcm, info, totals, gaps = decode_many.recover_all([data], h)[0]
+        write_wav(args.output, pcm, info)
+        print(f"{totals[0]} frames, {totals[1]} samples x {info['channels']} channels, {info['bits_per_sample']} bits, "
+              f"{totals[2]} of silence in {len(gaps)} gaps, {totals[3]} frames dropped, {totals[5]} breaks: "
+              f"{decode_many.recovered_status(pcm, info, totals)}")
+        return
     with _capi.Handle(0) as h:
         pcm, info = decode(data, h)
     bps = info["bits_per_sample"]
