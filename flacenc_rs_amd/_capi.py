@@ -74,7 +74,7 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_last_recover_plan",
                  "flacenc_hip_debug_set_encode_streams_chunk",
                  "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill",
-                 "flacenc_hip_debug_set_planar_fill_form")
+                 "flacenc_hip_debug_set_planar_fill_form", "flacenc_hip_debug_segmax_scan")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -385,6 +385,8 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
         L.flacenc_hip_debug_set_planar_fill_form.argtypes = [vp, C.c_int]
         L.flacenc_hip_debug_streams_fill.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32,
                                                      vp, C.c_size_t]
+    if hasattr(L, "flacenc_hip_debug_segmax_scan"):
+        L.flacenc_hip_debug_segmax_scan.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
     if hasattr(L, "flacenc_hip_debug_set_decode_plan"):
         L.flacenc_hip_debug_set_decode_plan.argtypes = [vp, C.c_size_t, C.c_size_t]
         L.flacenc_hip_debug_last_decode_plan.argtypes = [vp] + [C.POINTER(C.c_size_t)] * 4
@@ -832,6 +834,22 @@ class Handle:
         if check:
             self._check(rc)
         return rc
+
+    def debug_segmax_scan(self, values, heads, room: int = None, check: bool = True):
+        """The segmented max-scan of recover_streams alone (flacenc_hip_debug.h): values uint64 [n], heads [n] (non-zero:
+        the element starts a segment; element 0 must), the launches sized by room >= n (default n).  -> uint64 [n], each
+        element's maximum from its segment's head on; blocks.  check=False: -> (return code, the array)."""
+        v = np.ascontiguousarray(values, np.uint64)
+        hd = np.ascontiguousarray(np.asarray(heads) != 0, np.uint8)
+        assert v.ndim == 1 and hd.shape == v.shape
+        out = np.zeros(len(v), np.uint64)
+        ptr = (lambda x: x.ctypes.data) if len(v) else (lambda x: None)
+        rc = self._hook("flacenc_hip_debug_segmax_scan")(self._h, ptr(v), ptr(hd), len(v),
+                                                         len(v) if room is None else int(room), ptr(out))
+        if not check:
+            return rc, out
+        self._check(rc)
+        return out
 
     def synchronize(self):
         self._check(self._lib.flacenc_hip_synchronize(self._h))

@@ -3,6 +3,7 @@
 #include "api_internal.h"
 #include "flacenc_hip_debug.h"
 #include "stream_encode_core.h"
+#include "stream_index.h"
 
 extern "C" {
 
@@ -158,6 +159,57 @@ int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, 
                                               static_cast<uint32_t>(n_frames), channels, bytes_per_sample, 0, stride, frames,
                                               h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_segmax_scan(flacenc_hip_handle* h, const uint64_t* values, const uint8_t* heads, size_t n,
+                                  size_t room, uint64_t* out) {
+  using namespace flacenc_hip;
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (room < n || room > streambatch::MAX_FRAMES || (n && (!values || !heads || !out || !heads[0]))) {
+    h->last_error = "debug_segmax_scan: null pointer, room below n or above 2^30, or element 0 is no head";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  // the frame sequence the kernels see: segment k is slot k, base[k] its head's index, base[segments] = n
+  std::vector<uint32_t> slot(n);
+  std::vector<uint64_t> base;
+  for (size_t m = 0; m < n; ++m) {
+    if (heads[m]) base.push_back(m);
+    slot[m] = static_cast<uint32_t>(base.size() - 1);
+  }
+  base.push_back(n);
+  const uint32_t counters[4] = {0, 0, 0, static_cast<uint32_t>(n)};  // streamindex::C_FRAMES
+  static_assert(streamindex::C_FRAMES == 3, "counters above");
+  const size_t NB = (room + 255) / 256;
+  const size_t o_emax = 0, o_base = o_emax + a256(room * 8 + 8), o_aggv = o_base + a256(base.size() * 8);
+  const size_t o_slot = o_aggv + a256(NB * 8 + 8), o_aggh = o_slot + a256(n * 4 + 4), o_counters = o_aggh + a256(NB * 4 + 4);
+  HIP_TRY(h, hipSetDevice(h->device));
+  struct Scratch {
+    char* p = nullptr;
+    ~Scratch() {
+      if (p) (void)hipFree(p);
+    }
+  } d;
+  HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&d.p), o_counters + 256));
+  hipStream_t st = h->stream;
+  streamindex::Drain drain{h};  // the host vectors and the scratch outlive what was queued, on every way out
+  uint64_t* emax = reinterpret_cast<uint64_t*>(d.p + o_emax);
+  if (n) {
+    HIP_TRY(h, hipMemcpyAsync(emax, values, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(d.p + o_slot, slot.data(), n * 4, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(h, hipMemcpyAsync(d.p + o_base, base.data(), base.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(h, hipMemcpyAsync(d.p + o_counters, counters, sizeof counters, hipMemcpyHostToDevice, st));
+  uint64_t plan[4] = {0, 0, 0, 0};
+  const hipError_t launched = launch_segmax_scan(plan, reinterpret_cast<const uint32_t*>(d.p + o_slot),
+                                                 reinterpret_cast<const uint64_t*>(d.p + o_base), emax,
+                                                 reinterpret_cast<const uint32_t*>(d.p + o_counters), room,
+                                                 reinterpret_cast<uint32_t*>(d.p + o_aggh),
+                                                 reinterpret_cast<uint64_t*>(d.p + o_aggv), st);
+  HIP_TRY(h, launched);
+  if (n) HIP_TRY(h, hipMemcpyAsync(out, emax, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(h, hipStreamSynchronize(st));
+  drain.armed = false;
   return FLACENC_HIP_OK;
 }
 

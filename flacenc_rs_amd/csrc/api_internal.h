@@ -372,6 +372,16 @@ hipError_t launch_planar_pack(const uint32_t* elems, const planarenc::Frame* tab
                               const planarenc::Stream* streams, const flacenc_hip_pcm_stream_desc* descs, uint32_t per,
                               uint32_t sample_format, uint8_t* image, hipStream_t stream);
 
+// ---- flac_recover_streams.cpp ----
+// The segmented inclusive max-scan of flacenc_hip_recover_streams on `stream`: segmax_reduce_kernel, segmax_carry_kernel
+// and segmax_apply_kernel, sized by max_frames, over the counters[C_FRAMES] <= max_frames elements of a frame sequence.
+// Element m is a head where m == base[f_slot[m]]; emax[m] goes in as its value and comes out as the maximum from its
+// segment's head up to m.  agg_h, agg_v: ceil(max_frames / 256) words of scratch.  All pointers are device memory;
+// three launches, counted in plan[0].
+hipError_t launch_segmax_scan(uint64_t* plan, const uint32_t* f_slot, const uint64_t* base, uint64_t* emax,
+                              const uint32_t* counters, size_t max_frames, uint32_t* agg_h, uint64_t* agg_v,
+                              hipStream_t stream);
+
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);
 void fill_header_specs(FramePackArgs& a, uint32_t block_size, uint32_t sample_rate, uint32_t bits_per_sample);

@@ -319,6 +319,29 @@ __global__ void __launch_bounds__(256) recover_zero_kernel(Frames f, const uint6
   if (t < z.tail) reinterpret_cast<uint8_t*>(a_hi - z.tail)[t] = 0;
 }
 
+}  // namespace
+
+// The three launches of the segmented max-scan over a frame sequence of at most max_frames elements (api_internal.h):
+// recover_streams_impl below and flacenc_hip_debug_segmax_scan (api_debug_hooks.cpp) both come through here.
+hipError_t launch_segmax_scan(uint64_t* plan, const uint32_t* f_slot, const uint64_t* base, uint64_t* emax,
+                              const uint32_t* counters, size_t max_frames, uint32_t* agg_h, uint64_t* agg_v,
+                              hipStream_t stream) {
+  Frames f{};  // the kernels read these four fields and no other
+  f.f_slot = f_slot;
+  f.base = base;
+  f.emax = emax;
+  f.counters = counters;
+  const size_t NB = ceil_div(max_frames, 256);
+  const dim3 per_frame(max_frames ? NB : 1), wg(256);
+  COUNTED_LAUNCH(plan, segmax_reduce_kernel, per_frame, wg, 0, stream, f, agg_h, agg_v);
+  COUNTED_LAUNCH(plan, segmax_carry_kernel, dim3(1), dim3(1024), 0, stream, agg_h, agg_v,
+                 static_cast<uint32_t>(max_frames ? NB : 0));
+  COUNTED_LAUNCH(plan, segmax_apply_kernel, per_frame, wg, 0, stream, f, agg_h, agg_v);
+  return hipGetLastError();
+}
+
+namespace {
+
 int recover_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_bytes, const void* streams,
                          size_t n_streams, const uint64_t* origins, size_t max_frames, uint8_t* out, uint64_t out_bytes,
                          uint64_t* totals, uint64_t* gaps, size_t max_gaps, uint64_t call_totals[4], int memory_kind) {
@@ -425,9 +448,7 @@ int recover_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n
   HIP_TRY(h, hipMemsetAsync(f.acc, 0, n_streams * 32, st));
   // ---- positions, the prefix maximum per stream, placement ----
   COUNTED_LAUNCH(plan, recover_position_kernel, per_frame, wg, 0, st, f);
-  COUNTED_LAUNCH(plan, segmax_reduce_kernel, per_frame, wg, 0, st, f, agg_h, agg_v);
-  COUNTED_LAUNCH(plan, segmax_carry_kernel, dim3(1), dim3(1024), 0, st, agg_h, agg_v, static_cast<uint32_t>(F ? NB : 0));
-  COUNTED_LAUNCH(plan, segmax_apply_kernel, per_frame, wg, 0, st, f, agg_h, agg_v);
+  HIP_TRY(h, launch_segmax_scan(plan, f.f_slot, f.base, f.emax, f.counters, F, agg_h, agg_v, st));
   COUNTED_LAUNCH(plan, recover_place_kernel, per_frame, wg, 0, st, f);
   HIP_TRY(h, launch_scan2_dev(f.placed, nullptr, F, n_frames, f.pl, nullptr, st));
   ++plan[0];

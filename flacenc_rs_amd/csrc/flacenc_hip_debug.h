@@ -120,6 +120,17 @@ int flacenc_hip_debug_set_planar_fill_form(flacenc_hip_handle* h, int form);
 int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t total_samples, uint32_t channels,
                                    uint32_t bytes_per_sample, size_t n_frames, uint32_t block_size, int32_t* frames,
                                    size_t stride);
+/* Test hook (no reference counterpart): the segmented inclusive max-scan of flacenc_hip_recover_streams on its own -- the
+ * same three launches (a workgroup's aggregate, one workgroup over the aggregates, the aggregates applied) the call
+ * makes, sized by `room` as the call sizes them by max_frames and not by the frames it finds.  values[0 .. n) and
+ * heads[0 .. n) are host memory; heads[m] != 0 makes element m the first of a segment (a stream's first chain frame).
+ * out[m] (host memory, n words) gets the unsigned maximum of values from the head of m's segment up to m.  The contract:
+ * element 0 is a head, as it always is in the call; room >= n, at most 2^30; anything else is
+ * FLACENC_HIP_ERR_BAD_ARGUMENT.  n == 0 runs the launches over no element.  Builds the frame sequence (one slot per
+ * segment) on the host, uploads it into scratch of its own, launches on the handle's stream and blocks until `out` is
+ * written. */
+int flacenc_hip_debug_segmax_scan(flacenc_hip_handle* h, const uint64_t* values, const uint8_t* heads, size_t n,
+                                  size_t room, uint64_t* out);
 
 #ifdef __cplusplus
 }

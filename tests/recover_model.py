@@ -25,8 +25,14 @@ class Frame:
 
 
 def verified(data, channels, bps):
-    """Rule 1: every verified candidate of the span `data`, in ascending position."""
-    data = np.ascontiguousarray(data, np.uint8)
+    """Rule 1: every verified candidate of the span `data`, in ascending position.  (Kept per span: batches repeat their
+    streams, and the corpus tests walk the chains the expectations were made from.)"""
+    return list(_verified(np.ascontiguousarray(data, np.uint8).tobytes(), channels, bps))
+
+
+@functools.lru_cache(None)
+def _verified(raw, channels, bps):
+    data = np.frombuffer(raw, np.uint8)
     dec = decoder()
     out = []
     sync = np.flatnonzero((data[:-1] == 0xFF) & ((data[1:] & 0xFE) == 0xF8)) if len(data) > 1 else []
