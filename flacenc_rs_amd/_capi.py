@@ -74,7 +74,8 @@ DEBUG_SYMBOLS = ("flacenc_hip_debug_set_stamps", "flacenc_hip_debug_set_fixed_ke
                  "flacenc_hip_debug_last_recover_plan",
                  "flacenc_hip_debug_set_encode_streams_chunk",
                  "flacenc_hip_debug_last_encode_streams_plan", "flacenc_hip_debug_streams_fill",
-                 "flacenc_hip_debug_set_planar_fill_form", "flacenc_hip_debug_segmax_scan")
+                 "flacenc_hip_debug_set_planar_fill_form", "flacenc_hip_debug_segmax_scan",
+                 "flacenc_hip_debug_scratch_bytes", "flacenc_hip_debug_last_search_slices")
 EXPORTED_SYMBOLS = (
     "flacenc_hip_abi_version",
     "flacenc_hip_device_count",
@@ -387,6 +388,9 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
                                                      vp, C.c_size_t]
     if hasattr(L, "flacenc_hip_debug_segmax_scan"):
         L.flacenc_hip_debug_segmax_scan.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    if hasattr(L, "flacenc_hip_debug_scratch_bytes"):
+        L.flacenc_hip_debug_scratch_bytes.argtypes = [vp, vp]
+        L.flacenc_hip_debug_last_search_slices.argtypes = [vp, C.POINTER(C.c_uint32)]
     if hasattr(L, "flacenc_hip_debug_set_decode_plan"):
         L.flacenc_hip_debug_set_decode_plan.argtypes = [vp, C.c_size_t, C.c_size_t]
         L.flacenc_hip_debug_last_decode_plan.argtypes = [vp] + [C.POINTER(C.c_size_t)] * 4
@@ -717,6 +721,18 @@ class Handle:
         if not hasattr(self._lib, name):
             raise RuntimeError(name + " is not in the product library: make the handle with Handle(dev, hooks=True)")
         return getattr(self._lib, name)
+
+    def debug_scratch_bytes(self):
+        """(total, largest) capacity in bytes of the device buffers the handle holds (flacenc_hip_debug.h)."""
+        out = np.zeros(2, np.uint64)
+        self._check(self._hook("flacenc_hip_debug_scratch_bytes")(self._h, out.ctypes.data))
+        return int(out[0]), int(out[1])
+
+    def debug_last_search_slices(self) -> int:
+        """Slices of the last search-flag launch on the handle (flacenc_hip_debug.h); 0 before the first."""
+        n = C.c_uint32(0)
+        self._check(self._hook("flacenc_hip_debug_last_search_slices")(self._h, C.byref(n)))
+        return n.value
 
     def debug_set_fixed_keys(self, device_ptr: int):
         self._check(self._hook("flacenc_hip_debug_set_fixed_keys")(self._h, device_ptr or None))

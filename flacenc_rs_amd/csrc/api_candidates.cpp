@@ -415,7 +415,7 @@ int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const
     rc = ensure(h, h->d_order, flacenc_hip::order_search_scratch_bytes(a.n_subframes, cfg->lpc_order, shape));
     if (rc != FLACENC_HIP_OK) return rc;
     HIP_TRY(h, flacenc_hip::launch_order_search(a, plan, a.reference_order == 2u ? 1u : 0u, shape, h->d_order.ptr,
-                                                stream));
+                                                stream, &h->last_search_slices));
     return FLACENC_HIP_OK;
   }
   // frame-level callers on the big-block shapes: L / R candidates straight into the output rows, role min / max

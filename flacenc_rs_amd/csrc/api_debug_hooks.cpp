@@ -7,6 +7,23 @@
 
 extern "C" {
 
+int flacenc_hip_debug_scratch_bytes(flacenc_hip_handle* h, uint64_t out[2]) {
+  if (!h || !out) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  out[0] = out[1] = 0;
+  for (const flacenc_hip::DeviceBuffer* b : flacenc_hip::device_buffers(h)) {
+    if (!b->ptr) continue;
+    out[0] += b->cap;
+    if (b->cap > out[1]) out[1] = b->cap;
+  }
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_debug_last_search_slices(flacenc_hip_handle* h, uint32_t* slices) {
+  if (!h || !slices) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  *slices = h->last_search_slices;
+  return FLACENC_HIP_OK;
+}
+
 int flacenc_hip_debug_set_fixed_keys(flacenc_hip_handle* h, unsigned long long* device_keys) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   h->fixed_keys = device_keys;

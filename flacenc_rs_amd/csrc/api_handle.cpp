@@ -29,6 +29,18 @@ int ensure(flacenc_hip_handle* h, DeviceBuffer& b, size_t bytes) {
   return FLACENC_HIP_OK;
 }
 
+std::vector<DeviceBuffer*> device_buffers(flacenc_hip_handle* h) {
+  std::vector<DeviceBuffer*> all = {
+      &h->d_samples, &h->d_residual, &h->d_params, &h->d_bps, &h->d_autocorr, &h->d_lpc, &h->d_tables, &h->d_keys, &h->d_sel,
+      &h->d_results, &h->d_out, &h->d_outlen, &h->d_cparams, &h->d_cresid, &h->d_fparams, &h->d_fresid, &h->d_fkeys,
+      &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram, &h->d_esc, &h->d_dec,
+      &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack, &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk,
+      &h->d_wlist, &h->d_wrows, &h->d_wbps, &h->d_order, &h->d_ppk_off, &h->d_ppk_io, &h->d_dpcm_idx, &h->d_md5, &h->d_encs};
+  for (int i = 0; i < 2; ++i)
+    for (DeviceBuffer* b : {&h->d_pcm[i], &h->d_pack[i], &h->d_plen[i], &h->d_poff[i], &h->d_cont[i]}) all.push_back(b);
+  return all;
+}
+
 int drained(flacenc_hip_handle* h, int rc, bool nothing_queued) {
   if (rc != FLACENC_HIP_OK || nothing_queued) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -89,18 +101,11 @@ void flacenc_hip_destroy(flacenc_hip_handle* h) {
   h->comm = nullptr;
   for (WindowEntry& e : h->windows)
     if (e.dev) (void)hipFree(e.dev);
-  for (DeviceBuffer* b : {&h->d_samples, &h->d_residual, &h->d_params, &h->d_bps, &h->d_autocorr,
-                          &h->d_lpc, &h->d_tables, &h->d_keys, &h->d_sel, &h->d_results, &h->d_out, &h->d_outlen, &h->d_cparams, &h->d_cresid,
-                          &h->d_fparams, &h->d_fresid, &h->d_fkeys, &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram, &h->d_esc,
-                          &h->d_dec, &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack,
-                          &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk, &h->d_wlist, &h->d_wrows, &h->d_wbps, &h->d_order,
-                          &h->d_ppk_off, &h->d_ppk_io, &h->d_dpcm_idx, &h->d_md5, &h->d_encs})
+  for (DeviceBuffer* b : device_buffers(h))
     if (b->ptr) (void)hipFree(b->ptr);
   if (h->d_cert_fb) (void)hipFree(h->d_cert_fb);  // (the order mode's counters and their pinned mirror)
   if (h->h_cert_fb) (void)hipHostFree(h->h_cert_fb);
   for (int i = 0; i < 2; ++i) {
-    for (DeviceBuffer* b : {&h->d_pcm[i], &h->d_pack[i], &h->d_plen[i], &h->d_poff[i], &h->d_cont[i]})
-      if (b->ptr) (void)hipFree(b->ptr);
     for (void* p : {h->pin_in[i], h->pin_out[i], h->pin_meta[i]})
       if (p) (void)hipHostFree(p);
     for (hipEvent_t e : {h->ev_h2d[i], h->ev_fill[i], h->ev_pack[i], h->ev_d2h[i]})

@@ -227,6 +227,8 @@ struct flacenc_hip_handle {
   // frame-level call of flacenc_hip_encode_streams in place of its rule (0: the rule), and what the last call did
   size_t encode_streams_chunk_override = 0;
   uint64_t last_encode_streams_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // test hook, see flacenc_hip_debug_last_search_slices: the slices of the last order / window / precision search launch
+  uint32_t last_search_slices = 0;
   // measurement hook, see flacenc_hip_debug_set_planar_fill_form: how planar_fill_kernel loads (1 aligned 16-byte loads
   // brought into place, the product's form: the faster one; 0 dwords)
   int planar_fill_form = 1;
@@ -262,6 +264,8 @@ namespace flacenc_hip {
 bool set_error(flacenc_hip_handle* h, const char* what, hipError_t err);
 // grows by 25 % + 256 bytes, frees what it held: the contents do not survive
 int ensure(flacenc_hip_handle* h, DeviceBuffer& b, size_t bytes);
+// every DeviceBuffer the handle owns: what flacenc_hip_destroy frees and flacenc_hip_debug_scratch_bytes reports
+std::vector<DeviceBuffer*> device_buffers(flacenc_hip_handle* h);
 // the tail of a blocking call on device pointers: the async entry's code, or the handle's stream drained
 int drained(flacenc_hip_handle* h, int rc, bool nothing_queued);
 // the blocking calls on host pointers: `n_rows` rows of `block_size` words between the caller's buffer (row stride

@@ -131,6 +131,16 @@ int flacenc_hip_debug_streams_fill(flacenc_hip_handle* h, const uint8_t* bytes, 
  * written. */
 int flacenc_hip_debug_segmax_scan(flacenc_hip_handle* h, const uint64_t* values, const uint8_t* heads, size_t n,
                                   size_t room, uint64_t* out);
+/* Test hook (no reference counterpart): the device buffers the handle holds right now -- its scratch, staging and
+ * tables; not the window cache, not pinned host memory.  out[0] gets the sum of their capacities in bytes, out[1] the
+ * largest one's.  A buffer only ever grows (by a quarter more than was asked for), so after a call both words are at
+ * least what that call needed.  tests/test_gpu_launch_scale.py asserts with it that a launch it calls large did put
+ * handle scratch beyond the 2^32-byte or 2^31-element offset it claims. */
+int flacenc_hip_debug_scratch_bytes(flacenc_hip_handle* h, uint64_t out[2]);
+/* Test hook (no reference counterpart): into how many slices of at most kSearchScratchCap bytes of scratch the last
+ * launch under FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH on the handle cut its
+ * subframes (order_search.cpp, slice_subframes); 0 before the first such launch. */
+int flacenc_hip_debug_last_search_slices(flacenc_hip_handle* h, uint32_t* slices);
 
 #ifdef __cplusplus
 }

@@ -568,7 +568,8 @@ size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order, cons
 }
 
 hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly,
-                               const SearchShape& shape, void* scratch, hipStream_t stream) {
+                               const SearchShape& shape, void* scratch, hipStream_t stream, uint32_t* n_slices) {
+  if (n_slices) *n_slices = 0;
   if (a.n_subframes == 0) return hipSuccess;
   if (a.split_scratch == nullptr || scratch == nullptr || a.lpc_order < 1 || a.lpc_order > 32 || a.block_size < 64 ||
       a.block_size > 32767 || shape.n_windows < 1 || shape.n_windows > kMaxSearchWindows || shape.guess_orders > 32 ||
@@ -600,6 +601,7 @@ hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& pl
   }
   for (size_t sf0 = 0; sf0 < n; sf0 += slice) {
     const uint32_t ns = static_cast<uint32_t>(n - sf0 < slice ? n - sf0 : slice);
+    if (n_slices) ++*n_slices;
     // (stereo slices are whole frames: frame f's two channels at samples + 2 f stride)
     const int32_t* samples = a.samples + (a.stereo ? sf0 / 2 : sf0) * a.stride;
     // 1. R[0..P] of every window in the stable build's order (or nightly's)

@@ -58,7 +58,8 @@ size_t order_search_scratch_bytes(uint32_t n_subframes, uint32_t lpc_order, cons
 //   5. the stage-3 kernels write the records and residual rows from those predictors (a predictor record's word 35,
 //      when not 0, is the subframe's precision in place of the launch's: Q > 1 only).
 hipError_t launch_order_search(const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, uint32_t nightly,
-                               const SearchShape& shape, void* scratch, hipStream_t stream);
+                               const SearchShape& shape, void* scratch, hipStream_t stream, uint32_t* n_slices = nullptr);
+// (n_slices, when given: how many slices of at most kSearchScratchCap the call cut its subframes into)
 
 }  // namespace flacenc_hip
 #endif

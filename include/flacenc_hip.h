@@ -22,6 +22,13 @@
  * ONE STREAM AT A TIME PER HANDLE: the *_async entry points take a stream per call, but the handle's scratch
  * (and the marked-subframe counters its clean-up launches alternate between) is shared by all of them: calls
  * on one handle must be ordered on one stream (or by events) -- two streams need two handles.
+ * Launch size: every count of units a call takes (subframes, frames, frames x channels, rows) is at most 2^31 - 1;
+ * flacenc_hip_encode_[pack_]stereo_frames count four candidate subframes per frame, so at most (2^31 - 1) / 4
+ * frames; flacenc_hip_fill_le_bytes takes at most 65535 frames per call (a grid dimension).  More is
+ * FLACENC_HIP_ERR_BAD_ARGUMENT with nothing written.  Strides, offsets and buffer sizes are size_t / uint64_t, so
+ * rows, records, frame bytes and table offsets may lie beyond 2^32 bytes of the pointer they are counted from.
+ * DESIGN.md, "Launch size and address range", lists which entry points the test suite holds there, at which
+ * sizes (2^31 / 2^32 bytes, 2^31 / 2^32 elements), and which it does not.
  * Errors never unwind across this boundary: every call returns an int status
  * (0 = OK, negative = error) and per-subframe `status` fields carry the
  * conditions on which the reference would panic.
@@ -812,6 +819,9 @@ int flacenc_hip_allgather_records_async(flacenc_hip_handle* h, const void* local
  * to frames + (f*channels + c)*stride, zero-filled beyond total_samples (the short last block).
  * Uploading packed 16- / 24-bit PCM and widening here halves (or better) the PCIe traffic of the
  * host-pointer paths; the MD5 of the input stays with the caller (src/source.rs:406-428).
+ * At most 65535 frames per call (one grid row per frame): 65536 and more are FLACENC_HIP_ERR_BAD_ARGUMENT and
+ * nothing is written; a longer stream is filled in runs.  `bytes` and `frames` may be of any size (8 channels x
+ * 4 bytes x 65535 frames of 4096 samples are 8.6 GB in and out).
  */
 int flacenc_hip_fill_le_bytes(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t total_samples,
                               uint32_t channels, uint32_t bytes_per_sample, size_t n_frames, uint32_t block_size,
