@@ -40,28 +40,10 @@ __global__ void bitcount_pick_kernel(const unsigned long long* keys, uint32_t n,
 
 namespace flacenc_hip {
 
-// FLACENC_HIP_FLAG_WINDOW_SEARCH with no extra window is exactly the call with the summation-order flag in its place
-// (with FLACENC_HIP_FLAG_ORDER_SEARCH: the ORDER_SEARCH call; with FLACENC_HIP_FLAG_ORDER_GUESS: the ORDER_GUESS call),
-// and so is FLACENC_HIP_FLAG_PRECISION_SEARCH with the handle's floor at or above the config's quant_precision.
-// Callers of the flagged entry points run their config through this once, after flacenc_hip_verify_config.
-uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags, uint32_t quant_precision) {
-  const uint32_t dropped =
-      (((flags & FLACENC_HIP_FLAG_WINDOW_SEARCH) && h->lpc_windows.empty()) ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u) |
-      (((flags & FLACENC_HIP_FLAG_PRECISION_SEARCH) && h->precision_floor >= quant_precision)
-           ? FLACENC_HIP_FLAG_PRECISION_SEARCH : 0u);
-  if (!dropped) return flags;
-  flags &= ~dropped;
-  if (lpc_search(flags)) return flags;
-  flags &= ~(FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER | FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY);
-  if (!(flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER)) flags |= FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER;
-  return flags;
-}
-
-// The LPC candidate of a (normalised) config comes from the search over windows and orders (order_search.h): the frame
-// -level calls then take the candidate batches and the stand-alone deciding kernels for every shape.
-bool lpc_search(uint32_t flags) {
-  return (flags & (FLACENC_HIP_FLAG_ORDER_SEARCH | FLACENC_HIP_FLAG_WINDOW_SEARCH | FLACENC_HIP_FLAG_ORDER_GUESS |
-                   FLACENC_HIP_FLAG_PRECISION_SEARCH)) != 0;
+int check_bits_per_sample(flacenc_hip_handle* h, uint32_t bits_per_sample) {
+  if (bits_per_sample >= 8 && bits_per_sample <= 24) return FLACENC_HIP_OK;
+  h->last_error = "bits_per_sample must be in 8..=24";
+  return FLACENC_HIP_ERR_BAD_ARGUMENT;
 }
 
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
@@ -103,98 +85,58 @@ int check_candidate_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_con
   }
   return FLACENC_HIP_OK;
 }
-
-// QlpcKernelArgs::reference_order: 0 = the kernels' canonical sums, 1 = the stable build's orders
-// (FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER), 2 = the simd-nightly build's (FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER)
-uint32_t sum_order_mode(uint32_t flags) {
-  if (flags & FLACENC_HIP_FLAG_NIGHTLY_SUM_ORDER) return 2u;
-  return (flags & FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER) ? 1u : 0u;
-}
-
-// The unflagged order on the fused kernel's shapes is certified (QlpcKernelArgs::certify; launch_qlpc decides where it
-// applies).  Launches that cannot run it inside the fused kernel -- unaligned rows, FLACENC_HIP_FLAG_GENERIC_KERNEL, the
-// fused bit writer -- take the reference's R[] from acorr_reference_kernel through the split scratch.
-void set_certify(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, uint32_t flags) {
-  a.certify = (flags & FLACENC_HIP_FLAG_CANONICAL_SUM_ORDER) ? 0u : 1u;
-  // REFERENCE_SUM_ORDER | INTEGER_PARITY_ONLY: the certified shapes keep their own order (launch_qlpc)
-  a.integer_parity_only = ((flags & FLACENC_HIP_FLAG_INTEGER_PARITY_ONLY) && (flags & FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER)) ? 1u : 0u;
-  a.cert_stats = h->cert_stats;
-}
 }  // namespace
-
-bool certify_needs_scratch(const flacenc_hip::QlpcKernelArgs& a) {
-  return a.certify != 0u && flacenc_hip::cert_shape(a) && (a.reference_order == 0u || a.integer_parity_only) &&
-         !a.direct_mse && a.fixed_mode == 0 && (!flacenc_hip::wave_kernel_eligible(a) || a.pack_out != nullptr);
-}
 
 QlpcKernelArgs base_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, const WindowEntry* win,
                          const int32_t* samples, size_t stride, uint32_t block_size, size_t n_subframes,
                          const uint8_t* bps, uint32_t bps_uniform, bool stereo) {
-  QlpcKernelArgs a;
-  a.samples = samples;
-  a.stride = stride;
-  a.block_size = block_size;
-  a.n_subframes = static_cast<uint32_t>(n_subframes);
-  a.bps = bps;
-  a.bps_uniform = bps_uniform;
-  a.stereo = stereo ? 1u : 0u;
+  QlpcKernelArgs a = config_record(q, samples, stride, block_size, n_subframes, bps, bps_uniform, stereo);
   if (win) {
     a.window = win->dev;
     a.window_lanes = win->dev_lanes;
     a.flat_lo = win->flat_lo;
     a.flat_hi = win->flat_hi;
   }
-  a.lpc_order = q.lpc_order;
-  a.precision = q.quant_precision;
-  a.max_rice_parameter = q.max_rice_parameter;
-  a.rice_finest_only = (q.flags & FLACENC_HIP_FLAG_FINEST_RICE_ORDER) ? 1u : 0u;
-  a.force_generic = (q.flags & FLACENC_HIP_FLAG_GENERIC_KERNEL) ? 1u : 0u;
-  a.reference_order = sum_order_mode(q.flags);
-  set_certify(h, a, q.flags);
-  a.direct_mse = q.use_direct_mse ? 1u : 0u;  // (enqueue adds mae_steps and the scratch; elsewhere it keeps the launch off the fused wave kernel)
+  a.cert_stats = h->cert_stats;
   return a;
 }
 
-int lpc_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, bool with_minmax, LpcScratch* out) {
+int candidate_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, bool lpc, bool fixed, bool with_minmax,
+                      Candidates* out) {
+  const size_t records = n_rows * sizeof(flacenc_hip_subframe_params), rows = n_rows * padded_stride(block_size) * 4;
   int rc;
-  if ((rc = ensure(h, h->d_cparams, n_rows * sizeof(flacenc_hip_subframe_params))) != FLACENC_HIP_OK) return rc;
-  if ((rc = ensure(h, h->d_cresid, n_rows * padded_stride(block_size) * 4)) != FLACENC_HIP_OK) return rc;
-  if (with_minmax && (rc = ensure(h, h->d_minmax, n_rows * 2 * sizeof(int32_t))) != FLACENC_HIP_OK) return rc;
-  out->params = static_cast<flacenc_hip_subframe_params*>(h->d_cparams.ptr);
-  out->rows = static_cast<int32_t*>(h->d_cresid.ptr);
-  out->minmax = with_minmax ? static_cast<int32_t*>(h->d_minmax.ptr) : nullptr;
+  if (lpc) {
+    if ((rc = ensure(h, h->d_cparams, records)) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_cresid, rows)) != FLACENC_HIP_OK) return rc;
+    if (with_minmax && (rc = ensure(h, h->d_minmax, n_rows * 2 * sizeof(int32_t))) != FLACENC_HIP_OK) return rc;
+    out->lpc_params = static_cast<flacenc_hip_subframe_params*>(h->d_cparams.ptr);
+    out->lpc_residual = static_cast<int32_t*>(h->d_cresid.ptr);
+    out->minmax = with_minmax ? static_cast<int32_t*>(h->d_minmax.ptr) : nullptr;
+  }
+  if (fixed) {
+    if ((rc = ensure(h, h->d_fparams, records)) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_fresid, rows)) != FLACENC_HIP_OK) return rc;
+    if ((rc = ensure(h, h->d_fkeys, n_rows * 8)) != FLACENC_HIP_OK) return rc;
+    out->fixed_params = static_cast<flacenc_hip_subframe_params*>(h->d_fparams.ptr);
+    out->fixed_residual = static_cast<int32_t*>(h->d_fresid.ptr);
+    out->fixed_keys = static_cast<unsigned long long*>(h->d_fkeys.ptr);
+  }
   return FLACENC_HIP_OK;
 }
 
-int fixed_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, FixedScratch* out) {
+// What scratch_grant gives a record.  The split scratch: R[] and the predictor records between the launches of the split
+// pipelines, and the counter through which bigblock_residual_kernel tells the clean-up launch whether it marked anything
+// (QlpcKernelArgs::marked_count).  The pipeline's own counter is cleared on its stream here: a pipeline that attached this
+// scratch but had no clean-up launch behind it (the fused 4096 / 4608 kernels, for one) leaves its count and list entries
+// in the other slot, and the pipeline after the next one would otherwise start from them and visit records twice.
+int attach_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, ScratchGrant grant, hipStream_t stream) {
   int rc;
-  if ((rc = ensure(h, h->d_fparams, n_rows * sizeof(flacenc_hip_subframe_params))) != FLACENC_HIP_OK) return rc;
-  if ((rc = ensure(h, h->d_fresid, n_rows * padded_stride(block_size) * 4)) != FLACENC_HIP_OK) return rc;
-  if ((rc = ensure(h, h->d_fkeys, n_rows * 8)) != FLACENC_HIP_OK) return rc;
-  out->params = static_cast<flacenc_hip_subframe_params*>(h->d_fparams.ptr);
-  out->rows = static_cast<int32_t*>(h->d_fresid.ptr);
-  out->keys = static_cast<unsigned long long*>(h->d_fkeys.ptr);
-  return FLACENC_HIP_OK;
-}
-
-// FLACENC_HIP_FLAG_REFERENCE_SUM_ORDER with the ApproxEnt selector: room for sumabs_reference_kernel's
-// per-partition f32 sums (launch_qlpc runs it when `sumabs_scratch` is set)
-int attach_sumabs_scratch(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, bool approx_ent) {
-  if (!a.reference_order || !approx_ent) return FLACENC_HIP_OK;
-  int rc = ensure(h, h->d_sumabs, static_cast<size_t>(a.n_subframes) * 5 * 64 * sizeof(float));
-  if (rc != FLACENC_HIP_OK) return rc;
-  a.sumabs_scratch = static_cast<float*>(h->d_sumabs.ptr);
-  return FLACENC_HIP_OK;
-}
-
-// R[] and the predictor records between the launches of the split pipelines, and the counter through which
-// bigblock_residual_kernel tells the clean-up launch whether it marked anything (QlpcKernelArgs::marked_count).
-// The pipeline's own counter is cleared on its stream here: a pipeline that attached this scratch but had no clean-up
-// launch behind it (the fused 4096 / 4608 kernels, for one) leaves its count and list entries in the other slot, and
-// the pipeline after the next one would otherwise start from them and visit records twice.
-int attach_split_scratch(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, void* stream) {
-  int rc = ensure(h, h->d_split, static_cast<size_t>(a.n_subframes) * (33 * 8 + 36 * 4));
-  if (rc != FLACENC_HIP_OK) return rc;
+  if (grant.sumabs) {  // (launch_qlpc runs sumabs_reference_kernel when `sumabs_scratch` is set)
+    if ((rc = ensure(h, h->d_sumabs, static_cast<size_t>(a.n_subframes) * 5 * 64 * sizeof(float))) != FLACENC_HIP_OK) return rc;
+    a.sumabs_scratch = static_cast<float*>(h->d_sumabs.ptr);
+  }
+  if (!grant.split) return FLACENC_HIP_OK;
+  if ((rc = ensure(h, h->d_split, static_cast<size_t>(a.n_subframes) * (33 * 8 + 36 * 4))) != FLACENC_HIP_OK) return rc;
   a.split_scratch = h->d_split.ptr;
   // two counters (16 words reserved) + a list of the first kMarkedCap marks behind each
   constexpr uint32_t kMarkedCap = 1024;
@@ -209,103 +151,39 @@ int attach_split_scratch(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, 
   a.marked_list = static_cast<uint32_t*>(h->d_marked.ptr) + 16 + h->marked_parity * kMarkedCap;
   a.marked_cap = kMarkedCap;
   a.marked_unit = 1;
-  HIP_TRY(h, hipMemsetAsync(a.marked_count, 0, 4, static_cast<hipStream_t>(stream)));
+  HIP_TRY(h, hipMemsetAsync(a.marked_count, 0, 4, stream));
   return FLACENC_HIP_OK;
 }
 
-namespace {
-// The certified shapes (blocks of 4096 / 4608 samples at orders up to 12) by material.  The fused kernel settles a
-// subframe's order certificate in its first tier for next to nothing; the second tier and the recomputation from the
-// reference's chains are serial work of one wave while its workgroup waits -- rare on noise-like material (2 subframes in
-// 393 216 of the bench signal), the rule on music (the reference's real-audio fixtures: 26 % / 82 % / 100 % of the
-// subframes at orders 8 / 10 / 12 count as unsettled, 220 / 146 / 100 G samples/s where the bench signal runs at 350).  Two passes -- the
-// reference's chains on the matrix cores for every subframe, then the fused kernel on their R[] -- give the SAME integers
-// at a flat 1.4 x the certified kernel's best time.  So launches that return integers only (no R[], no coefficients: their
-// bits depend on the pass that produced them) watch the certificate's counters and take the two-pass form while the
-// material they were last given was hard: above kHardShare of the subframes unsettled by the first tier, for a span of
-// launches that doubles (8 .. 64) while the probes between the spans keep finding it so.
-constexpr double kHardShare = 0.10;
-// a verdict is taken from at least this many subframes (counters of smaller launches add up until they are), a probe's from
-// at least kProbeMinSubframes; launches of 2^25 subframes and more are not watched (the verdict's fields are 26 bits wide)
-constexpr uint32_t kFeedbackMinSubframes = 4096, kProbeMinSubframes = 1024, kFeedbackMaxSubframes = 1u << 25;
-inline uint32_t next_seq(uint32_t seq) { return ((seq + 1u) & 0xFFFu) ? ((seq + 1u) & 0xFFFu) : 1u; }  // (0: the word's initial state)
-}  // namespace
-
-int launch_adaptive(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, const flacenc_hip::QlpcLaunchPlan& plan,
-                    hipStream_t stream) {
-  const bool fused_certified = flacenc_hip::plan_qlpc_route(a).order == flacenc_hip::QlpcRoute::kCertifiedFused;
-  const bool watch = fused_certified && h->adaptive_order != 0 && h->cert_stats == nullptr && a.autocorr == nullptr &&
-                     a.lpc_coefs == nullptr && a.n_subframes < kFeedbackMaxSubframes;
-  if (!watch) {
-    HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-    return FLACENC_HIP_OK;
-  }
-  if (h->d_cert_fb == nullptr) {
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_cert_fb), 16));
-    HIP_TRY(h, hipMemset(h->d_cert_fb, 0, 16));
-    HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_cert_fb), 8, hipHostMallocMapped));
-    *h->h_cert_fb = 0ull;
-  }
-  // The latest verdict that has landed (a plain read of the pinned word: late is fine, torn it cannot be).  The host may
-  // run many launches ahead of the device, so nothing is concluded from launches whose counters are not in: on easy
-  // material every launch carries the counters and any new verdict counts; on hard material a span of two-pass launches
-  // is followed by ONE probe (a certified launch), and the launches behind the probe stay two-pass until ITS verdict is in.
-  const unsigned long long word = *reinterpret_cast<volatile unsigned long long*>(h->h_cert_fb);
-  const uint32_t l_seq = static_cast<uint32_t>(word >> 52), l_hard = static_cast<uint32_t>(word >> 26) & 0x3FFFFFFu,
-                 l_an = static_cast<uint32_t>(word) & 0x3FFFFFFu;
-  const bool is_hard = l_an != 0u && static_cast<double>(l_hard) > kHardShare * static_cast<double>(l_an);
-  bool two_pass;
-  if (h->two_pass_span == 0) {  // easy so far
-    if (l_seq != h->fb_seen_seq) {
-      h->fb_seen_seq = l_seq;
-      if (is_hard) h->two_pass_left = h->two_pass_span = 8;
+// The order mode of the certified shapes (order_mode_core.h has the rule and its reasons): the HIP calls around its step
+int launch_adaptive(flacenc_hip_handle* h, const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, hipStream_t stream) {
+  flacenc_hip_handle::OrderMode& om = h->adaptive;
+  order_mode::Step st{false, false, 0u};
+  if (plan_qlpc_route(a).order == QlpcRoute::kCertifiedFused && om.enabled != 0 && h->cert_stats == nullptr &&
+      a.autocorr == nullptr && a.lpc_coefs == nullptr && a.n_subframes < order_mode::kFeedbackMaxSubframes) {
+    if (om.d_counters == nullptr) {
+      HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&om.d_counters), 16));
+      HIP_TRY(h, hipMemset(om.d_counters, 0, 16));
+      HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&om.verdict), 8, hipHostMallocMapped));
+      *om.verdict = 0ull;
     }
-    two_pass = h->two_pass_span != 0;
-  } else if (h->two_pass_left > 0) {
-    two_pass = true;
-  } else if (!h->fb_probe_out) {
-    two_pass = false;  // the probe: certified launches until kProbeMinSubframes have been counted
-    h->fb_probe_out = true;
-    h->fb_probe_seq = 0u;  // (assigned when its feedback goes out)
-  } else if (h->fb_probe_seq == 0u) {
-    two_pass = false;  // the probe is still collecting
-  } else if (l_seq != h->fb_probe_seq) {
-    two_pass = true;  // the probe's verdict is not in yet
-  } else {
-    h->fb_probe_out = false;
-    h->fb_seen_seq = l_seq;
-    if (is_hard) {
-      h->two_pass_span = h->two_pass_span >= 64 ? 64 : 2 * h->two_pass_span;
-      h->two_pass_left = h->two_pass_span;
-      two_pass = true;
-    } else {
-      h->two_pass_span = 0;
-      two_pass = false;
-    }
+    // (the latest verdict that has landed, a plain read of the pinned word: late is fine, torn it cannot be)
+    st = order_mode::step(om.state, *reinterpret_cast<volatile unsigned long long*>(om.verdict), a.n_subframes);
   }
-  if (two_pass) {
-    if (h->two_pass_left > 0) --h->two_pass_left;
-    flacenc_hip::QlpcKernelArgs b = a;
+  QlpcKernelArgs b = a;
+  if (st.two_pass) {
     b.certify = 0;
     b.reference_order = 1u;  // (the autocorrelation alone: the selector's sums follow sumabs_scratch, which the flags decide)
-    if (b.split_scratch == nullptr) {
-      int rc = attach_split_scratch(h, b, stream);
-      if (rc != FLACENC_HIP_OK) return rc;
-    }
-    HIP_TRY(h, flacenc_hip::launch_qlpc(b, plan, stream));
-    return FLACENC_HIP_OK;
+    int rc;  // (lazily: certified launches, the rule, never pay for the split scratch)
+    if (b.split_scratch == nullptr && (rc = attach_scratch(h, b, {true, false}, stream)) != FLACENC_HIP_OK) return rc;
+  } else if (st.carry) {
+    b.cert_stats = om.d_counters;
   }
-  a.cert_stats = h->d_cert_fb;
-  HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-  h->fb_pending += a.n_subframes;
-  const bool probing = h->fb_probe_out && h->fb_probe_seq == 0u;
-  if (h->fb_pending >= (probing ? kProbeMinSubframes : kFeedbackMinSubframes)) {
-    h->fb_pending = 0;
-    h->fb_seq = next_seq(h->fb_seq);
-    if (probing) h->fb_probe_seq = h->fb_seq;
+  HIP_TRY(h, launch_qlpc(b, plan, stream));
+  if (st.feedback != 0u) {
     unsigned long long* out = nullptr;
-    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&out), h->h_cert_fb, 0));
-    hipLaunchKernelGGL(cert_feedback_kernel, dim3(1), dim3(1), 0, stream, h->d_cert_fb, out, h->fb_seq);
+    HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&out), om.verdict, 0));
+    hipLaunchKernelGGL(cert_feedback_kernel, dim3(1), dim3(1), 0, stream, om.d_counters, out, st.feedback);
     HIP_TRY(h, hipGetLastError());
   }
   return FLACENC_HIP_OK;
@@ -313,15 +191,13 @@ int launch_adaptive(flacenc_hip_handle* h, flacenc_hip::QlpcKernelArgs& a, const
 
 // FLACENC_HIP_FLAG_RICE_ESCAPE: the post-pass over the records and rows a candidate batch has just enqueued
 // (rice_escape.cpp)
-int enqueue_rice_escape(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, flacenc_hip_subframe_params* params,
-                        const int32_t* residual, size_t residual_stride, size_t n_subframes, uint32_t block_size,
-                        hipStream_t stream) {
+int enqueue_rice_escape(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, const CandidateBatch& b, hipStream_t stream) {
   flacenc_hip::RiceEscapeArgs e{};
-  e.params = params;
-  e.residual = residual;
-  e.residual_stride = residual_stride;
-  e.block_size = block_size;
-  e.n_rows = static_cast<uint32_t>(n_subframes);
+  e.params = b.params;
+  e.residual = b.residual;
+  e.residual_stride = b.residual_stride;
+  e.block_size = b.block_size;
+  e.n_rows = static_cast<uint32_t>(b.n_subframes);
   e.max_rice_parameter = q.max_rice_parameter;
   e.finest_only = (q.flags & FLACENC_HIP_FLAG_FINEST_RICE_ORDER) ? 1u : 0u;
   HIP_TRY(h, flacenc_hip::launch_rice_escape(e, stream));
@@ -329,31 +205,44 @@ int enqueue_rice_escape(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q,
 }
 
 namespace {
-int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
-                size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
-                flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
-                double* autocorr, double* lpc_coefs, hipStream_t stream, bool stereo, uint32_t bps_uniform,
-                int32_t* residual_lr, size_t residual_lr_stride, int32_t* minmax_out, bool* placed,
-                uint32_t residual_mode) {
-  if (placed) *placed = false;
+// What both batches start from: the launch plan at `order`, checked against the LDS; base_args with the batch's rows and
+// outputs; the bit tables' scratch of blocks above 16384 samples
+int batch_record(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, const WindowEntry* win, uint32_t order,
+                 const CandidateBatch& b, QlpcLaunchPlan* plan, QlpcKernelArgs* out) {
+  *plan = plan_qlpc_launch(b.block_size, order);
+  if (plan->smem_bytes > 160 * 1024) {
+    h->last_error = "internal: LDS plan exceeds 160 KiB";
+    return FLACENC_HIP_ERR_UNSUPPORTED;
+  }
+  QlpcKernelArgs a = base_args(h, q, win, b.samples, b.stride, b.block_size, b.n_subframes, b.bps, b.bps_uniform, b.stereo);
+  a.params = b.params;
+  a.residual = b.residual;
+  a.residual_stride = b.residual_stride;
+  if (plan->table_scratch_bytes_per_subframe) {
+    int rc = ensure(h, h->d_tables, plan->table_scratch_bytes_per_subframe * b.n_subframes);
+    if (rc != FLACENC_HIP_OK) return rc;
+    a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
+  }
+  *out = a;
+  return FLACENC_HIP_OK;
+}
+
+int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, CandidateBatch& b, hipStream_t stream) {
+  b.placed = false;
+  const uint32_t block_size = b.block_size;
+  const size_t n_subframes = b.n_subframes;
   flacenc_hip_qlpc_config qcfg = *cfg;
-  qcfg.flags = search_flags(h, cfg->flags, cfg->quant_precision);
+  qcfg.flags = search_flags(!h->lpc_windows.empty(), h->precision_floor, cfg->flags, cfg->quant_precision);
   cfg = &qcfg;
   const WindowEntry* win = nullptr;
   int rc = get_window(h, cfg, block_size, &win);
   if (rc != FLACENC_HIP_OK) return rc;
   const float* const win_dev = win->dev;  // (get_window_entry may grow h->windows below)
-  flacenc_hip::QlpcLaunchPlan plan = flacenc_hip::plan_qlpc_launch(block_size, cfg->lpc_order);
-  if (plan.smem_bytes > 160 * 1024) {
-    h->last_error = "internal: LDS plan exceeds 160 KiB";
-    return FLACENC_HIP_ERR_UNSUPPORTED;
-  }
-  QlpcKernelArgs a = base_args(h, *cfg, win, samples, stride, block_size, n_subframes, bps, bps_uniform, stereo);
-  a.params = params;
-  a.residual = residual;
-  a.residual_stride = residual_stride;
-  a.autocorr = autocorr;
-  a.lpc_coefs = lpc_coefs;
+  QlpcLaunchPlan plan;
+  QlpcKernelArgs a;
+  if ((rc = batch_record(h, *cfg, win, cfg->lpc_order, b, &plan, &a)) != FLACENC_HIP_OK) return rc;
+  a.autocorr = b.autocorr;
+  a.lpc_coefs = b.lpc_coefs;
   a.stamps = h->stamps;
   a.mae_steps = cfg->use_direct_mse ? cfg->mae_optimization_steps : 0u;  // (ignored without it, coding.rs:337-347)
   if (a.direct_mse && flacenc_hip::direct_mse_lds_bytes(block_size, a.mae_steps > 0, cfg->lpc_order) > 160 * 1024) {
@@ -374,19 +263,8 @@ int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const
     if (rc != FLACENC_HIP_OK) return rc;
     a.irls_weight_scratch = static_cast<float*>(h->d_irlsw.ptr);
   }
-  // (R[] and the predictor records between the launches of the split pipelines: orders from 13, and blocks of
-  // 8192 / 16384 at any order -- the big-block kernels)
-  // (... and, round 6, every unflagged launch: the reference's chains go in front of whatever kernel takes the shape)
   const bool order_search = lpc_search(cfg->flags);
-  if (cfg->lpc_order >= 13 || a.reference_order || a.direct_mse || block_size == 8192 || block_size == 16384 ||
-      flacenc_hip::subwave_shape(block_size) || a.certify != 0u || order_search) {
-    if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
-  }
-  if (plan.table_scratch_bytes_per_subframe) {
-    rc = ensure(h, h->d_tables, plan.table_scratch_bytes_per_subframe * n_subframes);
-    if (rc != FLACENC_HIP_OK) return rc;
-    a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
-  }
+  if ((rc = attach_scratch(h, a, scratch_grant(a, LaunchKind::kLpcBatch, order_search), stream)) != FLACENC_HIP_OK) return rc;
   if (order_search) {
     // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH (DESIGN.md 4.10, 4.11, 4.13,
     // 4.16): R[] of every window in the stable build's order (nightly's with its flag; the certificate and
@@ -418,49 +296,36 @@ int enqueue_lpc(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const
                                                 stream, &h->last_search_slices));
     return FLACENC_HIP_OK;
   }
-  // frame-level callers on the big-block shapes: L / R candidates straight into the output rows, role min / max
-  // from the residual kernel (only bigblock_residual_kernel knows how; see QlpcKernelArgs::residual_lr)
-  if (stereo && residual_lr != nullptr && minmax_out != nullptr &&
-      (reinterpret_cast<uintptr_t>(residual_lr) & 15) == 0 && (residual_lr_stride & 3) == 0 &&
-      (flacenc_hip::bigblock_eligible(a) || (a.direct_mse && flacenc_hip::bigblock_shape_eligible(a)))) {
-    a.residual_lr = residual_lr;
-    a.residual_lr_stride = residual_lr_stride;
-    a.minmax_out = minmax_out;
-    if (placed) *placed = true;
-  }
-  // ... or, with residual_mode 1, no rows at all: records and the roles' min / max only (the deciding store pass,
-  // bigblock_residual_kernel's mode 2, produces the two rows the frame keeps)
-  if (stereo && residual_mode == 1u && minmax_out != nullptr &&
-      (flacenc_hip::bigblock_eligible(a) || (a.direct_mse && flacenc_hip::bigblock_shape_eligible(a)))) {
-    a.residual_mode = 1u;
-    a.minmax_out = minmax_out;
-    if (placed) *placed = true;
+  // frame-level callers on the big-block shapes (only bigblock_residual_kernel knows how) ...
+  if (b.stereo && b.minmax_out != nullptr && (bigblock_eligible(a) || (a.direct_mse && bigblock_shape_eligible(a)))) {
+    if (b.analyse_only) {
+      // ... no rows at all: records and the roles' min / max only (the deciding store pass, bigblock_residual_kernel's
+      // mode 2, produces the two rows the frame keeps)
+      a.residual_mode = 1u;
+      b.placed = true;
+    } else if (b.residual_lr != nullptr && (reinterpret_cast<uintptr_t>(b.residual_lr) & 15) == 0 && (b.residual_lr_stride & 3) == 0) {
+      // ... L / R candidates straight into the output rows, role min / max from the residual kernel
+      a.residual_lr = b.residual_lr;
+      a.residual_lr_stride = b.residual_lr_stride;
+      b.placed = true;
+    }
+    if (b.placed) a.minmax_out = b.minmax_out;
   }
   return launch_adaptive(h, a, plan, stream);
 }
 }  // namespace
 
 // The one exit of the LPC candidates.  Under FLACENC_HIP_FLAG_RICE_ESCAPE every record and row goes to `params` /
-// `residual` (no rows placed in the caller's frame, no analyse-only launch) and the escape pass runs behind them -- on
-// the winner's record where a search flag chose one.
-int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
-            size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
-            flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
-            double* autocorr, double* lpc_coefs, hipStream_t stream, bool stereo, uint32_t bps_uniform,
-            int32_t* residual_lr, size_t residual_lr_stride, int32_t* minmax_out, bool* placed,
-            uint32_t residual_mode) {
-  if (!(cfg->flags & FLACENC_HIP_FLAG_RICE_ESCAPE))
-    return enqueue_lpc(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual, residual_stride, autocorr,
-                       lpc_coefs, stream, stereo, bps_uniform, residual_lr, residual_lr_stride, minmax_out, placed,
-                       residual_mode);
-  if (residual_mode != 0u) {
-    h->last_error = "internal: analyse-only QLPC batch under FLACENC_HIP_FLAG_RICE_ESCAPE";
-    return FLACENC_HIP_ERR_UNSUPPORTED;
-  }
-  int rc = enqueue_lpc(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual, residual_stride, autocorr,
-                       lpc_coefs, stream, stereo, bps_uniform, nullptr, 0, nullptr, placed, 0u);
+// `residual` (no rows placed in the caller's frame; plan_frame_call asks for no analyse-only launch) and the escape pass
+// runs behind them -- on the winner's record where a search flag chose one.
+int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, CandidateBatch& b, hipStream_t stream) {
+  if (!(cfg->flags & FLACENC_HIP_FLAG_RICE_ESCAPE)) return enqueue_lpc(h, cfg, b, stream);
+  b.placed = false;
+  CandidateBatch plain = b;
+  plain.residual_lr = plain.minmax_out = nullptr;
+  int rc = enqueue_lpc(h, cfg, plain, stream);
   if (rc != FLACENC_HIP_OK) return rc;
-  return enqueue_rice_escape(h, *cfg, params, residual, residual_stride, n_subframes, block_size, stream);
+  return enqueue_rice_escape(h, *cfg, b, stream);
 }
 
 // config::Fixed::verify (config.rs:246-255) + OrderSel::verify (:419-431)
@@ -477,61 +342,26 @@ int verify_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg) {
 }
 
 // `fixed_lpc` (coding.rs:298-331) for a batch, device pointers, on `stream`
-int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* samples,
-                  size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps,
-                  uint32_t bps_uniform, bool stereo, flacenc_hip_subframe_params* params, int32_t* residual,
-                  size_t residual_stride, unsigned long long* selector_keys, hipStream_t stream,
-                  uint32_t residual_mode) {
+int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, CandidateBatch& b, hipStream_t stream) {
   int rc = verify_fixed(h, cfg);
   if (rc != FLACENC_HIP_OK) return rc;
+  const size_t n_subframes = b.n_subframes;
   // FLACENC_HIP_FLAG_RICE_ESCAPE: the pass runs on the selected order's record; the selector's keys (and BitCount's
-  // comparison of unescaped code_bits) are what they are without the flag
-  auto escape = [&](int done) -> int {
-    if (done != FLACENC_HIP_OK || !(cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE)) return done;
-    return enqueue_rice_escape(h, cfg->qlpc, params, residual, residual_stride, n_subframes, block_size, stream);
+  // comparison of unescaped code_bits) are what they are without the flag.  (plan_frame_call: never analyse-only.)
+  auto escape = [&]() -> int {
+    return (cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE) ? enqueue_rice_escape(h, cfg->qlpc, b, stream) : FLACENC_HIP_OK;
   };
-  if ((cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE) && residual_mode != 0u) {
-    h->last_error = "internal: analyse-only fixed_lpc batch under FLACENC_HIP_FLAG_RICE_ESCAPE";
-    return FLACENC_HIP_ERR_UNSUPPORTED;
-  }
-  flacenc_hip::QlpcLaunchPlan plan = flacenc_hip::plan_qlpc_launch(block_size, 4);
-  if (plan.smem_bytes > 160 * 1024) {
-    h->last_error = "internal: LDS plan exceeds 160 KiB";
-    return FLACENC_HIP_ERR_UNSUPPORTED;
-  }
-  QlpcKernelArgs a = base_args(h, cfg->qlpc, nullptr, samples, stride, block_size, n_subframes, bps, bps_uniform, stereo);
-  a.lpc_order = 4;  // (no window, no quantisation: the fixed predictors)
-  a.precision = 0;
-  a.params = params;
-  a.residual = residual;
-  a.residual_stride = residual_stride;
-  a.use_fixed = 1;
-  a.fixed_max_order = cfg->fixed_max_order;
-  a.fixed_order_sel = cfg->fixed_order_sel;
+  QlpcLaunchPlan plan;
+  QlpcKernelArgs a;
+  if ((rc = batch_record(h, cfg->qlpc, nullptr, 4, b, &plan, &a)) != FLACENC_HIP_OK) return rc;
+  fixed_batch_fields(a, *cfg);
   a.fixed_keys = h->fixed_keys;
-  a.fixed_partitions = cfg->fixed_partitions;
-  a.selector_keys = selector_keys;
-  if (plan.table_scratch_bytes_per_subframe) {
-    rc = ensure(h, h->d_tables, plan.table_scratch_bytes_per_subframe * n_subframes);
-    if (rc != FLACENC_HIP_OK) return rc;
-    a.table_scratch = static_cast<uint32_t*>(h->d_tables.ptr);
-  }
-  if (cfg->fixed_order_sel == FLACENC_HIP_ORDERSEL_APPROXENT) {
-    a.fixed_mode = 1;
-    if ((rc = attach_sumabs_scratch(h, a, true)) != FLACENC_HIP_OK) return rc;
-    if (block_size == 4096 || block_size == 8192 || block_size == 16384 ||  // the big-block kernels' predictor records
-        flacenc_hip::subwave_shape(block_size)) {                            // ... the sub-wave kernel's clean-up counter
-      if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
-    }
-    if (residual_mode == 1u) {  // (the caller checked that this launch takes the big-block kernels)
-      if (!flacenc_hip::bigblock_fixed_eligible(a)) {
-        h->last_error = "internal: analyse-only fixed_lpc batch on a shape the big-block kernels do not take";
-        return FLACENC_HIP_ERR_UNSUPPORTED;
-      }
-      a.residual_mode = 1u;
-    }
+  a.selector_keys = b.selector_keys;
+  if ((rc = attach_scratch(h, a, scratch_grant(a, LaunchKind::kFixedBatch), stream)) != FLACENC_HIP_OK) return rc;
+  if (a.fixed_mode == 1) {  // ApproxEnt
+    if (b.analyse_only) a.residual_mode = 1u;  // (plan_frame_call asked bigblock_fixed_eligible of this record)
     HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-    return escape(FLACENC_HIP_OK);
+    return escape();
   }
   // BitCount: code every order, keep the first minimum of bps*order + code_bits, code it again
   const uint32_t n_orders = cfg->fixed_max_order + 1;
@@ -550,13 +380,13 @@ int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
   }
   const uint32_t n32 = static_cast<uint32_t>(n_subframes);
   hipLaunchKernelGGL(bitcount_pick_kernel, dim3((n32 + 255) / 256), dim3(256), 0, stream, keys, n32, n_orders,
-                     static_cast<uint8_t*>(h->d_sel.ptr), selector_keys);
+                     static_cast<uint8_t*>(h->d_sel.ptr), b.selector_keys);
   HIP_TRY(h, hipGetLastError());
   a.fixed_mode = 3;
   a.forced_orders = static_cast<const uint8_t*>(h->d_sel.ptr);
   a.selector_keys = nullptr;
   HIP_TRY(h, flacenc_hip::launch_qlpc(a, plan, stream));
-  return escape(FLACENC_HIP_OK);
+  return escape();
 }
 
 }  // namespace flacenc_hip
@@ -575,9 +405,11 @@ int flacenc_hip_qlpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_qlpc_c
                                       residual_stride);
   if (rc != FLACENC_HIP_OK || n_subframes == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default (null) stream
-  return enqueue(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual,
-                 residual_stride, autocorr, lpc_coefs, s);
+  CandidateBatch b(samples, n_subframes, block_size, stride, bps);
+  b.write_to(params, residual, residual_stride);
+  b.autocorr = autocorr;
+  b.lpc_coefs = lpc_coefs;
+  return enqueue(h, cfg, b, static_cast<hipStream_t>(stream));  // NULL = HIP's default (null) stream
 }
 
 int flacenc_hip_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg,
@@ -591,8 +423,8 @@ int flacenc_hip_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_config*
   if (rc != FLACENC_HIP_OK || n_subframes == 0) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
   if (memory_kind == FLACENC_HIP_MEM_DEVICE)
-    return drained(h, enqueue(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual, residual_stride,
-                              autocorr, lpc_coefs, h->stream), false);
+    return drained(h, flacenc_hip_qlpc_batch_async(h, cfg, samples, n_subframes, block_size, stride, bps, params, residual,
+                                                   residual_stride, autocorr, lpc_coefs, h->stream), false);
   if (memory_kind != FLACENC_HIP_MEM_HOST) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   // host pointers: stage through the handle's device scratch (PCIe both ways)
   const size_t dstride = padded_stride(block_size);
@@ -606,12 +438,12 @@ int flacenc_hip_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_config*
   hipStream_t s = h->stream;
   if ((rc = rows_to_device(h, h->d_samples, samples, stride, block_size, n_subframes)) != FLACENC_HIP_OK) return rc;
   if (bps) HIP_TRY(h, hipMemcpyAsync(h->d_bps.ptr, bps, n_subframes, hipMemcpyHostToDevice, s));
-  rc = enqueue(h, cfg, static_cast<const int32_t*>(h->d_samples.ptr), n_subframes, block_size, dstride,
-               bps ? static_cast<const uint8_t*>(h->d_bps.ptr) : nullptr,
-               static_cast<flacenc_hip_subframe_params*>(h->d_params.ptr),
-               static_cast<int32_t*>(h->d_residual.ptr), dstride,
-               autocorr ? static_cast<double*>(h->d_autocorr.ptr) : nullptr,
-               lpc_coefs ? static_cast<double*>(h->d_lpc.ptr) : nullptr, s);
+  rc = flacenc_hip_qlpc_batch_async(h, cfg, static_cast<const int32_t*>(h->d_samples.ptr), n_subframes, block_size, dstride,
+                                    bps ? static_cast<const uint8_t*>(h->d_bps.ptr) : nullptr,
+                                    static_cast<flacenc_hip_subframe_params*>(h->d_params.ptr),
+                                    static_cast<int32_t*>(h->d_residual.ptr), dstride,
+                                    autocorr ? static_cast<double*>(h->d_autocorr.ptr) : nullptr,
+                                    lpc_coefs ? static_cast<double*>(h->d_lpc.ptr) : nullptr, s);
   if (rc != FLACENC_HIP_OK) return rc;
   if ((rc = rows_to_host(h, residual, residual_stride, h->d_residual, block_size, n_subframes)) != FLACENC_HIP_OK) return rc;
   HIP_TRY(h, hipMemcpyAsync(params, h->d_params.ptr, n_subframes * sizeof(flacenc_hip_subframe_params),
@@ -632,14 +464,13 @@ int flacenc_hip_stereo_qlpc_batch_async(flacenc_hip_handle* h, const flacenc_hip
   int rc = check_candidate_batch_args(h, cfg, frames, n_frames * 4, block_size, stride, params, residual,
                                       residual_stride);
   if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
-  if (bits_per_sample < 8 || bits_per_sample > 24) {
-    h->last_error = "bits_per_sample must be in 8..=24";
-    return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  }
+  if ((rc = check_bits_per_sample(h, bits_per_sample)) != FLACENC_HIP_OK) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = HIP's default (null) stream
-  return enqueue(h, cfg, frames, n_frames * 4, block_size, stride, nullptr, params, residual,
-                 residual_stride, nullptr, nullptr, s, true, bits_per_sample);
+  CandidateBatch b(frames, n_frames * 4, block_size, stride);
+  b.write_to(params, residual, residual_stride);
+  b.stereo = true;
+  b.bps_uniform = bits_per_sample;
+  return enqueue(h, cfg, b, static_cast<hipStream_t>(stream));  // NULL = HIP's default (null) stream
 }
 
 int flacenc_hip_stereo_qlpc_batch(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg,
@@ -693,9 +524,12 @@ int flacenc_hip_fixed_lpc_batch_async(flacenc_hip_handle* h, const flacenc_hip_f
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   HIP_TRY(h, hipSetDevice(h->device));
-  return enqueue_fixed(h, cfg, samples, n_sub, block_size, stride, stereo ? nullptr : bps, bits_per_sample, stereo,
-                       params, residual, residual_stride, reinterpret_cast<unsigned long long*>(selector_keys),
-                       static_cast<hipStream_t>(stream));
+  CandidateBatch b(samples, n_sub, block_size, stride, stereo ? nullptr : bps);
+  b.write_to(params, residual, residual_stride);
+  b.stereo = stereo;
+  b.bps_uniform = bits_per_sample;
+  b.selector_keys = reinterpret_cast<unsigned long long*>(selector_keys);
+  return enqueue_fixed(h, cfg, b, static_cast<hipStream_t>(stream));
 }
 
 int flacenc_hip_fixed_lpc_batch(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg,

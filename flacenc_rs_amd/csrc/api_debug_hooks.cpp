@@ -38,16 +38,16 @@ int flacenc_hip_debug_set_stamps(flacenc_hip_handle* h, unsigned long long* devi
 
 int flacenc_hip_debug_set_adaptive_order(flacenc_hip_handle* h, int on) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  h->adaptive_order = on ? 1 : 0;
-  h->two_pass_left = h->two_pass_span = 0;
-  h->fb_probe_out = false;
+  h->adaptive.enabled = on ? 1 : 0;
+  h->adaptive.state.left = h->adaptive.state.span = 0;
+  h->adaptive.state.probe_out = false;
   return FLACENC_HIP_OK;
 }
 
 int flacenc_hip_debug_adaptive_state(flacenc_hip_handle* h, int* span, int* left) {
   if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  if (span) *span = h->two_pass_span;
-  if (left) *left = h->two_pass_left;
+  if (span) *span = h->adaptive.state.span;
+  if (left) *left = h->adaptive.state.left;
   return FLACENC_HIP_OK;
 }
 

@@ -1,5 +1,5 @@
 // api_frames.cpp -- encode_frame's decisions for batches of frames: Independent(channels) frames, 2-channel frames with
-// the stereo decision, FLACENC_HIP_FLAG_WASTED_BITS around both, and the encode + pack calls.
+// the stereo decision (both: check, plan_frame_call, run_frame_plan), FLACENC_HIP_FLAG_WASTED_BITS around them, encode + pack.
 #include "api_internal.h"
 #include "frame_decide.h"
 #include "wasted_bits.h"
@@ -14,125 +14,90 @@ struct PackTarget {  // optional: where the fused kernel puts the packed frames
   uint32_t* out_len = nullptr;
   uint32_t sample_rate = 0, first_frame_number = 0, frame_number_step = 1;
 };
-int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
-                              size_t n_frames, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
-                              flacenc_hip_stereo_frame_result* results, int32_t* residual, size_t residual_stride,
-                              void* stream, const PackTarget* pack, bool* packed);
+int encode_frames_common(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames, size_t n_frames,
+                         uint32_t channels, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
+                         flacenc_hip_stereo_frame_result* results, flacenc_hip_channel_result* chan_results,
+                         int32_t* residual, size_t residual_stride, void* stream, const PackTarget* pack, bool* packed);
 
-// The config a frame-level call runs with: the window search without windows and the precision search without a
-// precision below quant_precision normalised away (search_flags), and
-// too_short (coding.rs:396): neither fixed_lpc nor estimated_qlpc is tried; Constant or Verbatim
-flacenc_hip_frame_config frame_config(const flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, uint32_t block_size) {
-  flacenc_hip_frame_config c = *cfg;
-  c.qlpc.flags = search_flags(h, cfg->qlpc.flags, cfg->qlpc.quant_precision);
-  if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE) c.use_fixed = c.use_lpc = 0;
-  return c;
-}
-
-// QlpcKernelArgs::fixed_group_log2 of the fused kernels: with the ApproxEnt selector the estimator's partitions must be
-// whole groups of 64-sample lanes, 2^g lanes each.  *composite: they are not (a partition count that is no power of
-// two) and the launch takes the general path.  (`cfg` has passed verify_fixed: 1..=64 partitions.)
-uint32_t fixed_group_log2(const flacenc_hip_frame_config* cfg, bool* composite) {
-  *composite = false;
-  if (!cfg->use_fixed || cfg->fixed_order_sel != FLACENC_HIP_ORDERSEL_APPROXENT) return 0;
-  const uint32_t p = cfg->fixed_partitions;
-  *composite = (p & (p - 1)) != 0;
-  uint32_t g = 0;
-  for (uint32_t lanes = *composite ? 1u : 64u / p; lanes > 1; lanes >>= 1) ++g;
-  return g;
-}
-
-// The launch record of a frame-level call over `n_sub` rows of one width: base_args with the config's window (none
-// for a short block, which never reads it: short blocks take the candidate-free general path), the output rows and
-// encode_frame's switches.  The caller names its results (frame_results / chan_results) and, stereo, the stamps.
-int frame_args(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames, size_t n_sub,
-               uint32_t block_size, size_t stride, uint32_t bits_per_sample, bool stereo, int32_t* residual,
-               size_t residual_stride, uint32_t group_log2, QlpcKernelArgs* out) {
-  const WindowEntry* win = nullptr;
-  if (block_size >= FLACENC_HIP_MIN_BLOCK_SIZE) {
-    int rc = get_window(h, &cfg->qlpc, block_size, &win);
-    if (rc != FLACENC_HIP_OK) return rc;
+// The general path's candidates (what flacenc_hip_qlpc_batch and flacenc_hip_fixed_lpc_batch run) in handle scratch, for
+// the stereo call (with the roles' min / max), the Independent(n) call, the big-block form and the wasted-bits fix-up
+int enqueue_candidates(flacenc_hip_handle* h, const flacenc_hip_frame_config& cfg, bool lpc_batch, bool fixed_batch,
+                       const CandidateBatch& rows, hipStream_t s, Candidates* out) {
+  const size_t cstride = padded_stride(rows.block_size);
+  int rc;
+  if ((rc = candidate_scratch(h, rows.n_subframes, rows.block_size, lpc_batch, fixed_batch, rows.stereo, out)) != FLACENC_HIP_OK)
+    return rc;
+  if (lpc_batch) {
+    CandidateBatch b = rows;
+    b.write_to(out->lpc_params, out->lpc_residual, cstride);
+    b.minmax_out = out->minmax;
+    if ((rc = enqueue(h, &cfg.qlpc, b, s)) != FLACENC_HIP_OK) return rc;
+    out->placed = b.placed;
   }
-  QlpcKernelArgs a = base_args(h, cfg->qlpc, win, frames, stride, block_size, n_sub, nullptr, bits_per_sample, stereo);
-  a.residual = residual;
-  a.residual_stride = residual_stride;
-  a.use_constant = cfg->use_constant;
-  a.use_lpc = cfg->use_lpc;
-  a.use_leftside = stereo ? cfg->use_leftside : 0;
-  a.use_rightside = stereo ? cfg->use_rightside : 0;
-  a.use_midside = stereo ? cfg->use_midside : 0;
-  a.use_fixed = cfg->use_fixed;
-  a.fixed_max_order = cfg->fixed_max_order;
-  a.fixed_order_sel = cfg->fixed_order_sel;
-  a.fixed_group_log2 = group_log2;
-  a.fixed_keys = h->fixed_keys;
-  *out = a;
+  if (fixed_batch) {
+    CandidateBatch b = rows;
+    b.write_to(out->fixed_params, out->fixed_residual, cstride);
+    b.selector_keys = out->fixed_keys;
+    if ((rc = enqueue_fixed(h, &cfg, b, s)) != FLACENC_HIP_OK) return rc;
+  }
   return FLACENC_HIP_OK;
 }
-
+// (the deciding kernels' records -- FrameDecideArgs, ChannelDecideArgs, WastedArgs -- name the candidates alike)
+template <typename Decide>
+void name_candidates(Decide& d, const Candidates& c) {
+  d.lpc_params = c.lpc_params;
+  d.lpc_residual = c.lpc_residual;
+  d.fixed_params = c.fixed_params;
+  d.fixed_residual = c.fixed_residual;
+  d.fixed_keys = c.fixed_keys;
+}
 // qlpc_subwave_kernel's frame variants on blocks of 8 / 16 / 32 finest Rice partitions (512 .. 2304 samples), and the
 // clean-up of what they marked.  The kernel does the whole of encode_frame (`fd`: 2-channel frames, both candidates of
 // the four roles, the decision, the two chosen rows) resp. encode_subframe of every channel (`cd`: independent
 // channels) in one launch, several frames per workgroup.  A frame (a subframe) with a candidate beyond its exact sums
 // (residuals of 2^25 and more) comes back marked and takes the general path, restricted to what is marked: the QLPC
 // clean-up, the fixed_lpc clean-up and the deciding kernel, three launches that return at once when the count is 0.
-// Exactly one of `fd` / `cd` is given, filled but for the candidates.  *taken = false: not this kernel's launch (the
-// split scratch has been attached all the same).
-int subwave_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const QlpcKernelArgs& a,
-                   FrameDecideArgs* fd, ChannelDecideArgs* cd, hipStream_t s, bool* taken) {
-  *taken = false;
+// Exactly one of `fd` / `cd` is given, filled but for the candidates.  A plan on another path than kSubwave: the split
+// scratch is attached all the same, nothing is launched.
+int subwave_frames(flacenc_hip_handle* h, const FramePlan& p, const QlpcKernelArgs& a, FrameDecideArgs* fd,
+                   ChannelDecideArgs* cd, hipStream_t s) {
   int rc;
   QlpcKernelArgs m = a;
-  m.stamps = nullptr;
-  m.fixed_partitions = cfg->fixed_partitions;
-  // (the unflagged order on these shapes is the reference's: its chains for every QLPC candidate in front, QlpcKernelArgs::cert_subwave)
-  m.cert_subwave = (a.certify != 0u && a.reference_order == 0u && !a.direct_mse && cfg->use_lpc && cfg->qlpc.lpc_order <= 12) ? 1u : 0u;
-  if ((rc = attach_split_scratch(h, m, s)) != FLACENC_HIP_OK) return rc;
+  subwave_fields(m, p.cfg, p.cert_subwave);
+  if ((rc = attach_scratch(h, m, scratch_grant(m, LaunchKind::kSubwaveFrames), s)) != FLACENC_HIP_OK) return rc;
   m.marked_unit = fd ? 4 : 1;  // (the frame variant lists marked FRAMES; the candidate clean-ups visit their four roles)
-  if (!(fd ? subwave_frame_eligible(m) : subwave_channels_eligible(m))) return FLACENC_HIP_OK;
-  *taken = true;
-  LpcScratch lpc;
-  FixedScratch fixed{};
-  if ((rc = lpc_scratch(h, a.n_subframes, a.block_size, false, &lpc)) != FLACENC_HIP_OK) return rc;
-  m.cand_lpc_params = lpc.params;
-  if (cfg->use_fixed) {
-    if ((rc = fixed_scratch(h, a.n_subframes, a.block_size, &fixed)) != FLACENC_HIP_OK) return rc;
-    m.cand_fixed_params = fixed.params;
-  }
+  if (p.path != FramePlan::kSubwave) return FLACENC_HIP_OK;
+  Candidates cand;
+  if ((rc = candidate_scratch(h, a.n_subframes, a.block_size, true, p.cfg.use_fixed, false, &cand)) != FLACENC_HIP_OK) return rc;
+  m.cand_lpc_params = cand.lpc_params;
+  m.cand_fixed_params = cand.fixed_params;
   HIP_TRY(h, launch_subwave_frames(m, s));
   // the marked candidates, by the generic kernel's clean-up launches (status -1 in the scratch records)
   QlpcKernelArgs c = m;
   c.frame_results = nullptr;
   c.chan_results = nullptr;
   c.cand_lpc_params = c.cand_fixed_params = nullptr;
-  c.params = lpc.params;
-  c.residual = lpc.rows;
+  c.params = cand.lpc_params;
+  c.residual = cand.lpc_residual;
   c.residual_stride = padded_stride(a.block_size);
   c.only_marked = 1;
   c.use_fixed = 0;
   c.fixed_keys = nullptr;
-  HIP_TRY(h, launch_qlpc(c, plan_qlpc_launch(a.block_size, cfg->qlpc.lpc_order), s));
-  if (cfg->use_fixed) {
+  HIP_TRY(h, launch_qlpc(c, plan_qlpc_launch(a.block_size, p.cfg.qlpc.lpc_order), s));
+  if (p.cfg.use_fixed) {
     QlpcKernelArgs x = c;
-    x.params = fixed.params;
-    x.residual = fixed.rows;
-    x.selector_keys = fixed.keys;
+    x.params = cand.fixed_params;
+    x.residual = cand.fixed_residual;
+    x.selector_keys = cand.fixed_keys;
     x.window = nullptr;
     x.window_lanes = nullptr;
     x.flat_lo = x.flat_hi = 0;
-    x.lpc_order = 4;
-    x.precision = 0;
-    x.use_fixed = 1;
-    x.fixed_mode = 1;
+    fixed_batch_fields(x, p.cfg);
     HIP_TRY(h, launch_qlpc(x, plan_qlpc_launch(a.block_size, 4), s));
   }
   // (the two deciding kernels' records name the candidates and the marked list alike; entries: frames resp. subframes)
   auto marked_candidates = [&](auto& d) {
-    d.lpc_params = lpc.params;
-    d.lpc_residual = lpc.rows;
-    d.fixed_params = fixed.params;
-    d.fixed_residual = fixed.rows;
-    d.fixed_keys = fixed.keys;
+    name_candidates(d, cand);
     d.only_marked = 1;
     d.marked_count = m.marked_count;
     d.marked_list = m.marked_list;
@@ -151,26 +116,18 @@ int subwave_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, c
 // FLACENC_HIP_FLAG_WASTED_BITS for stereo frames (channels == 0) or Independent(channels) frames: scan, one host
 // synchronisation for the count m of frames with wasted bits, the unflagged pipeline unless every frame has some, then
 // the fix-up of the m frames -- their rows x >> k through the candidate batches (per-row width w - k) and a deciding
-// kernel that writes their records and residual rows over the first pass's.  Device pointers, `stream`.
+// kernel that writes their records and residual rows over the first pass's.  Device pointers, `stream`; checked arguments.
 int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames, size_t n_frames,
                   uint32_t channels, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
                   flacenc_hip_stereo_frame_result* results, flacenc_hip_channel_result* chan_results, int32_t* residual,
                   size_t residual_stride, void* stream) {
   const bool stereo = channels == 0;
   const size_t rows = stereo ? 4 : channels;
-  int rc = check_batch_args(h, &cfg->qlpc, frames, n_frames * rows, block_size, stride,
-                            stereo ? reinterpret_cast<flacenc_hip_subframe_params*>(results)
-                                   : reinterpret_cast<flacenc_hip_subframe_params*>(chan_results),
-                            residual, residual_stride, 1);
-  if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
-  if (bits_per_sample < 8 || bits_per_sample > 24) {
-    h->last_error = "bits_per_sample must be in 8..=24";
-    return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  }
-  if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
+  int rc;
   // the unflagged configuration (FUSED_PACK: a kernel choice the fix-up's packer has no part in)
   flacenc_hip_frame_config plain = *cfg;
-  plain.qlpc.flags = search_flags(h, plain.qlpc.flags, plain.qlpc.quant_precision) & ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
+  plain.qlpc.flags = search_flags(!h->lpc_windows.empty(), h->precision_floor, cfg->qlpc.flags, cfg->qlpc.quant_precision) &
+                     ~(FLACENC_HIP_FLAG_WASTED_BITS | FLACENC_HIP_FLAG_FUSED_PACK);
   HIP_TRY(h, hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if ((rc = ensure(h, h->d_wk, n_frames * rows)) != FLACENC_HIP_OK) return rc;
@@ -193,10 +150,8 @@ int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
   HIP_TRY(h, hipMemcpyAsync(&m, w.count, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(h, hipStreamSynchronize(s));
   if (m < n_frames) {  // (m = 0: exactly the unflagged launches)
-    rc = stereo ? encode_stereo_frames_impl(h, &plain, frames, n_frames, block_size, stride, bits_per_sample, results,
-                                            residual, residual_stride, stream, nullptr, nullptr)
-                : flacenc_hip_encode_frames_async(h, &plain, frames, n_frames, channels, block_size, stride,
-                                                  bits_per_sample, chan_results, residual, residual_stride, stream);
+    rc = encode_frames_common(h, &plain, frames, n_frames, channels, block_size, stride, bits_per_sample, results,
+                              chan_results, residual, residual_stride, stream, nullptr, nullptr);
     if (rc != FLACENC_HIP_OK || m == 0) return rc;
   }
   // ---- the fix-up of the m marked frames ----
@@ -220,33 +175,21 @@ int encode_wasted(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, co
   w.residual = residual;
   w.residual_stride = residual_stride;
   HIP_TRY(h, launch_wasted_shift(w, s));
-  if (plain.use_lpc) {  // estimated_qlpc of the shifted rows: what flacenc_hip_qlpc_batch runs
-    LpcScratch lpc;
-    if ((rc = lpc_scratch(h, n_rows, block_size, false, &lpc)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue(h, &plain.qlpc, w.shifted, n_rows, block_size, cstride, w.shifted_bps, lpc.params, lpc.rows, cstride,
-                 nullptr, nullptr, s);
-    if (rc != FLACENC_HIP_OK) return rc;
-    w.lpc_params = lpc.params;
-    w.lpc_residual = lpc.rows;
-  }
-  if (plain.use_fixed) {  // fixed_lpc of the shifted rows: what flacenc_hip_fixed_lpc_batch runs
-    FixedScratch fixed;
-    if ((rc = fixed_scratch(h, n_rows, block_size, &fixed)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue_fixed(h, &plain, w.shifted, n_rows, block_size, cstride, w.shifted_bps, bits_per_sample, false,
-                       fixed.params, fixed.rows, cstride, fixed.keys, s);
-    if (rc != FLACENC_HIP_OK) return rc;
-    w.fixed_params = fixed.params;
-    w.fixed_residual = fixed.rows;
-    w.fixed_keys = fixed.keys;
-  }
+  // estimated_qlpc and fixed_lpc of the shifted rows, each at its own width
+  CandidateBatch shifted(w.shifted, n_rows, block_size, cstride, w.shifted_bps);
+  Candidates cand;
+  if ((rc = enqueue_candidates(h, plain, plain.use_lpc, plain.use_fixed, shifted, s, &cand)) != FLACENC_HIP_OK) return rc;
+  name_candidates(w, cand);
   HIP_TRY(h, launch_wasted_decide(w, s));
   return FLACENC_HIP_OK;
 }
 
 // Frame::write inside the deciding wave kernel: the header constants and CRC powers of `pack` into the launch record.
-// Leaves a.pack_out null when the frame's bit buffer does not fit where the kernel keeps it.
+// The frame's bit buffer reuses the two channel images; FrameCall::pack says whether it fits there (at most 35424 bytes).
+uint32_t pack_lds_words(uint32_t block_size, uint32_t bits_per_sample) {
+  return static_cast<uint32_t>(flacenc_hip_stereo_frame_bytes_bound(block_size, bits_per_sample) / 4 + 4);
+}
 void attach_fused_pack(QlpcKernelArgs& a, const PackTarget* pack, uint32_t bits_per_sample) {
-  const size_t bound = flacenc_hip_stereo_frame_bytes_bound(a.block_size, bits_per_sample);
   FramePackArgs pa{};
   fill_header_specs(pa, a.block_size, pack->sample_rate, bits_per_sample);
   a.pack_out = pack->out;
@@ -257,176 +200,142 @@ void attach_fused_pack(QlpcKernelArgs& a, const PackTarget* pack, uint32_t bits_
   for (int i = 0; i < 4; ++i) a.pack_extra[i] = pa.extra[i];
   a.pack_first_frame = pack->first_frame_number;
   a.pack_frame_step = pack->frame_number_step;
-  a.pack_lds_words = static_cast<uint32_t>(bound / 4 + 4);
+  a.pack_lds_words = pack_lds_words(a.block_size, bits_per_sample);
   fill_crc_powers(a.pack_lds_words, &a.pack_crc_per, a.pack_crc_pow);
-  if (static_cast<size_t>(a.pack_lds_words) * 4 > 35424) a.pack_out = nullptr;  // the bit buffer reuses the two channel images
 }
 
-// Big-block shapes: two analyse-only passes (QLPC, fixed_lpc: records, no residual rows), then one kernel that
-// decides and writes only the two rows the frame keeps (bigblock_residual_kernel, modes 1 and 2) -- eight candidate
-// rows per frame stay off HBM, and so does the copy of the chosen two.
-bool big_block_frames(const flacenc_hip_frame_config* cfg, const QlpcKernelArgs& a) {
-  const uint32_t block_size = a.block_size;
-  const bool big_shape =
-      cfg->use_lpc && (block_size == 8192 || block_size == 16384 || (block_size == 4096 && cfg->qlpc.lpc_order >= 13)) &&
-      !(cfg->qlpc.flags & FLACENC_HIP_FLAG_GENERIC_KERNEL) && !cfg->qlpc.use_direct_mse &&
-      (reinterpret_cast<uintptr_t>(a.samples) & 15) == 0 && (a.stride & 3) == 0 &&
-      (reinterpret_cast<uintptr_t>(a.residual) & 15) == 0 && (a.residual_stride & 3) == 0;
-  const uint32_t fparts = cfg->fixed_partitions;
-  const bool fixed_big = !cfg->use_fixed ||
-                         (cfg->fixed_order_sel == FLACENC_HIP_ORDERSEL_APPROXENT && fparts != 0 && (fparts & (fparts - 1)) == 0 &&
-                          block_size / fparts >= 64 && block_size / fparts <= 4096 && cfg->fixed_max_order <= 4);
-  return big_shape && fixed_big;
-}
-
-int encode_big_block_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const QlpcKernelArgs& a,
-                            hipStream_t s) {
-  const size_t n_sub = a.n_subframes, cstride = padded_stride(a.block_size);
+// Runs a plan, in its order: the frame-level record with its scratch; the fused kernel, or the big-block form, or the
+// sub-wave kernel with the general path behind it for what it marked, or the general path -- the candidate batches (4 QLPC
+// + 4 fixed-LPC candidates per frame in handle scratch) and the stand-alone deciding kernel (frame_decide.cpp).
+int run_frame_plan(flacenc_hip_handle* h, const FrameCall& c, const FramePlan& p, size_t n_frames, uint32_t channels,
+                   flacenc_hip_stereo_frame_result* results, flacenc_hip_channel_result* chan_results, int32_t* residual,
+                   const PackTarget* pack, hipStream_t s) {
+  const flacenc_hip_frame_config& cfg = p.cfg;
+  const size_t n_sub = n_frames * (c.stereo ? 4 : channels);
   int rc;
-  LpcScratch lpc;
-  if ((rc = lpc_scratch(h, n_sub, a.block_size, true, &lpc)) != FLACENC_HIP_OK) return rc;
-  bool analysed = false;
-  rc = enqueue(h, &cfg->qlpc, a.samples, n_sub, a.block_size, a.stride, nullptr, lpc.params, lpc.rows, cstride, nullptr,
-               nullptr, s, true, a.bps_uniform, nullptr, 0, lpc.minmax, &analysed, 1u);
-  if (rc != FLACENC_HIP_OK) return rc;
-  if (!analysed) {
-    h->last_error = "internal: analyse-only QLPC batch on a shape the big-block kernels do not take";
-    return FLACENC_HIP_ERR_UNSUPPORTED;
-  }
-  QlpcKernelArgs m = a;  // (shape, width, the frame's results and rows and the encode_frame switches are set there)
-  m.residual_mode = 2u;
-  m.stamps = nullptr;
-  m.cand_lpc_params = lpc.params;
-  m.cand_lpc_rows = lpc.rows;
-  m.cand_minmax = lpc.minmax;
-  m.cand_stride = cstride;
-  if (cfg->use_fixed) {
-    FixedScratch fixed;
-    if ((rc = fixed_scratch(h, n_sub, a.block_size, &fixed)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue_fixed(h, cfg, a.samples, n_sub, a.block_size, a.stride, nullptr, a.bps_uniform, true, fixed.params,
-                       fixed.rows, cstride, fixed.keys, s, 1u);
-    if (rc != FLACENC_HIP_OK) return rc;
-    m.cand_fixed_params = fixed.params;
-    m.cand_fixed_rows = fixed.rows;
-    m.cand_fixed_keys = fixed.keys;
-  }
-  HIP_TRY(h, launch_bigblock_residual(m, s));
-  return FLACENC_HIP_OK;
-}
-
-// General shapes: the same result from candidate batches (4 QLPC + 4 fixed-LPC candidates per
-// frame in handle scratch) and the stand-alone controller kernel (frame_decide.cpp).
-int encode_general_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const QlpcKernelArgs& a,
-                          FrameDecideArgs& d, hipStream_t s) {
-  const size_t n_sub = a.n_subframes, cstride = padded_stride(a.block_size);
-  int rc;
-  if (cfg->use_lpc) {
-    LpcScratch lpc;
-    if ((rc = lpc_scratch(h, n_sub, a.block_size, true, &lpc)) != FLACENC_HIP_OK) return rc;
-    bool placed_lr = false;
-    rc = enqueue(h, &cfg->qlpc, a.samples, n_sub, a.block_size, a.stride, nullptr, lpc.params, lpc.rows, cstride, nullptr,
-                 nullptr, s, true, a.bps_uniform, a.residual, a.residual_stride, lpc.minmax, &placed_lr);
-    if (rc != FLACENC_HIP_OK) return rc;
-    d.lpc_lr_in_place = placed_lr ? 1u : 0u;
-    d.minmax = placed_lr ? lpc.minmax : nullptr;
-    d.lpc_params = lpc.params;
-    d.lpc_residual = lpc.rows;
-  }
-  if (cfg->use_fixed) {
-    FixedScratch fixed;
-    if ((rc = fixed_scratch(h, n_sub, a.block_size, &fixed)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue_fixed(h, cfg, a.samples, n_sub, a.block_size, a.stride, nullptr, a.bps_uniform, true, fixed.params,
-                       fixed.rows, cstride, fixed.keys, s);
-    if (rc != FLACENC_HIP_OK) return rc;
-    d.fixed_params = fixed.params;
-    d.fixed_residual = fixed.rows;
-    d.fixed_keys = fixed.keys;
-  }
-  HIP_TRY(h, launch_frame_decide(d, s));
-  return FLACENC_HIP_OK;
-}
-
-// `pack` non-null: if the launch can run as the fused kernel with the bit writer, the frames are
-// packed there (*packed = true, `residual` untouched); otherwise *packed = false and the call
-// behaves like flacenc_hip_encode_stereo_frames_async (the caller packs in a second launch).
-int encode_stereo_frames_impl(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
-                              size_t n_frames, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
-                              flacenc_hip_stereo_frame_result* results, int32_t* residual, size_t residual_stride,
-                              void* stream, const PackTarget* pack, bool* packed) {
-  if (packed) *packed = false;
-  if (!h || !cfg || (!results && n_frames)) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_WASTED_BITS)  // (never the fused bit writer: the caller packs)
-    return encode_wasted(h, cfg, frames, n_frames, 0, block_size, stride, bits_per_sample, results, nullptr, residual,
-                         residual_stride, stream);
-  int rc = check_batch_args(h, &cfg->qlpc, frames, n_frames * 4, block_size, stride,
-                            reinterpret_cast<flacenc_hip_subframe_params*>(results), residual, residual_stride, 1);
-  if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
-  if (bits_per_sample < 8 || bits_per_sample > 24) {
-    h->last_error = "bits_per_sample must be in 8..=24";
-    return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  }
-  const flacenc_hip_frame_config run_cfg = frame_config(h, cfg, block_size);
-  cfg = &run_cfg;
-  if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
-  bool fixed_composite = false;  // partitions not whole lane groups: general path
-  const uint32_t group_log2 = fixed_group_log2(cfg, &fixed_composite);
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
   QlpcKernelArgs a;
-  if ((rc = frame_args(h, cfg, frames, n_frames * 4, block_size, stride, bits_per_sample, true, residual, residual_stride,
-                       group_log2, &a)) != FLACENC_HIP_OK)
-    return rc;
-  a.stamps = h->stamps;
-  a.frame_results = results;
-  if (a.reference_order) {  // R[] of the reference-order pass
-    if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
-    rc = attach_sumabs_scratch(h, a, a.use_fixed && a.fixed_order_sel == FLACENC_HIP_ORDERSEL_APPROXENT);
-    if (rc != FLACENC_HIP_OK) return rc;
+  if (p.frame_record) {
+    // base_args with the config's window (none for a short block, which never reads it: short blocks take the
+    // candidate-free general path), the output rows and encode_frame's switches
+    const WindowEntry* win = nullptr;
+    if (c.block_size >= FLACENC_HIP_MIN_BLOCK_SIZE && (rc = get_window(h, &cfg.qlpc, c.block_size, &win)) != FLACENC_HIP_OK) return rc;
+    a = base_args(h, cfg.qlpc, win, c.samples, c.stride, c.block_size, n_sub, nullptr, c.bits_per_sample, c.stereo);
+    a.residual = residual;
+    a.residual_stride = c.residual_stride;
+    frame_fields(a, cfg, c.stereo, p.group_log2);
+    a.fixed_keys = h->fixed_keys;
+    if (c.stereo) a.stamps = h->stamps;
+    a.frame_results = results;
+    a.chan_results = chan_results;
+    // One kernel or two?  Measured on MI355X (24576 frames, order 8): with the fixed-LPC candidate the fused
+    // bit writer takes 1.80 ms against 1.13 + 0.63 ms for the deciding kernel followed by the stand-alone
+    // packer; without it 1.62 against 0.72 + 0.63 ms.  The deciding kernels run at three workgroups per CU,
+    // the fused one -- whose packing tail keeps two of four waves busy -- fits only two, so the two-launch
+    // form is the default; FLACENC_HIP_FLAG_FUSED_PACK / _TWO_STAGE_PACK in cfg->qlpc.flags override it.
+    if (p.fused_pack) attach_fused_pack(a, pack, c.bits_per_sample);
+    if ((rc = attach_scratch(h, a, scratch_grant(a, LaunchKind::kFrame), s)) != FLACENC_HIP_OK) return rc;
   }
-  // One kernel or two?  Measured on MI355X (24576 frames, order 8): with the fixed-LPC candidate the fused
-  // bit writer takes 1.80 ms against 1.13 + 0.63 ms for the deciding kernel followed by the stand-alone
-  // packer; without it 1.62 against 0.72 + 0.63 ms.  The deciding kernels run at three workgroups per CU,
-  // the fused one -- whose packing tail keeps two of four waves busy -- fits only two, so the two-launch
-  // form is the default; FLACENC_HIP_FLAG_FUSED_PACK / _TWO_STAGE_PACK in cfg->qlpc.flags override it.
-  bool want_fused = false;
-  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_FUSED_PACK) want_fused = true;
-  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_TWO_STAGE_PACK) want_fused = false;
-  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH / _ORDER_GUESS / _PRECISION_SEARCH: the candidate batches +
-  // frame_decide_kernel for every shape (FUSED_PACK ignored)
-  // FLACENC_HIP_FLAG_RICE_ESCAPE: the same, whatever the candidates -- the pass sits between the batches and the decision
-  const bool order_search = (lpc_search(cfg->qlpc.flags) && cfg->use_lpc) || (cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE);
-  if (pack && want_fused && !fixed_composite && !order_search && block_size == 4096 && wave_kernel_eligible(a)) {
-    attach_fused_pack(a, pack, bits_per_sample);
-    if (packed) *packed = a.pack_out != nullptr;
+  // block size 4096 / 4608, order <= 12: one fused kernel (analysis, fixed-LPC candidate, the decision, only the chosen
+  // residual written; Independent(n): a wave per channel)
+  if (p.path == FramePlan::kFused) return launch_adaptive(h, a, plan_qlpc_launch(c.block_size, cfg.qlpc.lpc_order), s);
+  CandidateBatch rows(c.samples, n_sub, c.block_size, c.stride);
+  rows.bps_uniform = c.bits_per_sample;
+  rows.stereo = c.stereo;
+  Candidates cand;
+  if (p.path == FramePlan::kBigBlock) {
+    // Big-block shapes: two analyse-only passes (QLPC, fixed_lpc: records, no residual rows), then one kernel that
+    // decides and writes only the two rows the frame keeps (bigblock_residual_kernel, modes 1 and 2) -- eight candidate
+    // rows per frame stay off HBM, and so does the copy of the chosen two.
+    rows.analyse_only = true;
+    if ((rc = enqueue_candidates(h, cfg, p.lpc_batch, p.fixed_batch, rows, s, &cand)) != FLACENC_HIP_OK) return rc;
+    a.residual_mode = 2u;  // (shape, width, the frame's results and rows and the encode_frame switches are set)
+    a.stamps = nullptr;
+    a.cand_lpc_params = cand.lpc_params;
+    a.cand_lpc_rows = cand.lpc_residual;
+    a.cand_minmax = cand.minmax;
+    a.cand_stride = padded_stride(c.block_size);
+    a.cand_fixed_params = cand.fixed_params;
+    a.cand_fixed_rows = cand.fixed_residual;
+    a.cand_fixed_keys = cand.fixed_keys;
+    HIP_TRY(h, launch_bigblock_residual(a, s));
+    return FLACENC_HIP_OK;
   }
-  if (a.split_scratch == nullptr && certify_needs_scratch(a)) {  // (the fused bit writer is handed the reference's R[])
-    if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
+  FrameDecideArgs fd{};
+  ChannelDecideArgs cd{};
+  auto decide_fields = [&](auto& d) {
+    d.stride = c.stride;
+    d.block_size = c.block_size;
+    d.bits_per_sample = c.bits_per_sample;
+    d.use_constant = cfg.use_constant;
+    d.use_fixed = cfg.use_fixed;
+    d.use_lpc = cfg.use_lpc;
+    d.cand_stride = padded_stride(c.block_size);
+    d.residual = residual;
+    d.residual_stride = c.residual_stride;
+  };
+  if (c.stereo) {
+    decide_fields(fd);
+    fd.frames = c.samples;
+    fd.n_frames = static_cast<uint32_t>(n_frames);
+    fd.use_leftside = cfg.use_leftside;
+    fd.use_rightside = cfg.use_rightside;
+    fd.use_midside = cfg.use_midside;
+    fd.results = results;
+  } else {
+    decide_fields(cd);
+    cd.samples = c.samples;
+    cd.n_subframes = static_cast<uint32_t>(n_sub);
+    cd.results = chan_results;
   }
-  if (wave_kernel_eligible(a) && !fixed_composite && !order_search)
-    return launch_adaptive(h, a, plan_qlpc_launch(block_size, cfg->qlpc.lpc_order), s);
-  if (!order_search && big_block_frames(cfg, a)) return encode_big_block_frames(h, cfg, a, s);
-  FrameDecideArgs d{};
-  d.frames = frames;
-  d.stride = stride;
-  d.block_size = block_size;
-  d.n_frames = static_cast<uint32_t>(n_frames);
-  d.bits_per_sample = bits_per_sample;
-  d.use_constant = cfg->use_constant;
-  d.use_fixed = cfg->use_fixed;
-  d.use_lpc = cfg->use_lpc;
-  d.use_leftside = cfg->use_leftside;
-  d.use_rightside = cfg->use_rightside;
-  d.use_midside = cfg->use_midside;
-  d.cand_stride = padded_stride(block_size);
-  d.results = results;
-  d.residual = residual;
-  d.residual_stride = residual_stride;
-  if (block_size >= FLACENC_HIP_MIN_BLOCK_SIZE && subwave_shape(block_size) && !order_search) {
-    bool taken = false;
-    rc = subwave_frames(h, cfg, a, &d, nullptr, s, &taken);
-    if (rc != FLACENC_HIP_OK || taken) return rc;
+  if (p.subwave_scratch) {
+    rc = subwave_frames(h, p, a, c.stereo ? &fd : nullptr, c.stereo ? nullptr : &cd, s);
+    if (rc != FLACENC_HIP_OK || p.path == FramePlan::kSubwave) return rc;
   }
-  return encode_general_frames(h, cfg, a, d, s);
+  if (c.stereo) {  // (the big-block shapes: L / R in place)
+    rows.residual_lr = residual;
+    rows.residual_lr_stride = c.residual_stride;
+  }
+  if ((rc = enqueue_candidates(h, cfg, p.lpc_batch, p.fixed_batch, rows, s, &cand)) != FLACENC_HIP_OK) return rc;
+  if (c.stereo) {
+    name_candidates(fd, cand);
+    fd.lpc_lr_in_place = cand.placed ? 1u : 0u;
+    fd.minmax = cand.placed ? cand.minmax : nullptr;
+    HIP_TRY(h, launch_frame_decide(fd, s));
+  } else {
+    name_candidates(cd, cand);
+    HIP_TRY(h, launch_channel_decide(cd, s));
+  }
+  return FLACENC_HIP_OK;
+}
+
+// Both frame-level calls: check the arguments, plan, run the plan.  channels == 0: 2-channel frames into `results`, else
+// Independent(channels) frames into `chan_results`.  `pack` non-null: if the launch can run as the fused kernel with the bit
+// writer, the frames are packed there (*packed = true, `residual` untouched); otherwise the caller packs in a second launch.
+int encode_frames_common(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames, size_t n_frames,
+                         uint32_t channels, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
+                         flacenc_hip_stereo_frame_result* results, flacenc_hip_channel_result* chan_results,
+                         int32_t* residual, size_t residual_stride, void* stream, const PackTarget* pack, bool* packed) {
+  if (packed) *packed = false;
+  const bool stereo = channels == 0;
+  void* const records = stereo ? static_cast<void*>(results) : static_cast<void*>(chan_results);
+  if (!h || !cfg || (!records && n_frames)) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  int rc = check_batch_args(h, &cfg->qlpc, frames, n_frames * (stereo ? 4 : channels), block_size, stride,
+                            static_cast<flacenc_hip_subframe_params*>(records), residual, residual_stride, 1);
+  if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
+  if ((rc = check_bits_per_sample(h, bits_per_sample)) != FLACENC_HIP_OK) return rc;
+  const bool wasted = (cfg->qlpc.flags & FLACENC_HIP_FLAG_WASTED_BITS) != 0;
+  // (the plain stereo call has always let a short block's fixed config pass unverified: too_short drops it)
+  const bool unverified = stereo && !wasted && block_size < FLACENC_HIP_MIN_BLOCK_SIZE;
+  if (cfg->use_fixed && !unverified && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
+  if (wasted)  // (never the fused bit writer: the caller packs)
+    return encode_wasted(h, cfg, frames, n_frames, channels, block_size, stride, bits_per_sample, results, chan_results,
+                         residual, residual_stride, stream);
+  const FrameCall call{*cfg, stereo, block_size, bits_per_sample, frames, stride, residual, residual_stride,
+                       pack && pack_lds_words(block_size, bits_per_sample) * 4ull <= 35424, !h->lpc_windows.empty(), h->precision_floor};
+  const FramePlan plan = plan_frame_call(call);
+  HIP_TRY(h, hipSetDevice(h->device));
+  if (packed) *packed = plan.fused_pack;
+  return run_frame_plan(h, call, plan, n_frames, channels, results, chan_results, residual, pack, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -438,88 +347,9 @@ int flacenc_hip_encode_frames_async(flacenc_hip_handle* h, const flacenc_hip_fra
                                     uint32_t block_size, size_t stride, uint32_t bits_per_sample,
                                     flacenc_hip_channel_result* results, int32_t* residual,
                                     size_t residual_stride, void* stream) {
-  if (!h || !cfg || (!results && n_frames) || channels < 1 || channels > 8) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  if (cfg->qlpc.flags & FLACENC_HIP_FLAG_WASTED_BITS)
-    return encode_wasted(h, cfg, frames, n_frames, channels, block_size, stride, bits_per_sample, nullptr, results,
-                         residual, residual_stride, stream);
-  const size_t n_sub = n_frames * channels;
-  int rc = check_batch_args(h, &cfg->qlpc, frames, n_sub, block_size, stride,
-                            reinterpret_cast<flacenc_hip_subframe_params*>(results), residual, residual_stride, 1);
-  if (rc != FLACENC_HIP_OK || n_frames == 0) return rc;
-  if (bits_per_sample < 8 || bits_per_sample > 24) {
-    h->last_error = "bits_per_sample must be in 8..=24";
-    return FLACENC_HIP_ERR_BAD_ARGUMENT;
-  }
-  if (cfg->use_fixed && (rc = verify_fixed(h, cfg)) != FLACENC_HIP_OK) return rc;
-  const flacenc_hip_frame_config run_cfg = frame_config(h, cfg, block_size);
-  cfg = &run_cfg;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t cstride = padded_stride(block_size);
-  ChannelDecideArgs d{};
-  d.samples = frames;
-  d.stride = stride;
-  d.block_size = block_size;
-  d.n_subframes = static_cast<uint32_t>(n_sub);
-  d.bits_per_sample = bits_per_sample;
-  d.use_constant = cfg->use_constant;
-  d.use_fixed = cfg->use_fixed;
-  d.use_lpc = cfg->use_lpc;
-  d.cand_stride = cstride;
-  d.results = results;
-  d.residual = residual;
-  d.residual_stride = residual_stride;
-  // FLACENC_HIP_FLAG_ORDER_SEARCH / _WINDOW_SEARCH: the candidate batches + channel_decide_kernel for every shape
-  // ... and FLACENC_HIP_FLAG_RICE_ESCAPE, whose pass sits between the batches and the decision
-  if (!((lpc_search(cfg->qlpc.flags) && cfg->use_lpc) || (cfg->qlpc.flags & FLACENC_HIP_FLAG_RICE_ESCAPE))) {
-    // block size 4096, order <= 12: one fused kernel, a wave per channel (analysis, fixed-LPC
-    // candidate, encode_subframe's choice, only the chosen residual written)
-    bool composite = false;
-    const uint32_t glog = fixed_group_log2(cfg, &composite);
-    QlpcKernelArgs a;
-    if ((rc = frame_args(h, cfg, frames, n_sub, block_size, stride, bits_per_sample, false, residual, residual_stride,
-                         glog, &a)) != FLACENC_HIP_OK)
-      return rc;
-    a.chan_results = results;
-    if (a.reference_order || certify_needs_scratch(a)) {  // R[] of the reference-order pass
-      if ((rc = attach_split_scratch(h, a, stream)) != FLACENC_HIP_OK) return rc;
-    }
-    if ((rc = attach_sumabs_scratch(h, a, cfg->use_fixed && cfg->fixed_order_sel == FLACENC_HIP_ORDERSEL_APPROXENT)) !=
-        FLACENC_HIP_OK)
-      return rc;
-    if (!composite && wave_kernel_eligible(a)) {
-      QlpcLaunchPlan plan = plan_qlpc_launch(block_size, cfg->qlpc.lpc_order);
-      return launch_adaptive(h, a, plan, s);
-    }
-    // the sub-wave kernel's independent-channel variant; what it marks takes the general path below, restricted to
-    // the marked subframes
-    if (block_size >= FLACENC_HIP_MIN_BLOCK_SIZE && subwave_shape(block_size)) {
-      bool taken = false;
-      rc = subwave_frames(h, cfg, a, nullptr, &d, s, &taken);
-      if (rc != FLACENC_HIP_OK || taken) return rc;
-    }
-  }
-  if (cfg->use_lpc) {
-    LpcScratch lpc;
-    if ((rc = lpc_scratch(h, n_sub, block_size, false, &lpc)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue(h, &cfg->qlpc, frames, n_sub, block_size, stride, nullptr, lpc.params, lpc.rows, cstride, nullptr,
-                 nullptr, s, false, bits_per_sample);
-    if (rc != FLACENC_HIP_OK) return rc;
-    d.lpc_params = lpc.params;
-    d.lpc_residual = lpc.rows;
-  }
-  if (cfg->use_fixed) {
-    FixedScratch fixed;
-    if ((rc = fixed_scratch(h, n_sub, block_size, &fixed)) != FLACENC_HIP_OK) return rc;
-    rc = enqueue_fixed(h, cfg, frames, n_sub, block_size, stride, nullptr, bits_per_sample, false, fixed.params,
-                       fixed.rows, cstride, fixed.keys, s);
-    if (rc != FLACENC_HIP_OK) return rc;
-    d.fixed_params = fixed.params;
-    d.fixed_residual = fixed.rows;
-    d.fixed_keys = fixed.keys;
-  }
-  HIP_TRY(h, launch_channel_decide(d, s));
-  return FLACENC_HIP_OK;
+  if (channels < 1 || channels > 8) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  return encode_frames_common(h, cfg, frames, n_frames, channels, block_size, stride, bits_per_sample, nullptr, results,
+                              residual, residual_stride, stream, nullptr, nullptr);
 }
 
 int flacenc_hip_encode_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg,
@@ -579,16 +409,10 @@ int flacenc_hip_encode_pack_stereo_frames_async(flacenc_hip_handle* h, const fla
   int rc;
   const size_t cstride = padded_stride(block_size);
   if ((rc = ensure(h, h->d_presid, n_frames * 2 * cstride * 4)) != FLACENC_HIP_OK) return rc;
-  PackTarget pt;
-  pt.out = out;
-  pt.out_stride = out_stride;
-  pt.out_len = out_len;
-  pt.sample_rate = sample_rate;
-  pt.first_frame_number = first_frame_number;
-  pt.frame_number_step = frame_number_step;
+  const PackTarget pt{out, out_stride, out_len, sample_rate, first_frame_number, frame_number_step};
   bool packed = false;
-  rc = encode_stereo_frames_impl(h, cfg, frames, n_frames, block_size, stride, bits_per_sample, results,
-                                 static_cast<int32_t*>(h->d_presid.ptr), cstride, stream, &pt, &packed);
+  rc = encode_frames_common(h, cfg, frames, n_frames, 0, block_size, stride, bits_per_sample, results, nullptr,
+                            static_cast<int32_t*>(h->d_presid.ptr), cstride, stream, &pt, &packed);
   if (rc != FLACENC_HIP_OK || packed) return rc;
   return flacenc_hip_pack_stereo_frames_async(h, frames, n_frames, block_size, stride, results,
                                               static_cast<const int32_t*>(h->d_presid.ptr), cstride, bits_per_sample,
@@ -623,8 +447,8 @@ int flacenc_hip_encode_stereo_frames_async(flacenc_hip_handle* h, const flacenc_
                                            size_t stride, uint32_t bits_per_sample,
                                            flacenc_hip_stereo_frame_result* results, int32_t* residual,
                                            size_t residual_stride, void* stream) {
-  return encode_stereo_frames_impl(h, cfg, frames, n_frames, block_size, stride, bits_per_sample, results, residual,
-                                   residual_stride, stream, nullptr, nullptr);
+  return encode_frames_common(h, cfg, frames, n_frames, 0, block_size, stride, bits_per_sample, results, nullptr, residual,
+                              residual_stride, stream, nullptr, nullptr);
 }
 
 int flacenc_hip_encode_stereo_frames(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg,

@@ -103,8 +103,8 @@ void flacenc_hip_destroy(flacenc_hip_handle* h) {
     if (e.dev) (void)hipFree(e.dev);
   for (DeviceBuffer* b : device_buffers(h))
     if (b->ptr) (void)hipFree(b->ptr);
-  if (h->d_cert_fb) (void)hipFree(h->d_cert_fb);  // (the order mode's counters and their pinned mirror)
-  if (h->h_cert_fb) (void)hipHostFree(h->h_cert_fb);
+  if (h->adaptive.d_counters) (void)hipFree(h->adaptive.d_counters);  // (the order mode's counters and their pinned mirror)
+  if (h->adaptive.verdict) (void)hipHostFree(h->adaptive.verdict);
   for (int i = 0; i < 2; ++i) {
     for (void* p : {h->pin_in[i], h->pin_out[i], h->pin_meta[i]})
       if (p) (void)hipHostFree(p);

@@ -8,8 +8,10 @@
 //
 //   api_handle.cpp       create / destroy / synchronize, verify_config, pinned memory, set_error, ensure
 //   api_windows.cpp      the analysis windows and their cache
-//   api_candidates.cpp   the candidate batches: argument checks, scratch, the order mode, enqueue, enqueue_fixed
-//   api_frames.cpp       encode_frame's decisions: independent channels, stereo, wasted bits, encode + pack
+//   api_candidates.cpp   the candidate batches: argument checks, scratch, the order mode's launches, enqueue, enqueue_fixed
+//   frame_plan.cpp       pure, host-only testable: the records' config fields, the scratch rule, plan_frame_call
+//   order_mode_core.h    pure: the order mode's step
+//   api_frames.cpp       encode_frame's decisions: check, plan_frame_call, run the plan; wasted bits, encode + pack
 //   api_pack.cpp         Frame::write, frame lengths, the wire format, stream offsets
 //   api_stream.cpp       the streaming host path (flacenc_hip_encode_pcm)
 //   api_decode.cpp       decode / verify / index
@@ -37,6 +39,8 @@
 #include "comm.h"
 #include "flacenc_hip.h"
 #include "frame_pack.h"
+#include "frame_plan.h"
+#include "order_mode_core.h"
 #include "qlpc_kernel.h"
 
 namespace streamenc {
@@ -233,15 +237,14 @@ struct flacenc_hip_handle {
   // brought into place, the product's form: the faster one; 0 dwords)
   int planar_fill_form = 1;
   flacenc_hip::CommState* comm = nullptr;  // RCCL communicator of the ordered gather (comm.cpp)
-  // Order mode of the certified shapes by material (launch_adaptive): the certificate's own counters of the last
-  // launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each such launch
-  uint32_t* d_cert_fb = nullptr;               // device: the three counters of QlpcKernelArgs::cert_stats
-  unsigned long long* h_cert_fb = nullptr;     // pinned, device-visible: the latest verdict (cert_feedback_kernel)
-  uint32_t fb_seq = 0, fb_seen_seq = 0, fb_probe_seq = 0;  // sequence numbers of the launches that carried the counters
-  uint32_t fb_pending = 0;  // subframes counted on the device since the last verdict went out
-  bool fb_probe_out = false;
-  int two_pass_left = 0, two_pass_span = 0;
-  int adaptive_order = 1;                      // flacenc_hip_debug_set_adaptive_order(h, 0) pins the certified kernel
+  // Order mode of the certified shapes by material (launch_adaptive, order_mode_core.h): the certificate's own counters
+  // of the last launches, cumulative on the device and mirrored into one pinned word by a one-thread kernel behind each
+  struct OrderMode {
+    uint32_t* d_counters = nullptr;         // device: the three counters of QlpcKernelArgs::cert_stats
+    unsigned long long* verdict = nullptr;  // pinned, device-visible: the latest verdict (cert_feedback_kernel)
+    order_mode::State state;
+    int enabled = 1;                        // flacenc_hip_debug_set_adaptive_order(h, 0) pins the certified kernel
+  } adaptive;
 };
 
 #define HIP_TRY(h, expr)                          \
@@ -275,8 +278,7 @@ int rows_to_device(flacenc_hip_handle* h, const DeviceBuffer& b, const int32_t* 
 int rows_to_host(flacenc_hip_handle* h, int32_t* rows, size_t stride, const DeviceBuffer& b, uint32_t block_size,
                  size_t n_rows);
 
-// row stride of every scratch buffer of sample or residual rows: whole 16-byte groups
-inline size_t padded_stride(uint32_t block_size) { return (static_cast<size_t>(block_size) + 3) & ~static_cast<size_t>(3); }
+// (padded_stride, frame_plan.h: the row stride of every scratch buffer of sample or residual rows, whole 16-byte groups)
 inline size_t a256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 
 // ---- api_windows.cpp ----
@@ -285,46 +287,58 @@ int get_window_entry(flacenc_hip_handle* h, uint32_t type, float alpha, uint32_t
 int get_window(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, uint32_t n, const WindowEntry** out);
 
 // ---- api_candidates.cpp ----
-uint32_t search_flags(const flacenc_hip_handle* h, uint32_t flags, uint32_t quant_precision);
-bool lpc_search(uint32_t flags);
 int check_batch_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples,
                      size_t n_subframes, uint32_t block_size, size_t stride, flacenc_hip_subframe_params* params,
                      int32_t* residual, size_t residual_stride, uint32_t min_block = FLACENC_HIP_MIN_BLOCK_SIZE);
+int check_bits_per_sample(flacenc_hip_handle* h, uint32_t bits_per_sample);  // 8..=24
 int verify_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg);
-// What every launch record shares, from (handle, qlpc config, shape): the rows, the window entry (`win` null: no window,
-// flat range 0), order and precision, max_rice_parameter, the three flag-derived words, set_certify and direct_mse.
-// Everything else is as QlpcKernelArgs initialises it; each caller sets what is its own.
+// config_record (frame_plan.h) + what the handle adds: the window entry (`win` null: no window, flat range 0) and the
+// statistics hook.  Everything else is as QlpcKernelArgs initialises it; each caller sets what is its own.
 QlpcKernelArgs base_args(flacenc_hip_handle* h, const flacenc_hip_qlpc_config& q, const WindowEntry* win,
                          const int32_t* samples, size_t stride, uint32_t block_size, size_t n_subframes,
                          const uint8_t* bps, uint32_t bps_uniform, bool stereo);
-bool certify_needs_scratch(const QlpcKernelArgs& a);
-int attach_sumabs_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, bool approx_ent);
-int attach_split_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, void* stream);
-int launch_adaptive(flacenc_hip_handle* h, QlpcKernelArgs& a, const QlpcLaunchPlan& plan, hipStream_t stream);
-// The candidates' scratch of a frame-level call, `n_rows` candidates of `block_size` samples in the handle's buffers:
-// records, rows at padded_stride(block_size) and (LPC, on request) the roles' min / max resp. (fixed) the selector keys
-struct LpcScratch {
-  flacenc_hip_subframe_params* params;
-  int32_t* rows;
-  int32_t* minmax;  // null unless asked for
+// gives the record what scratch_grant (frame_plan.h) says
+int attach_scratch(flacenc_hip_handle* h, QlpcKernelArgs& a, ScratchGrant grant, hipStream_t stream);
+int launch_adaptive(flacenc_hip_handle* h, const QlpcKernelArgs& a, const QlpcLaunchPlan& plan, hipStream_t stream);
+// The candidates' scratch of a frame-level call in the handle's buffers, named as the deciding kernels' records name it:
+// records, rows at padded_stride(block_size), on request the roles' min / max, the selector keys; null where a kind is off
+struct Candidates {
+  flacenc_hip_subframe_params *lpc_params = nullptr, *fixed_params = nullptr;
+  int32_t *lpc_residual = nullptr, *fixed_residual = nullptr, *minmax = nullptr;
+  unsigned long long* fixed_keys = nullptr;
+  bool placed = false;  // CandidateBatch::placed of the LPC batch
 };
-struct FixedScratch {
-  flacenc_hip_subframe_params* params;
-  int32_t* rows;
-  unsigned long long* keys;
+int candidate_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, bool lpc, bool fixed, bool with_minmax,
+                      Candidates* out);
+// One candidate batch, estimated_qlpc (enqueue) resp. fixed_lpc (enqueue_fixed): a call site gives the rows and names the rest
+struct CandidateBatch {
+  CandidateBatch(const int32_t* rows, size_t n, uint32_t block, size_t row_stride, const uint8_t* widths = nullptr)
+      : samples(rows), n_subframes(n), stride(row_stride), block_size(block), bps(widths) {}
+  void write_to(flacenc_hip_subframe_params* records, int32_t* rows, size_t row_stride) {
+    params = records;
+    residual = rows;
+    residual_stride = row_stride;
+  }
+  const int32_t* samples;  // the rows: n_subframes of block_size words, `stride` words apart
+  size_t n_subframes, stride;
+  uint32_t block_size;
+  const uint8_t* bps;            // per-row widths, or (null) bps_uniform for all
+  uint32_t bps_uniform = 16;
+  bool stereo = false;           // rows 4f .. 4f + 3 are the roles of 2-channel frame f
+  flacenc_hip_subframe_params* params = nullptr;  // out: the records, the rows
+  int32_t* residual = nullptr;
+  size_t residual_stride = 0;
+  double *autocorr = nullptr, *lpc_coefs = nullptr;  // optional outputs of enqueue ...
+  unsigned long long* selector_keys = nullptr;       // ... and of enqueue_fixed
+  // frame-level callers on the big-block shapes (QlpcKernelArgs::residual_lr, ::residual_mode): L / R candidates straight
+  // into the frame's rows with the roles' min / max, or (analyse_only) records and min / max alone
+  int32_t *residual_lr = nullptr, *minmax_out = nullptr;
+  size_t residual_lr_stride = 0;
+  bool analyse_only = false;
+  bool placed = false;  // out: enqueue did so (the big-block kernels took the launch)
 };
-int lpc_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, bool with_minmax, LpcScratch* out);
-int fixed_scratch(flacenc_hip_handle* h, size_t n_rows, uint32_t block_size, FixedScratch* out);
-int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, const int32_t* samples, size_t n_subframes,
-            uint32_t block_size, size_t stride, const uint8_t* bps, flacenc_hip_subframe_params* params,
-            int32_t* residual, size_t residual_stride, double* autocorr, double* lpc_coefs, hipStream_t stream,
-            bool stereo = false, uint32_t bps_uniform = 16, int32_t* residual_lr = nullptr,
-            size_t residual_lr_stride = 0, int32_t* minmax_out = nullptr, bool* placed = nullptr,
-            uint32_t residual_mode = 0);
-int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* samples,
-                  size_t n_subframes, uint32_t block_size, size_t stride, const uint8_t* bps, uint32_t bps_uniform,
-                  bool stereo, flacenc_hip_subframe_params* params, int32_t* residual, size_t residual_stride,
-                  unsigned long long* selector_keys, hipStream_t stream, uint32_t residual_mode = 0);
+int enqueue(flacenc_hip_handle* h, const flacenc_hip_qlpc_config* cfg, CandidateBatch& b, hipStream_t stream);
+int enqueue_fixed(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, CandidateBatch& b, hipStream_t stream);
 
 // ---- api_stream.cpp ----
 // what the streaming host paths (encode_pcm, decode_pcm) share: is the caller's buffer page-locked, the two pinned

@@ -74,7 +74,6 @@ static bool subwave_candidates_ok(const QlpcKernelArgs& a, uint32_t reference_or
   if (reference_order != 0 && !have_r) return false;
   return a.frame_results == nullptr && a.chan_results == nullptr && a.params != nullptr;
 }
-bool subwave_eligible(const QlpcKernelArgs& a) { return subwave_candidates_ok(a, a.reference_order, a.acorr_in != nullptr); }
 
 bool subwave_fixed_eligible(const QlpcKernelArgs& a) {
   if (!subwave_buffers_ok(a) || a.fixed_mode != 1u || !subwave_fixed_ok(a)) return false;
@@ -238,7 +237,6 @@ hipError_t launch_subwave_frames(const QlpcKernelArgs& a, hipStream_t stream) {
 
 QlpcLaunchPlan plan_qlpc_launch(uint32_t block_size, uint32_t lpc_order) {
   QlpcLaunchPlan plan;
-  plan.wave = false;
   const int n = static_cast<int>(block_size);
   const int rows = (n + 15) / 16;
   plan.big = n > 16384;

@@ -160,7 +160,6 @@ __device__ __forceinline__ void count_marked(const QlpcKernelArgs& a, uint32_t i
 }
 
 struct QlpcLaunchPlan {
-  bool wave;       // wave-per-subframe kernel (block_size 4096, order <= 12, aligned buffers)
   int maxp;        // template bucket for the LPC order
   bool big;        // block_size > 16384: unpadded LDS image, bit tables in HBM scratch
   int threads;     // workgroup size (power of two, 64..1024)
@@ -262,7 +261,6 @@ FLACENC_HIP_FOR_EACH_BIGRES_INSTANCE(FLACENC_HIP_DECLARE_BIGRES_INSTANCE)
 // variant: 0 QLPC candidates, 1 fixed_lpc batch with the ApproxEnt selector, 2 the 2-channel frame decision, 3 frames of
 // independent channels)
 bool subwave_shape(uint32_t block_size);
-bool subwave_eligible(const QlpcKernelArgs& args);        // variant 0
 bool subwave_fixed_eligible(const QlpcKernelArgs& args);  // variant 1 (args.fixed_mode == 1)
 bool subwave_frame_eligible(const QlpcKernelArgs& args);  // variant 2 (args.frame_results set)
 // variant 2: results + the two chosen rows per frame; frames it could not decide (a candidate beyond the exact sums) are

@@ -15,8 +15,8 @@ row ends at it and the next one starts there -- so only buffers whose row size d
 the seam strictly inside (seam_rows says which of the two holds).  The sparse cases of the GPU file choose their stride
 so that one row always has the seam strictly inside it (sparse_stride).
 
-Memory.  need_bytes(case) is caller buffers + handle scratch by the sizing rules of api_candidates.cpp (lpc_scratch,
-fixed_scratch, attach_split_scratch, attach_sumabs_scratch), api_frames.cpp (the encode + pack calls' residual rows, the
+Memory.  need_bytes(case) is caller buffers + handle scratch by the sizing rules of api_candidates.cpp (candidate_scratch,
+attach_scratch), api_frames.cpp (the encode + pack calls' residual rows, the
 wasted-bits rows) and api_pack.cpp (the escape list), each grown as flacenc_hip::ensure grows a buffer (a quarter more +
 256 bytes), + the largest temporary the comparison makes.  The rule is a condition, not a measurement: at most 64 GiB
 per case on a card of 288 GB that is shared."""

@@ -42,7 +42,7 @@ def routes(tmp_path_factory):
     subprocess.check_call([makefile_hipcc(), "--offload-host-only", "-O2", "-std=c++17", "-Wall", "-Werror",
                            "-Wno-unused-function", "-I", INCLUDE, "-I", CSRC, "-x", "hip",
                            os.path.join(ROOT, "tests", "host", "dispatch_trace.cpp"),
-                           os.path.join(CSRC, "qlpc_dispatch.cpp"), "-pthread", "-o", exe])
+                           os.path.join(CSRC, "qlpc_dispatch.cpp"), os.path.join(CSRC, "frame_plan.cpp"), "-pthread", "-o", exe])
     p = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     return p.stdout
