@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_set_lpc_windows",
     "flacenc_hip_set_order_guesses",
     "flacenc_hip_set_precision_floor",
+    "flacenc_hip_set_max_bits_per_sample",
     "flacenc_hip_lpc_window_weights",
     "flacenc_hip_qlpc_batch",
     "flacenc_hip_qlpc_batch_async",
@@ -365,6 +366,8 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_set_order_guesses.restype = C.c_int
     L.flacenc_hip_set_precision_floor.argtypes = [vp, C.c_uint32]
     L.flacenc_hip_set_precision_floor.restype = C.c_int
+    L.flacenc_hip_set_max_bits_per_sample.argtypes = [vp, C.c_uint32]
+    L.flacenc_hip_set_max_bits_per_sample.restype = C.c_int
     L.flacenc_hip_lpc_window_weights.argtypes = [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.flacenc_hip_lpc_window_weights.restype = C.c_int
     L.flacenc_hip_synchronize.argtypes = [vp]
@@ -716,6 +719,11 @@ class Handle:
         """flacenc_hip_set_precision_floor: F of FLAG_PRECISION_SEARCH, the lowest coefficient precision searched,
         1..15 (a fresh handle holds 5); applies to the calls made after it."""
         self._check(self._lib.flacenc_hip_set_precision_floor(self._h, int(floor)))
+
+    def set_max_bits_per_sample(self, bits: int):
+        """flacenc_hip_set_max_bits_per_sample: the deepest FLAC stream the decode calls take, 24 (a fresh handle) or
+        32; applies to the calls made after it.  The encode calls take at most 24 bits whatever the setting."""
+        self._check(self._lib.flacenc_hip_set_max_bits_per_sample(self._h, int(bits)))
 
     def _hook(self, name):
         if not hasattr(self._lib, name):

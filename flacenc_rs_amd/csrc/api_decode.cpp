@@ -13,8 +13,8 @@ static int check_decode_args(flacenc_hip_handle* h, const uint8_t* bytes, const 
                     "stride < max_block_size or more than 2^31 - 1 frames";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
-  if (bits_per_sample < 4 || bits_per_sample > 24) {
-    h->last_error = "decode_frames: bits_per_sample not in 4..=24";
+  if (bits_per_sample < 4 || bits_per_sample > h->max_bps) {
+    h->last_error = "decode_frames: bits_per_sample not in 4..=24 (4..=32 with flacenc_hip_set_max_bits_per_sample)";
     return FLACENC_HIP_ERR_UNSUPPORTED;
   }
   return FLACENC_HIP_OK;
@@ -33,8 +33,8 @@ static int decode_or_verify_async(flacenc_hip_handle* h, const uint8_t* bytes, u
   HIP_TRY(h, hipSetDevice(h->device));
   if ((rc = ensure(h, h->d_dec, flacenc_hip::decode_scratch_bytes(n_frames))) != FLACENC_HIP_OK) return rc;
   HIP_TRY(h, flacenc_hip::launch_decode_frames(bytes, n_bytes, offsets, lengths, static_cast<uint32_t>(n_frames),
-                                               channels, bits_per_sample, max_block_size, out, expected, stride,
-                                               block_sizes, numbers, status, h->d_dec.ptr,
+                                               channels, bits_per_sample, max_block_size, h->max_bps, out, expected,
+                                               stride, block_sizes, numbers, status, h->d_dec.ptr,
                                                static_cast<hipStream_t>(stream)));
   return FLACENC_HIP_OK;
 }
@@ -114,15 +114,16 @@ int flacenc_hip_index_frames_async(flacenc_hip_handle* h, const uint8_t* bytes, 
     h->last_error = "index_frames: null pointer, channels not in 1..=8, max_frames >= 2^30 or n_bytes >= 16 TiB";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
-  if (bits_per_sample < 4 || bits_per_sample > 24) {
-    h->last_error = "index_frames: bits_per_sample not in 4..=24";
+  if (bits_per_sample < 4 || bits_per_sample > h->max_bps) {
+    h->last_error = "index_frames: bits_per_sample not in 4..=24 (4..=32 with flacenc_hip_set_max_bits_per_sample)";
     return FLACENC_HIP_ERR_UNSUPPORTED;
   }
   HIP_TRY(h, hipSetDevice(h->device));
   const size_t cap = flacenc_hip::index_candidate_capacity(max_frames);
   int rc = ensure(h, h->d_idx, flacenc_hip::index_scratch_bytes(n_bytes, cap));
   if (rc != FLACENC_HIP_OK) return rc;
-  HIP_TRY(h, flacenc_hip::launch_index_frames(bytes, n_bytes, channels, bits_per_sample, max_frames, offsets, lengths,
+  HIP_TRY(h, flacenc_hip::launch_index_frames(bytes, n_bytes, channels, bits_per_sample, h->max_bps, max_frames, offsets,
+                                              lengths,
                                               n_frames, h->d_idx.ptr, cap, static_cast<hipStream_t>(stream)));
   return FLACENC_HIP_OK;
 }

@@ -106,8 +106,8 @@ int flacenc_hip_decode_pcm(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t
                     "bytes_per_sample above 4";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
-  if (bits_per_sample < 4 || bits_per_sample > 24) {
-    h->last_error = "decode_pcm: bits_per_sample not in 4..=24";
+  if (bits_per_sample < 4 || bits_per_sample > h->max_bps) {
+    h->last_error = "decode_pcm: bits_per_sample not in 4..=24 (4..=32 with flacenc_hip_set_max_bits_per_sample)";
     return FLACENC_HIP_ERR_UNSUPPORTED;
   }
   if (bytes_per_sample < (bits_per_sample + 7) / 8) {

@@ -177,6 +177,16 @@ int flacenc_hip_set_precision_floor(flacenc_hip_handle* h, uint32_t floor) {
   return FLACENC_HIP_OK;
 }
 
+int flacenc_hip_set_max_bits_per_sample(flacenc_hip_handle* h, uint32_t bits) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (bits != 24 && bits != 32) {
+    h->last_error = "flacenc_hip_set_max_bits_per_sample: bits must be 24 or 32";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->max_bps = bits;
+  return FLACENC_HIP_OK;
+}
+
 void* flacenc_hip_host_alloc(size_t bytes) {
   void* p = nullptr;
   if (bytes == 0 || hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) return nullptr;

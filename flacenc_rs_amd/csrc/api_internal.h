@@ -192,6 +192,8 @@ struct flacenc_hip_handle {
   uint32_t order_guesses = 1;  // FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window (flacenc_hip_set_order_guesses)
   // FLACENC_HIP_FLAG_PRECISION_SEARCH: F, the lowest precision searched (flacenc_hip_set_precision_floor)
   uint32_t precision_floor = 5;
+  // the deepest stream the decode calls take, 24 or 32 (flacenc_hip_set_max_bits_per_sample)
+  uint32_t max_bps = 24;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into

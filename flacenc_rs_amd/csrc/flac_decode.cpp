@@ -32,7 +32,8 @@ __global__ void __launch_bounds__(256) skim_kernel(const uint8_t* __restrict__ b
                                                    const uint64_t* __restrict__ offsets,
                                                    const uint32_t* __restrict__ lengths, uint32_t n,
                                                    const uint32_t* __restrict__ n_dev, uint32_t channels, uint32_t bps,
-                                                   uint32_t max_block_size, FrameRec* __restrict__ recs,
+                                                   uint32_t max_block_size, uint32_t max_bps,
+                                                   FrameRec* __restrict__ recs,
                                                    uint64_t* __restrict__ nums) {
   const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
   if (n_dev) n = min(n, *n_dev);
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(256) skim_kernel(const uint8_t* __restrict__ b
     rec.status = flacdec::LENGTH;
     rec.block_size = rec.info = rec.len = 0;
   } else {
-    flacdec::skim_frame(bytes + off, len, channels, bps, max_block_size, lengths != nullptr, kCrc, rec, &num);
+    flacdec::skim_frame(bytes + off, len, channels, bps, max_block_size, max_bps, lengths != nullptr, kCrc, rec, &num);
   }
   recs[f] = rec;
   if (nums) nums[f] = num;
@@ -99,10 +100,12 @@ __global__ void __launch_bounds__(256) crc16_kernel(const uint8_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------- reconstruction: one lane per subframe
-template <int MAXP, bool VERIFY>
-__device__ bool run_subframe(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t sbps,
-                             uint32_t ch_tag, uint32_t c, int32_t* row, const int32_t* erow, int32_t* stage) {
-  flacdec::SubDecoder<MAXP> d;
+// WIDE, on: the decoder instance and the lane's flag (AT_WAVE_DECODER); a lane that is not on is idle
+template <int MAXP, bool VERIFY, bool WIDE>
+__device__ __forceinline__ bool run_subframe(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t sbps,
+                             uint32_t ch_tag, uint32_t c, int32_t* row, const int32_t* erow, int32_t* stage, bool on) {
+  if (!on) bs = 0;
+  typename flacdec::Decoder<MAXP, WIDE>::type d;
   if (bs) d.init(fp, flen, start, bs, sbps);
   const int32_t* mem = VERIFY ? erow : row;
   const bool vec = (reinterpret_cast<uintptr_t>(mem) & 15u) == 0;
@@ -131,7 +134,9 @@ __device__ bool run_subframe(const uint8_t* fp, uint32_t flen, uint32_t start, u
   return bad;
 }
 
-template <bool VERIFY>
+// DEEP: the launch's stream takes the wide decoder (AT_WAVE_DECODER; bps is the launch's, so every wave of a deep
+// launch is wide)
+template <bool VERIFY, bool DEEP>
 __global__ void __launch_bounds__(256) subframe_kernel(const uint8_t* __restrict__ bytes,
                                                        const uint64_t* __restrict__ offsets,
                                                        const FrameRec* __restrict__ recs,
@@ -166,8 +171,9 @@ __global__ void __launch_bounds__(256) subframe_kernel(const uint8_t* __restrict
   const int32_t* erow = (VERIFY && live) ? expected + row0 : nullptr;
   int32_t* stage = stage_all + threadIdx.x * kStage;
   const int bucket = lane_bucket(fp, flen, start, bs, sbps);
-  bool bad;
-  AT_WAVE_BUCKET(bucket, bad = run_subframe<MAXP, VERIFY>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage));
+  bool bad = false;
+  AT_WAVE_DECODER(DEEP, bucket, flacdec::needs_wide(bps),
+                  bad |= run_subframe<MAXP, VERIFY, WIDE>(fp, flen, start, bs, sbps, ch_tag, c, row, erow, stage, ON));
   if (!VERIFY && live)
     for (uint32_t t = bs; t < max_block_size; ++t) row[t] = 0;  // the rest of the row; all of it for a bad frame
   if (bad) atomicOr(&mism[lf], flacdec::MISMATCH);
@@ -188,31 +194,39 @@ size_t decode_scratch_bytes(size_t n_frames) { return align256(n_frames * sizeof
 
 hipError_t launch_decode_frames(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets,
                                 const uint32_t* lengths, uint32_t n_frames, uint32_t channels, uint32_t bps,
-                                uint32_t max_block_size, int32_t* out, const int32_t* expected, size_t stride,
-                                uint32_t* block_sizes, uint64_t* numbers, uint32_t* status, void* scratch,
-                                hipStream_t stream) {
+                                uint32_t max_block_size, uint32_t max_bps, int32_t* out, const int32_t* expected,
+                                size_t stride, uint32_t* block_sizes, uint64_t* numbers, uint32_t* status,
+                                void* scratch, hipStream_t stream) {
   FrameRec* recs = static_cast<FrameRec*>(scratch);
   uint64_t* nums = reinterpret_cast<uint64_t*>(static_cast<char*>(scratch) + align256(n_frames * sizeof(FrameRec)));
   hipLaunchKernelGGL(skim_kernel, dim3(ceil_div(n_frames, 256)), dim3(256), 0, stream, bytes, n_bytes, offsets,
-                     lengths, n_frames, nullptr, channels, bps, max_block_size, recs, nums);
+                     lengths, n_frames, nullptr, channels, bps, max_block_size, max_bps, recs, nums);
   hipLaunchKernelGGL(crc16_kernel, dim3(ceil_div(n_frames, 4)), dim3(256), 0, stream, bytes, offsets, n_frames,
                      nullptr, recs);
   const uint32_t per_block = 256 / channels;
   const dim3 grid(ceil_div(n_frames, per_block)), block(per_block * channels);
-  if (expected)
-    hipLaunchKernelGGL(subframe_kernel<true>, grid, block, 0, stream, bytes, offsets, recs, nums, n_frames, channels,
-                       bps, max_block_size, nullptr, expected, stride, nullptr, nullptr, status);
+  const bool deep = flacdec::needs_wide(bps);
+  if (expected && deep)
+    hipLaunchKernelGGL((subframe_kernel<true, true>), grid, block, 0, stream, bytes, offsets, recs, nums, n_frames,
+                       channels, bps, max_block_size, nullptr, expected, stride, nullptr, nullptr, status);
+  else if (expected)
+    hipLaunchKernelGGL((subframe_kernel<true, false>), grid, block, 0, stream, bytes, offsets, recs, nums, n_frames,
+                       channels, bps, max_block_size, nullptr, expected, stride, nullptr, nullptr, status);
+  else if (deep)
+    hipLaunchKernelGGL((subframe_kernel<false, true>), grid, block, 0, stream, bytes, offsets, recs, nums, n_frames,
+                       channels, bps, max_block_size, out, nullptr, stride, block_sizes, numbers, status);
   else
-    hipLaunchKernelGGL(subframe_kernel<false>, grid, block, 0, stream, bytes, offsets, recs, nums, n_frames, channels,
-                       bps, max_block_size, out, nullptr, stride, block_sizes, numbers, status);
+    hipLaunchKernelGGL((subframe_kernel<false, false>), grid, block, 0, stream, bytes, offsets, recs, nums, n_frames,
+                       channels, bps, max_block_size, out, nullptr, stride, block_sizes, numbers, status);
   return hipGetLastError();
 }
 
 // skim_kernel in index mode and crc16_kernel for the frame index (stream_index.cpp)
 hipError_t launch_frame_skim(const uint8_t* bytes, uint64_t n_bytes, const uint64_t* offsets, uint32_t n,
-                             const uint32_t* n_dev, uint32_t channels, uint32_t bps, void* recs, hipStream_t stream) {
+                             const uint32_t* n_dev, uint32_t channels, uint32_t bps, uint32_t max_bps, void* recs,
+                             hipStream_t stream) {
   hipLaunchKernelGGL(skim_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, bytes, n_bytes, offsets, nullptr, n, n_dev,
-                     channels, bps, 65536u, static_cast<FrameRec*>(recs), nullptr);
+                     channels, bps, 65536u, max_bps, static_cast<FrameRec*>(recs), nullptr);
   return hipGetLastError();
 }
 

@@ -30,7 +30,11 @@ namespace flacdec {
 // status bits (FLACENC_HIP_DECODE_* in include/flacenc_hip.h)
 constexpr uint32_t BAD_HEADER = 1u, HEADER_CRC = 2u, FRAME_CRC = 4u, PARSE = 8u, LENGTH = 16u, STREAM_MISMATCH = 32u,
                    UNSUPPORTED = 64u, MISMATCH = 128u;
-constexpr uint32_t MAX_CHANNELS = 8, MAX_BPS = 24;
+constexpr uint32_t MAX_CHANNELS = 8;
+// The depth limit is the caller's (flacenc_hip_set_max_bits_per_sample): MAX_BPS is the default and what callers without
+// a handle pass, MAX_BPS_WIDE the most the format allows.  A frame deeper than WIDE_ABOVE_BPS is reconstructed by the
+// wide decoder (WideSubDecoder below), every other frame by SubDecoder.
+constexpr uint32_t MAX_BPS = 24, MAX_BPS_WIDE = 32, WIDE_ABOVE_BPS = 24;
 
 // ---- CRCs (RFC 9639 section 9.1.8: CRC-8 poly 0x07, section 9.3: CRC-16 poly 0x8005; MSB first, init 0) ----
 struct CrcTables {
@@ -138,6 +142,12 @@ struct BitReader {
     if (n == 0 || n == 32) return static_cast<int32_t>(v);
     return static_cast<int32_t>(v << (32 - n)) >> (32 - n);
   }
+  FD_HD int64_t s64(uint32_t n) {  // two's complement, n <= 33: the samples of a 33-bit side subframe
+    if (n <= 32) return s(n);
+    const uint64_t hi = u(n - 32);  // two reads, so that u() keeps its 32-bit contract
+    const uint64_t v = (hi << 32) | u(32);
+    return static_cast<int64_t>(v << (64 - n)) >> (64 - n);
+  }
   FD_HD void skip(uint32_t n) {
     while (n > 32) {
       u(32);
@@ -194,9 +204,10 @@ struct Header {
   uint64_t number;
 };
 
-// `len` is what the frame may occupy; status 0 or BAD_HEADER / HEADER_CRC / STREAM_MISMATCH / UNSUPPORTED
+// `len` is what the frame may occupy; status 0 or BAD_HEADER / HEADER_CRC / STREAM_MISMATCH / UNSUPPORTED.  max_bps is
+// the depth limit: a header that says more bits per sample is UNSUPPORTED.
 FD_HD uint32_t parse_header(const uint8_t* p, uint32_t len, uint32_t channels, uint32_t bits_per_sample,
-                            uint32_t max_block_size, const CrcTables& tab, Header& h) {
+                            uint32_t max_block_size, uint32_t max_bps, const CrcTables& tab, Header& h) {
   BitReader r;
   r.init(p, len, 0);
   if (r.u(15) != 0x7FFCu) return BAD_HEADER;  // 14-bit sync + the reserved bit
@@ -243,7 +254,7 @@ FD_HD uint32_t parse_header(const uint8_t* p, uint32_t len, uint32_t channels, u
                          : 32u;
   uint32_t st = 0;
   if (h.channels != channels || h.bps != bits_per_sample) st |= STREAM_MISMATCH;
-  if (h.bps > MAX_BPS || bs > max_block_size) st |= UNSUPPORTED;
+  if (h.bps > max_bps || bs > max_block_size) st |= UNSUPPORTED;
   return st;
 }
 
@@ -393,14 +404,14 @@ struct FrameRec {
 // Header + every subframe's codes.  `len` is the frame's byte span (decode: lengths[f]; index: what is left of the
 // buffer).  check_length: LENGTH when the parsed length differs from len.  The CRC-16 is left to the caller.
 FD_HD void skim_frame(const uint8_t* p, uint32_t len, uint32_t channels, uint32_t bps, uint32_t max_block_size,
-                      bool check_length, const CrcTables& tab, FrameRec& rec, uint64_t* number) {
+                      uint32_t max_bps, bool check_length, const CrcTables& tab, FrameRec& rec, uint64_t* number) {
   rec.status = 0;
   rec.block_size = 0;
   rec.info = 0;
   rec.len = 0;
   for (uint32_t c = 0; c < MAX_CHANNELS; ++c) rec.sub_bit[c] = 0;
   Header h;
-  uint32_t st = parse_header(p, len, channels, bps, max_block_size, tab, h);
+  uint32_t st = parse_header(p, len, channels, bps, max_block_size, max_bps, tab, h);
   if (number) *number = st & (BAD_HEADER | HEADER_CRC) ? 0 : h.number;
   if (st) {
     rec.status = st;
@@ -530,6 +541,123 @@ FD_HD void undo_stereo(uint32_t ch_tag, int32_t& a, int32_t& b) {
     b = static_cast<int32_t>(static_cast<uint32_t>(m) - static_cast<uint32_t>(s)) >> 1;
   }
 }
+
+// ---- the wide forms: frames of more than WIDE_ABOVE_BPS bits per sample ----
+// The side subframe of a 32-bit stereo frame carries 33-bit samples, and undoing mid/side forms (mid << 1 | side & 1)
+// +- side, which reaches 34 bits.  The wide decoder therefore keeps its history, its constant and its value in 64 bits:
+// the prediction is a sum of at most 32 products of a 15-bit coefficient and a 33-bit sample, below 2^52, and
+// e + (pred >> shift) with a 32-bit residual stays below 2^53.  The value rule: on a valid stream every channel value
+// behind undo_stereo_wide fits 32 bits, and that int32_t is the result; on an invalid stream that passes both CRCs the
+// result is the low 32 bits of the same computation carried out in two's-complement 64-bit arithmetic (sums, products
+// and left shifts wrap at 64 bits, right shifts are arithmetic) -- not the narrow decoder's truncation to i32 at every
+// step.  Both builds run this one code, so they agree on every input.  Residuals stay int32_t: a valid stream's fit
+// (RFC 9639 section 9.2.7.3) and residual_next rejects longer codes.
+// WideSubDecoder is SubDecoder line for line but for the value type, s64 in place of s and the 64-bit wrap: the narrow
+// one is kept as it was on purpose, so a change to either's parse steps (init, the order of reads in next) goes into
+// both.
+template <int MAXP>
+struct WideSubDecoder {
+  BitReader warm;  // the warm-up samples (Verbatim: every sample)
+  BitReader res;   // the residual
+  ResidualState rs;
+  uint32_t kind, order, wasted, ebps, shift, t, warm_n;
+  int64_t cval;
+  int32_t coef[MAXP];
+  int64_t hist[MAXP];  // hist[0] = the previous sample
+
+  FD_HD void init(const uint8_t* p, uint32_t len, uint32_t start_bit, uint32_t bs, uint32_t sbps) {
+    BitReader r;
+    r.init(p, len, start_bit);
+    SubInfo si;
+    parse_subframe_header(r, bs, sbps, si);
+    kind = si.kind;
+    order = si.order;
+    wasted = si.wasted;
+    ebps = si.ebps;
+    shift = 0;
+    t = 0;
+    cval = 0;
+FD_UNROLL
+    for (int j = 0; j < MAXP; ++j) {
+      coef[j] = 0;
+      hist[j] = 0;
+    }
+    warm = r;
+    warm_n = kind == KIND_VERBATIM ? bs : order;
+    if (kind == KIND_CONSTANT) {
+      cval = r.s64(ebps);
+      return;
+    }
+    if (kind == KIND_VERBATIM) return;
+    r.skip_bits(static_cast<uint64_t>(ebps) * order);
+    if (kind == KIND_FIXED) {
+      const int32_t o = static_cast<int32_t>(order);
+      coef[0] = o;
+      if (MAXP > 1) coef[1 % MAXP] = o == 2 ? -1 : o == 3 ? -3 : o == 4 ? -6 : 0;
+      if (MAXP > 2) coef[2 % MAXP] = o == 3 ? 1 : o == 4 ? 4 : 0;
+      if (MAXP > 3) coef[3 % MAXP] = o == 4 ? -1 : 0;
+    } else {
+      const uint32_t prec = r.u(4) + 1;
+      shift = static_cast<uint32_t>(r.s(5));
+FD_UNROLL
+      for (int j = 0; j < MAXP; ++j)
+        if (static_cast<uint32_t>(j) < order) coef[j] = r.s(prec);
+    }
+    res = r;
+    residual_begin(res, bs, order, rs);
+  }
+
+  FD_HD int64_t next() {
+    int64_t v;
+    if (t < warm_n) {
+      v = warm.s64(ebps);
+    } else if (kind == KIND_CONSTANT) {
+      v = cval;
+    } else {
+      uint32_t bad = 0;
+      residual_partition(res, order, rs);
+      const int32_t e = residual_next(res, rs, &bad);
+      uint64_t pred = 0;  // unsigned: wraps at 64 bits on an invalid stream
+FD_UNROLL
+      for (int j = 0; j < MAXP; ++j)
+        pred += static_cast<uint64_t>(static_cast<int64_t>(coef[j])) * static_cast<uint64_t>(hist[j]);
+      v = static_cast<int64_t>(static_cast<uint64_t>(static_cast<int64_t>(e)) +
+                               static_cast<uint64_t>(static_cast<int64_t>(pred) >> shift));
+    }
+FD_UNROLL
+    for (int j = MAXP - 1; j > 0; --j) hist[j] = hist[j - 1];
+    hist[0] = v;
+    ++t;
+    return static_cast<int64_t>(static_cast<uint64_t>(v) << wasted);
+  }
+};
+
+// undo_stereo on the wide decoder's values; the caller keeps the low 32 bits of a and b
+FD_HD void undo_stereo_wide(uint32_t ch_tag, int64_t& a, int64_t& b) {
+  const uint64_t ua = static_cast<uint64_t>(a), ub = static_cast<uint64_t>(b);
+  if (ch_tag == 8) {
+    b = static_cast<int64_t>(ua - ub);
+  } else if (ch_tag == 9) {
+    a = static_cast<int64_t>(ua + ub);
+  } else if (ch_tag == 10) {
+    const uint64_t m = (ua << 1) | (ub & 1u);
+    a = static_cast<int64_t>(m + ub) >> 1;
+    b = static_cast<int64_t>(m - ub) >> 1;
+  }
+}
+
+// the decoder of a frame: Decoder<MAXP, WIDE>::type
+template <int MAXP, bool WIDE>
+struct Decoder {
+  typedef SubDecoder<MAXP> type;
+};
+template <int MAXP>
+struct Decoder<MAXP, true> {
+  typedef WideSubDecoder<MAXP> type;
+};
+
+// does a frame of `bps` bits per sample take the wide decoder?
+FD_HD bool needs_wide(uint32_t bps) { return bps > WIDE_ABOVE_BPS; }
 
 // order bucket of the decoder's register history
 FD_HD int order_bucket(uint32_t order) { return order <= 4 ? 4 : order <= 8 ? 8 : order <= 16 ? 16 : 32; }

@@ -122,6 +122,46 @@ __device__ inline int lane_bucket(const uint8_t* fp, uint32_t flen, uint32_t sta
     }                                 \
   } while (0)
 
+// The wide ladder: AT_WAVE_BUCKET once more, with WIDE (a constant expression) the decoder instance and ON (a lane's
+// flag) whether the lane takes part.  `deep` is the kernel's template flag: the launch may hold frames that take the
+// wide decoder.  A kernel that is not deep holds the narrow instance alone, with every lane on -- the code, and the
+// registers, it had before there was a wide one; a launch of shallow streams runs that kernel.  In a deep kernel `wide`
+// is flacdec::needs_wide of the depth of the lane's frame; both lanes of a stereo pair hold the same frame, so they
+// agree and stay together.  A wave none of whose lanes is wide runs the narrow instance with every lane on.  A wave
+// with a wide lane runs the wide instance on its wide lanes and, where it also holds others, the narrow instance on
+// those first -- so what a frame decodes to never depends on its neighbours in the wave, also where the two value rules
+// (flac_decode_core.h) differ.  A lane that is not ON runs the statement as an idle lane does.
+#define AT_WAVE_DECODER(deep, bucket, wide, ...)            \
+  do {                                                      \
+    if constexpr (deep) {                                   \
+      if (__any(wide)) {                                    \
+        if (__any(!(wide))) {                               \
+          constexpr bool WIDE = false;                      \
+          const bool ON = !(wide);                          \
+          AT_WAVE_BUCKET(ON ? (bucket) : 4, __VA_ARGS__);   \
+        }                                                   \
+        constexpr bool WIDE = true;                         \
+        const bool ON = (wide);                             \
+        AT_WAVE_BUCKET(ON ? (bucket) : 4, __VA_ARGS__);     \
+      } else {                                              \
+        constexpr bool WIDE = false;                        \
+        const bool ON = true;                               \
+        AT_WAVE_BUCKET(bucket, __VA_ARGS__);                \
+      }                                                     \
+    } else {                                                \
+      constexpr bool WIDE = false;                          \
+      const bool ON = true;                                 \
+      AT_WAVE_BUCKET(bucket, __VA_ARGS__);                  \
+    }                                                       \
+  } while (0)
+
+// does a table hold a stream that takes the wide decoder?  (host: which kernel a batch call launches)
+inline bool any_deep_stream(const flacenc_hip_stream_desc* d, size_t n) {
+  for (size_t s = 0; s < n; ++s)
+    if (flacdec::needs_wide(d[s].bits_per_sample)) return true;
+  return false;
+}
+
 // The sample step of channel c: the subframe's next value, exchanged with the pair lane and stereo undone where the
 // frame is a stereo pair (which sits on an even / odd lane pair; both lanes take the step together).
 template <int MAXP>
@@ -136,14 +176,33 @@ __device__ __forceinline__ int32_t next_sample(flacdec::SubDecoder<MAXP>& d, uin
   return v;
 }
 
+// The same step of the wide decoder: the pair lanes exchange the full 64-bit value (two 32-bit moves), stereo is undone
+// in 64 bits and the low 32 bits are the sample (flac_decode_core.h's value rule).
+template <int MAXP>
+__device__ __forceinline__ int32_t next_sample(flacdec::WideSubDecoder<MAXP>& d, uint32_t ch_tag, uint32_t c) {
+  int64_t v = d.next();
+  if (ch_tag >= 8) {
+    const uint64_t u = static_cast<uint64_t>(v);
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(u), 1), hi = __shfl_xor(static_cast<uint32_t>(u >> 32), 1);
+    const int64_t o = static_cast<int64_t>(static_cast<uint64_t>(hi) << 32 | lo);
+    int64_t a = c == 0 ? v : o, b = c == 0 ? o : v;
+    flacdec::undo_stereo_wide(ch_tag, a, b);
+    v = c == 0 ? a : b;
+  }
+  return static_cast<int32_t>(static_cast<uint64_t>(v));
+}
+
 // Samples [skip, skip + take) of channel c of a frame of `bs` samples into packed PCM: sample t at dst + ((t - skip) *
 // channels + c) * B, the low B bytes of its value, little-endian.  The recurrence runs from sample 0 and stops at
 // skip + take.  Whole samples where the address allows, else bytes: a neighbouring sample's bytes are another lane's and
-// are never read back.  Both lanes of a stereo pair have the same bounds, so the exchange stays convergent.
-template <int MAXP>
-__device__ void write_pcm(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
-                          uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t channels, uint32_t B, uint8_t* dst) {
-  flacdec::SubDecoder<MAXP> d;
+// are never read back.  Both lanes of a stereo pair have the same bounds, so the exchange stays convergent.  WIDE, on: the
+// instance and the lane's flag (AT_WAVE_DECODER); a lane that is not on is idle.
+template <int MAXP, bool WIDE>
+__device__ __forceinline__ void write_pcm(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
+                          uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t channels, uint32_t B, uint8_t* dst,
+                          bool on) {
+  if (!on) bs = skip = take = 0;
+  typename flacdec::Decoder<MAXP, WIDE>::type d;
   if (bs) d.init(fp, flen, start, bs, sbps);
   uint8_t* p = dst + static_cast<size_t>(c) * B;
   const size_t step = static_cast<size_t>(channels) * B;
@@ -203,12 +262,14 @@ __device__ __forceinline__ void planar_flush(PlanarStage& s, uint32_t* stage) {
 // end: the elements up to the first boundary leave one by one (streamplanar::split's head), whole vectors as 16-byte
 // stores, and what is left behind the last boundary one by one.  One loop over the recurrence, as in write_pcm: both
 // lanes of a stereo pair have the same skip and take -- only their rows differ -- so the exchange stays convergent
-// whatever the rows' alignment.
-template <int MAXP>
-__device__ void write_planar(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
+// whatever the rows' alignment.  A float32 element of a stream of more than 24 bits is float(v), rounded to nearest
+// even, times 2^-(bits - 1): it is no longer exact and can equal 1.0 (streamplanar::element).
+template <int MAXP, bool WIDE>
+__device__ __forceinline__ void write_planar(const uint8_t* fp, uint32_t flen, uint32_t start, uint32_t bs, uint32_t skip, uint32_t take,
                              uint32_t sbps, uint32_t ch_tag, uint32_t c, uint32_t sample_format, float scale,
-                             uint32_t* row, uint32_t* stage) {
-  flacdec::SubDecoder<MAXP> d;
+                             uint32_t* row, uint32_t* stage, bool on) {
+  if (!on) bs = skip = take = 0;
+  typename flacdec::Decoder<MAXP, WIDE>::type d;
   if (bs) d.init(fp, flen, start, bs, sbps);
   PlanarStage s;
   s.lead = streamplanar::lead(reinterpret_cast<uintptr_t>(row));

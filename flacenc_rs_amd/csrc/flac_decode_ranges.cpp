@@ -159,7 +159,8 @@ __global__ void __launch_bounds__(256) ranges_enumerate_kernel(const uint64_t* _
 // ---------------------------------------------------------------- reconstruction: one lane per subframe
 // The range-frames [k_lo, k_hi) all belong to streams of `channels` channels; lane (range-frame, c) as in
 // streams_decode_kernel.  A range's PCM starts at out + where[q] (`where` given: the compact staging of the host path)
-// or at out + its out_offset.
+// or at out + its out_offset.  DEEP: see AT_WAVE_DECODER.
+template <bool DEEP>
 __global__ void __launch_bounds__(256) ranges_decode_kernel(const uint8_t* __restrict__ bytes,
                                                             const Desc* __restrict__ descs,
                                                             const Range* __restrict__ ranges,
@@ -203,12 +204,14 @@ __global__ void __launch_bounds__(256) ranges_decode_kernel(const uint8_t* __res
   }
   const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
   const int bucket = lane_bucket(fp, flen, start, bs, sbps);
-  AT_WAVE_BUCKET(bucket, write_pcm<MAXP>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst));
+  AT_WAVE_DECODER(DEEP, bucket, flacdec::needs_wide(bps),
+                  write_pcm<MAXP, WIDE>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, channels, B, dst, ON));
 }
 
 // The planar form: the same lanes under the same rules, each with its row of the range's slot -- channel c's n_samples
 // elements (`where` given: its `written` elements, the rows packed back to back in compact staging) -- and the planar
 // writer (write_planar, flac_decode_device.h) in place of write_pcm.
+template <bool DEEP>
 __global__ void __launch_bounds__(256) ranges_decode_planar_kernel(const uint8_t* __restrict__ bytes,
                                                                    const Desc* __restrict__ descs,
                                                                    const Range* __restrict__ ranges,
@@ -257,8 +260,9 @@ __global__ void __launch_bounds__(256) ranges_decode_planar_kernel(const uint8_t
   const float scale = streamplanar::scale_of(bps);
   uint32_t* stage = stage_all + threadIdx.x * kPlanarStage;
   const int bucket = lane_bucket(fp, flen, start, bs, sbps);
-  AT_WAVE_BUCKET(bucket, write_planar<MAXP>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, sample_format, scale,
-                                            reinterpret_cast<uint32_t*>(dst), stage));
+  AT_WAVE_DECODER(DEEP, bucket, flacdec::needs_wide(bps),
+                  write_planar<MAXP, WIDE>(fp, flen, start, bs, skip, take, sbps, ch_tag, c, sample_format, scale,
+                                           reinterpret_cast<uint32_t*>(dst), stage, ON));
 }
 
 // The zero pass of the planar form in device memory: elements [written, n_samples) of every row of every range.  Rows
@@ -316,9 +320,9 @@ int decode_ranges_call(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_b
   }
   const Desc* table = static_cast<const Desc*>(streams);
   const Range* rtable = static_cast<const Range*>(ranges);
-  int rc = streamranges::check_spans(table, n_streams, n_bytes);
+  int rc = streamranges::check_spans(table, n_streams, n_bytes, h->max_bps);
   if (rc == FLACENC_HIP_ERR_UNSUPPORTED) {
-    h->last_error = who + ": a stream's bits_per_sample not in 4..=24";
+    h->last_error = who + ": a stream's bits_per_sample not in 4..=24 (4..=32 with flacenc_hip_set_max_bits_per_sample)";
     return rc;
   }
   if (rc != FLACENC_HIP_OK) {
@@ -433,20 +437,29 @@ int decode_ranges_call(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_b
     if ((rc = ensure(h, h->d_cont[0], static_cast<size_t>(pcm_bytes) + 16)) != FLACENC_HIP_OK) return rc;
     d_out = static_cast<uint8_t*>(h->d_cont[0].ptr);
   }
+  const bool deep = any_deep_stream(table, n_streams);
   for (uint32_t c = 1; c <= 8; ++c) {
     if (rslot_lo.lo[c] == rslot_lo.lo[c + 1]) continue;
     const uint32_t k_lo = static_cast<uint32_t>(r_meta[M_CLASS + c]), k_hi = static_cast<uint32_t>(r_meta[M_CLASS + c + 1]);
     const uint32_t per_block = 256 / c;
     // (a class whose ranges touch no frame still counts as a launch of the plan: the plan depends on the classes only)
     const dim3 grid(k_hi > k_lo ? ceil_div(k_hi - k_lo, per_block) : 1), block(per_block * c);
-    if (planar)
-      COUNTED_LAUNCH(plan, ranges_decode_planar_kernel, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
+    if (planar && deep)
+      COUNTED_LAUNCH(plan, ranges_decode_planar_kernel<true>, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
                      ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo,
                      k_hi, c, where, sample_format, d_out);
+    else if (planar)
+      COUNTED_LAUNCH(plan, ranges_decode_planar_kernel<false>, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
+                     ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo,
+                     k_hi, c, where, sample_format, d_out);
+    else if (deep)
+      COUNTED_LAUNCH(plan, ranges_decode_kernel<true>, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
+                     ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo,
+                     k_hi, c, where, d_out);
     else
-      COUNTED_LAUNCH(plan, ranges_decode_kernel, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm, ix.base,
-                     ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo, k_hi, c,
-                     where, d_out);
+      COUNTED_LAUNCH(plan, ranges_decode_kernel<false>, grid, block, 0, st, ix.d_bytes, ix.descs, d_ranges, rperm,
+                     ix.base, ix.pcm, ix.f_node, ix.f_slot, rf_range, rf_frame, r_written, ix.cand_pos, ix.recs, k_lo,
+                     k_hi, c, where, d_out);
   }
   if (planar && !host) {  // the rows' tails, all ranges in one launch (host memory: the host threads zero them below)
     uint64_t longest = 0;

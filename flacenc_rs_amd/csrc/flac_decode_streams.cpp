@@ -76,7 +76,8 @@ __global__ void __launch_bounds__(256) streams_totals_kernel(const Desc* __restr
 
 // The frames [m_lo, m_hi) of the sequence all have `channels` channels; lane (frame, c) as in subframe_kernel.  A frame
 // behind its stream's cut keeps its lanes idle.  A stream's PCM starts at out + where[stream] (`where` given: the
-// compact staging of the host path) or at out + its out_offset.
+// compact staging of the host path) or at out + its out_offset.  DEEP: see AT_WAVE_DECODER.
+template <bool DEEP>
 __global__ void __launch_bounds__(256) streams_decode_kernel(const uint8_t* __restrict__ bytes,
                                                              const Desc* __restrict__ descs,
                                                              const uint32_t* __restrict__ perm,
@@ -113,7 +114,8 @@ __global__ void __launch_bounds__(256) streams_decode_kernel(const uint8_t* __re
   }
   const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
   const int bucket = lane_bucket(fp, flen, start, bs, sbps);
-  AT_WAVE_BUCKET(bucket, write_pcm<MAXP>(fp, flen, start, bs, 0, bs, sbps, ch_tag, c, channels, B, dst));
+  AT_WAVE_DECODER(DEEP, bucket, flacdec::needs_wide(bps),
+                  write_pcm<MAXP, WIDE>(fp, flen, start, bs, 0, bs, sbps, ch_tag, c, channels, B, dst, ON));
 }
 
 // the digest of the empty string, for the streams of a call that wrote nothing
@@ -139,9 +141,10 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   const Desc* table = static_cast<const Desc*>(streams);
-  int rc = streambatch::check_streams(table, n_streams, n_bytes, out_bytes);
+  int rc = streambatch::check_streams(table, n_streams, n_bytes, out_bytes, h->max_bps);
   if (rc == FLACENC_HIP_ERR_UNSUPPORTED) {
-    h->last_error = "decode_streams: a stream's bits_per_sample not in 4..=24";
+    h->last_error = "decode_streams: a stream's bits_per_sample not in 4..=24 (4..=32 with "
+                    "flacenc_hip_set_max_bits_per_sample)";
     return rc;
   }
   if (rc != FLACENC_HIP_OK) {
@@ -209,6 +212,7 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
 
   // ---- decode straight into packed PCM: one launch per channel count present ----
   uint8_t* d_out = out;
+  const bool deep = any_deep_stream(table, n_streams);
   const uint64_t pcm_bytes = host ? r_where[n_streams] : 0;
   if (host) {
     if ((rc = ensure(h, h->d_cont[0], static_cast<size_t>(pcm_bytes) + 16)) != FLACENC_HIP_OK) return rc;
@@ -219,9 +223,13 @@ int decode_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n_
     const uint32_t m_lo = static_cast<uint32_t>(r_base[ix.slot_lo[c]]), m_hi = static_cast<uint32_t>(r_base[ix.slot_lo[c + 1]]);
     const uint32_t per_block = 256 / c;
     // (a class whose streams hold no frame still counts as a launch of the plan: the plan depends on the classes only)
-    COUNTED_LAUNCH(plan, streams_decode_kernel, dim3(m_hi > m_lo ? ceil_div(m_hi - m_lo, per_block) : 1),
-                   dim3(per_block * c), 0, st, ix.d_bytes, ix.descs, ix.perm, ix.base, ix.pcm, ix.f_node, ix.f_slot,
-                   ix.s_accepted, ix.cand_pos, ix.recs, m_lo, m_hi, c, where, d_out);
+    const dim3 grid(m_hi > m_lo ? ceil_div(m_hi - m_lo, per_block) : 1), block(per_block * c);
+    if (deep)
+      COUNTED_LAUNCH(plan, streams_decode_kernel<true>, grid, block, 0, st, ix.d_bytes, ix.descs, ix.perm, ix.base,
+                     ix.pcm, ix.f_node, ix.f_slot, ix.s_accepted, ix.cand_pos, ix.recs, m_lo, m_hi, c, where, d_out);
+    else
+      COUNTED_LAUNCH(plan, streams_decode_kernel<false>, grid, block, 0, st, ix.d_bytes, ix.descs, ix.perm, ix.base,
+                     ix.pcm, ix.f_node, ix.f_slot, ix.s_accepted, ix.cand_pos, ix.recs, m_lo, m_hi, c, where, d_out);
   }
   HIP_TRY(h, hipGetLastError());
   if (md5) {

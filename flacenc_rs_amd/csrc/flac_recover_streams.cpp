@@ -259,6 +259,7 @@ __global__ void __launch_bounds__(256) recover_records_kernel(Frames f, uint64_t
 // ---------------------------------------------------------------- decode and zero pass
 // streams_decode_kernel with the frame's coded destination: the frames [m_lo, m_hi) all have `channels` channels; a
 // frame that is dropped or lies behind its stream's cut keeps its lanes idle (bs == 0), as both lanes of a pair do
+template <bool DEEP>
 __global__ void __launch_bounds__(256) recover_decode_kernel(const uint8_t* __restrict__ bytes, Frames f, uint32_t m_lo,
                                                              uint32_t m_hi, uint32_t channels,
                                                              const uint64_t* __restrict__ where,
@@ -287,7 +288,8 @@ __global__ void __launch_bounds__(256) recover_decode_kernel(const uint8_t* __re
   }
   const uint32_t sbps = flacdec::subframe_bps(bps, ch_tag, c);
   const int bucket = lane_bucket(fp, flen, start, bs, sbps);
-  AT_WAVE_BUCKET(bucket, write_pcm<MAXP>(fp, flen, start, bs, 0, bs, sbps, ch_tag, c, channels, B, dst));
+  AT_WAVE_DECODER(DEEP, bucket, flacdec::needs_wide(bps),
+                  write_pcm<MAXP, WIDE>(fp, flen, start, bs, 0, bs, sbps, ch_tag, c, channels, B, dst, ON));
 }
 
 // Workgroup `blockIdx.x` clears piece q of the gap in front of frame m, pc[m] <= blockIdx.x < pc[m + 1]: bytes
@@ -355,9 +357,10 @@ int recover_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   const Desc* table = static_cast<const Desc*>(streams);
-  int rc = streambatch::check_streams(table, n_streams, n_bytes, out_bytes);
+  int rc = streambatch::check_streams(table, n_streams, n_bytes, out_bytes, h->max_bps);
   if (rc == FLACENC_HIP_ERR_UNSUPPORTED) {
-    h->last_error = "recover_streams: a stream's bits_per_sample not in 4..=24";
+    h->last_error = "recover_streams: a stream's bits_per_sample not in 4..=24 (4..=32 with "
+                    "flacenc_hip_set_max_bits_per_sample)";
     return rc;
   }
   if (rc != FLACENC_HIP_OK) {
@@ -493,14 +496,18 @@ int recover_streams_impl(flacenc_hip_handle* h, const uint8_t* bytes, uint64_t n
     if ((rc = ensure(h, h->d_cont[0], static_cast<size_t>(pcm_bytes) + 16)) != FLACENC_HIP_OK) return rc;
     d_out = static_cast<uint8_t*>(h->d_cont[0].ptr);
   }
+  const bool deep = any_deep_stream(table, n_streams);
   // (the records: behind the one place the call can still end without having written anything)
   COUNTED_LAUNCH(plan, recover_records_kernel, per_frame, wg, 0, st, f, d_gaps, static_cast<uint64_t>(host ? gap_room : max_gaps));
   for (uint32_t c = 1; c <= 8; ++c) {
     if (ix.slot_lo[c] == ix.slot_lo[c + 1]) continue;
     const uint32_t m_lo = static_cast<uint32_t>(r_base[ix.slot_lo[c]]), m_hi = static_cast<uint32_t>(r_base[ix.slot_lo[c + 1]]);
     const uint32_t per_block = 256 / c;
-    COUNTED_LAUNCH(plan, recover_decode_kernel, dim3(m_hi > m_lo ? ceil_div(m_hi - m_lo, per_block) : 1),
-                   dim3(per_block * c), 0, st, ix.d_bytes, f, m_lo, m_hi, c, where, d_out);
+    const dim3 grid(m_hi > m_lo ? ceil_div(m_hi - m_lo, per_block) : 1), block(per_block * c);
+    if (deep)
+      COUNTED_LAUNCH(plan, recover_decode_kernel<true>, grid, block, 0, st, ix.d_bytes, f, m_lo, m_hi, c, where, d_out);
+    else
+      COUNTED_LAUNCH(plan, recover_decode_kernel<false>, grid, block, 0, st, ix.d_bytes, f, m_lo, m_hi, c, where, d_out);
   }
   // (a call without gaps still counts the launch: the plan does not depend on the damage)
   COUNTED_LAUNCH(plan, recover_zero_kernel, dim3(n_pieces ? static_cast<uint32_t>(n_pieces) : 1), wg, 0, st, f, where,

@@ -69,8 +69,9 @@ SB_HD uint64_t accepted_frames(const uint64_t* pcm, const uint64_t* bad, uint64_
 }
 
 // The descriptor table against the call's buffers: 0, FLACENC_HIP_ERR_BAD_ARGUMENT or FLACENC_HIP_ERR_UNSUPPORTED (the
-// first stream that fails decides).
-inline int check_streams(const flacenc_hip_stream_desc* d, size_t n, uint64_t n_bytes, uint64_t out_bytes) {
+// first stream that fails decides).  max_bps: the handle's depth limit (flacenc_hip_set_max_bits_per_sample).
+inline int check_streams(const flacenc_hip_stream_desc* d, size_t n, uint64_t n_bytes, uint64_t out_bytes,
+                         uint32_t max_bps = 24) {
   uint64_t end = 0;  // where the previous span ends
   for (size_t s = 0; s < n; ++s) {
     const flacenc_hip_stream_desc& x = d[s];
@@ -79,7 +80,7 @@ inline int check_streams(const flacenc_hip_stream_desc* d, size_t n, uint64_t n_
     if (x.out_capacity > out_bytes || x.out_offset > out_bytes - x.out_capacity) return FLACENC_HIP_ERR_BAD_ARGUMENT;
     if (x.channels < 1 || x.channels > 8 || x.max_block_size < 1 || x.max_block_size > 65536 || x.bytes_per_sample > 4)
       return FLACENC_HIP_ERR_BAD_ARGUMENT;
-    if (x.bits_per_sample < 4 || x.bits_per_sample > 24) return FLACENC_HIP_ERR_UNSUPPORTED;
+    if (x.bits_per_sample < 4 || x.bits_per_sample > max_bps) return FLACENC_HIP_ERR_UNSUPPORTED;
     if (x.bytes_per_sample < (x.bits_per_sample + 7) / 8) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   return FLACENC_HIP_OK;

@@ -37,7 +37,7 @@ constexpr uint64_t kIndexError = 0x8000000000000000ull;  // FLACENC_HIP_INDEX_ER
 // ---------------------------------------------------------------- span policies
 struct Span {
   uint64_t end;  // the first byte behind the span
-  uint32_t channels, bps;
+  uint32_t channels, bps, max_bps;  // max_bps: the handle's depth limit, the same for every span of a call
 };
 
 // a descriptor table; cand_stream[i] remembers the stream of candidate i
@@ -45,9 +45,10 @@ struct TableSpans {
   const Desc* descs;
   uint32_t n_streams;
   uint32_t* cand_stream;
+  uint32_t max_bps;
   __device__ uint32_t find(uint64_t p) const { return streambatch::stream_of_byte(descs, n_streams, p); }
   __device__ Span span(uint32_t s) const {
-    return {descs[s].offset + descs[s].n_bytes, descs[s].channels, descs[s].bits_per_sample};
+    return {descs[s].offset + descs[s].n_bytes, descs[s].channels, descs[s].bits_per_sample, max_bps};
   }
   __device__ void keep(uint32_t i, uint32_t s) const { cand_stream[i] = s; }
   __device__ Span of_candidate(uint32_t i) const { return span(cand_stream[i]); }
@@ -56,9 +57,9 @@ struct TableSpans {
 // one stream: [0, n_bytes)
 struct OneSpan {
   uint64_t n_bytes;
-  uint32_t channels, bps;
+  uint32_t channels, bps, max_bps;
   __device__ uint32_t find(uint64_t p) const { return p < n_bytes ? 0u : streambatch::NONE; }
-  __device__ Span span(uint32_t) const { return {n_bytes, channels, bps}; }
+  __device__ Span span(uint32_t) const { return {n_bytes, channels, bps, max_bps}; }
   __device__ void keep(uint32_t, uint32_t) const {}
   __device__ Span of_candidate(uint32_t) const { return span(0); }
 };
@@ -73,8 +74,8 @@ __device__ bool is_candidate(const uint8_t* bytes, uint64_t n_bytes, const Spans
   const Span x = spans.span(s);
   const uint64_t left = x.end - p;  // what the parse may read ends with the span
   flacdec::Header h;
-  return flacdec::parse_header(bytes + p, left > 64 ? 64u : static_cast<uint32_t>(left), x.channels, x.bps, 65536u, kCrc,
-                               h) == 0;
+  return flacdec::parse_header(bytes + p, left > 64 ? 64u : static_cast<uint32_t>(left), x.channels, x.bps, 65536u,
+                               x.max_bps, kCrc, h) == 0;
 }
 
 // WRITE false: block_counts[block] = its candidates.  WRITE true: block_offsets (their exclusive scan) in, the
@@ -170,7 +171,7 @@ __global__ void __launch_bounds__(256) streams_skim_kernel(const uint8_t* __rest
   FrameRec rec;
   uint64_t number = 0;
   flacdec::skim_frame(bytes + off, left > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(left), x.channels, x.bps,
-                      65536u, false, kCrc, rec, NUMBERS ? &number : nullptr);
+                      65536u, x.max_bps, false, kCrc, rec, NUMBERS ? &number : nullptr);
   recs[i] = rec;
   if (NUMBERS) numbers[i] = number << 1 | (bytes[off + 1] & 1u);
 }
@@ -189,7 +190,8 @@ void launch_skim(const uint8_t* bytes, uint64_t, const TableSpans& spans, const 
 }
 void launch_skim(const uint8_t* bytes, uint64_t n_bytes, const OneSpan& spans, const uint64_t* cand_pos,
                  const uint32_t* counters, uint32_t cap, FrameRec* recs, uint64_t*, hipStream_t st) {
-  (void)launch_frame_skim(bytes, n_bytes, cand_pos, cap, counters + C_CANDS, spans.channels, spans.bps, recs, st);
+  (void)launch_frame_skim(bytes, n_bytes, cand_pos, cap, counters + C_CANDS, spans.channels, spans.bps, spans.max_bps,
+                          recs, st);
 }
 
 // jump[0][i]: the verified candidate that starts where candidate i ends, kEnd at its span's end, kDead otherwise -- so a
@@ -455,7 +457,7 @@ size_t index_scratch_bytes(uint64_t n_bytes, size_t capacity) {
 }
 
 hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t channels, uint32_t bps,
-                               size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
+                               uint32_t max_bps, size_t max_frames, uint64_t* offsets, uint32_t* lengths, uint64_t* n_frames,
                                void* scratch, size_t capacity, hipStream_t stream) {
   const uint32_t n_blocks = ceil_div(n_bytes, kPosPerBlock);
   const uint32_t cap = static_cast<uint32_t>(capacity), levels = jump_levels(capacity);
@@ -474,7 +476,7 @@ hipError_t launch_index_frames(const uint8_t* bytes, uint64_t n_bytes, uint32_t 
   hipError_t e = hipMemsetAsync(counters, 0, 256, stream);
   if (e != hipSuccess) return e;
   if (n_blocks) {
-    e = launch_links(bytes, n_bytes, OneSpan{n_bytes, channels, bps}, n_blocks, block_counts, block_offsets, cand_pos,
+    e = launch_links(bytes, n_bytes, OneSpan{n_bytes, channels, bps, max_bps}, n_blocks, block_counts, block_offsets, cand_pos,
                      recs, jump, counters, capacity, nullptr, stream);
     if (e != hipSuccess) return e;
   }
@@ -605,7 +607,7 @@ int streamindex::build(flacenc_hip_handle* h, uint64_t* plan, const Request& rq,
 
   // ---- the segmented index ----
   if (n_blocks)
-    HIP_TRY(h, launch_links(d_bytes, n_bytes, TableSpans{descs, ns, reinterpret_cast<uint32_t*>(S + o_cstream)}, n_blocks,
+    HIP_TRY(h, launch_links(d_bytes, n_bytes, TableSpans{descs, ns, reinterpret_cast<uint32_t*>(S + o_cstream), h->max_bps}, n_blocks,
                             reinterpret_cast<uint64_t*>(S + o_bcount), reinterpret_cast<uint64_t*>(S + o_boff), cand_pos,
                             recs, jump, counters, capacity, plan, st, rq.resync ? &resync : nullptr));
   if (rq.resync) {

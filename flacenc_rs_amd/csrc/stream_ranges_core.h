@@ -80,13 +80,13 @@ SB_HD Window window(uint64_t pos, uint32_t bs, uint64_t a, uint64_t end) {
 
 // The stream table as flacenc_hip_decode_ranges reads it: the rules of streambatch::check_streams with out_offset and
 // out_capacity ignored.
-inline int check_spans(const flacenc_hip_stream_desc* d, size_t n, uint64_t n_bytes) {
+inline int check_spans(const flacenc_hip_stream_desc* d, size_t n, uint64_t n_bytes, uint32_t max_bps = 24) {
   uint64_t end = 0;
   for (size_t s = 0; s < n; ++s) {
     flacenc_hip_stream_desc x = d[s];
     x.out_offset = x.out_capacity = 0;
     if (x.offset < end) return FLACENC_HIP_ERR_BAD_ARGUMENT;
-    const int rc = streambatch::check_streams(&x, 1, n_bytes, 0);
+    const int rc = streambatch::check_streams(&x, 1, n_bytes, 0, max_bps);
     if (rc != FLACENC_HIP_OK) return rc;
     end = x.offset + x.n_bytes;
   }

@@ -38,7 +38,7 @@ uint32_t vbs_tiling_node(uint32_t mask, uint32_t levels, uint32_t t) { return vb
 uint32_t vbs_parse_header(const uint8_t* p, uint32_t len, uint32_t channels, uint32_t bits_per_sample,
                           uint32_t* out, uint64_t* number) {
   flacdec::Header h{};
-  const uint32_t st = flacdec::parse_header(p, len, channels, bits_per_sample, 65536, kTab, h);
+  const uint32_t st = flacdec::parse_header(p, len, channels, bits_per_sample, 65536, flacdec::MAX_BPS, kTab, h);
   out[0] = h.block_size;
   out[1] = h.channels;
   out[2] = h.bps;
@@ -85,7 +85,7 @@ int main() {
       const uint32_t hv = vbs::write_variable_header(fixed, uint64_t(v), var);
       check(hv == hf - 1 + vbs::coded_number_bytes(uint64_t(v)), "variable header length", hv, hf);
       flacdec::Header h{};
-      const uint32_t st = flacdec::parse_header(var, hv, 2, 16, 65536, kTab, h);
+      const uint32_t st = flacdec::parse_header(var, hv, 2, 16, 65536, flacdec::MAX_BPS, kTab, h);
       check(st == 0 && h.variable == 1 && h.number == uint64_t(v) && h.header_bytes == hv && h.block_size == 4096,
             "parse_header of the variable header", h.number, uint64_t(v));
     }

@@ -47,14 +47,15 @@ def build_sanitized_driver(out_dir: str | None = None) -> str:
 
 
 def run_sanitized(exe: str, data: bytes, offsets, lengths, channels: int, bits_per_sample: int, max_block_size: int,
-                  work_dir: str):
-    """-> (status, block_sizes, samples, index offsets, index ok, the driver's stderr); raises on any report."""
+                  work_dir: str, max_bits_per_sample: int = 0):
+    """-> (status, block_sizes, samples, index offsets, index ok, the driver's stderr); raises on any report.
+    max_bits_per_sample: the depth limit the driver decodes under, 0 (= 24), 24 or 32."""
     off = np.ascontiguousarray(offsets, np.uint64)
     ln = np.ascontiguousarray(lengths, np.uint32)
     n = len(off)
     src, dst = os.path.join(work_dir, "corpus.bin"), os.path.join(work_dir, "result.bin")
     with open(src, "wb") as f:
-        f.write(np.array([n], np.uint64).tobytes() + np.array([channels, bits_per_sample, max_block_size, 0],
+        f.write(np.array([n], np.uint64).tobytes() + np.array([channels, bits_per_sample, max_block_size, max_bits_per_sample],
                                                                 np.uint32).tobytes())
         f.write(np.array([len(data)], np.uint64).tobytes() + off.tobytes() + ln.tobytes() + bytes(data))
     p = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
@@ -81,12 +82,27 @@ class DecoderCpu:
         L.fdc_decode_frames.restype = C.c_int
         L.fdc_index_frames.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_size_t, vp, vp, vp]
         L.fdc_index_frames.restype = C.c_int
+        # the same two with the depth limit (flacenc_hip_set_max_bits_per_sample) behind the other arguments
+        L.fdc_decode_frames_depth.argtypes = L.fdc_decode_frames.argtypes + [C.c_uint32]
+        L.fdc_decode_frames_depth.restype = C.c_int
+        L.fdc_index_frames_depth.argtypes = L.fdc_index_frames.argtypes + [C.c_uint32]
+        L.fdc_index_frames_depth.restype = C.c_int
         self._lib = L
 
+    def _decode(self, max_bits_per_sample, *args):
+        if max_bits_per_sample is None:
+            rc = self._lib.fdc_decode_frames(*args)
+            assert rc == 0, rc
+            return
+        rc = self._lib.fdc_decode_frames_depth(*args, max_bits_per_sample)
+        if rc != 0:
+            raise ValueError(rc)
+
     def decode_frames(self, data, offsets, lengths, channels: int, bits_per_sample: int, max_block_size: int,
-                      threads: int = 1, expected: np.ndarray | None = None):
+                      threads: int = 1, expected: np.ndarray | None = None, max_bits_per_sample: int | None = None):
         """-> (samples int32 [n, channels, max_block_size], block_sizes, numbers, status); with `expected` (same
-        shape) it verifies instead and the samples are None."""
+        shape) it verifies instead and the samples are None.  max_bits_per_sample: None for fdc_decode_frames (24
+        bits, as it always was), else fdc_decode_frames_depth with that limit, where a refused call raises ValueError."""
         buf = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
         buf = np.ascontiguousarray(buf, np.uint8)
         off = np.ascontiguousarray(offsets, np.uint64)
@@ -95,27 +111,28 @@ class DecoderCpu:
         st = np.zeros(n, np.uint32)
         if expected is not None:
             exp = np.ascontiguousarray(expected, np.int32)
-            rc = self._lib.fdc_decode_frames(buf.ctypes.data, off.ctypes.data, ln.ctypes.data, n, channels,
-                                             bits_per_sample, max_block_size, None, exp.ctypes.data,
-                                             exp.shape[-1], None, None, st.ctypes.data, threads)
-            assert rc == 0, rc
+            self._decode(max_bits_per_sample, buf.ctypes.data, off.ctypes.data, ln.ctypes.data, n, channels,
+                         bits_per_sample, max_block_size, None, exp.ctypes.data, exp.shape[-1], None, None,
+                         st.ctypes.data, threads)
             return None, None, None, st
         out = np.full((n, channels, max_block_size), -1, np.int32)
         bs = np.zeros(n, np.uint32)
         num = np.zeros(n, np.uint64)
-        rc = self._lib.fdc_decode_frames(buf.ctypes.data, off.ctypes.data, ln.ctypes.data, n, channels, bits_per_sample,
-                                         max_block_size, out.ctypes.data, None, max_block_size, bs.ctypes.data,
-                                         num.ctypes.data, st.ctypes.data, threads)
-        assert rc == 0, rc
+        self._decode(max_bits_per_sample, buf.ctypes.data, off.ctypes.data, ln.ctypes.data, n, channels,
+                     bits_per_sample, max_block_size, out.ctypes.data, None, max_block_size, bs.ctypes.data,
+                     num.ctypes.data, st.ctypes.data, threads)
         return out, bs, num, st
 
-    def index_frames(self, data, channels: int, bits_per_sample: int, max_frames: int):
-        """-> (offsets, lengths, ok)"""
+    def index_frames(self, data, channels: int, bits_per_sample: int, max_frames: int,
+                     max_bits_per_sample: int | None = None):
+        """-> (offsets, lengths, ok); max_bits_per_sample as in decode_frames"""
         buf = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data,
                                    np.uint8)
         off = np.zeros(max(1, max_frames), np.uint64)
         ln = np.zeros(max(1, max_frames), np.uint32)
         nf = C.c_uint64(0)
-        rc = self._lib.fdc_index_frames(buf.ctypes.data, buf.size, channels, bits_per_sample, max_frames,
-                                        off.ctypes.data, ln.ctypes.data, C.byref(nf))
+        args = (buf.ctypes.data, buf.size, channels, bits_per_sample, max_frames, off.ctypes.data, ln.ctypes.data,
+                C.byref(nf))
+        rc = (self._lib.fdc_index_frames(*args) if max_bits_per_sample is None
+              else self._lib.fdc_index_frames_depth(*args, max_bits_per_sample))
         return off[: nf.value], ln[: nf.value], rc == 0

@@ -562,6 +562,12 @@ class HipContext {
     if (flacenc_hip_set_precision_floor(h_, floor) != FLACENC_HIP_OK)
       throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
   }
+  // the deepest FLAC stream the handle's decode calls take: 24 (a fresh handle, the reference's limit) or 32
+  // (flacenc_hip_set_max_bits_per_sample); the encode calls take at most 24 bits whatever the setting
+  void set_max_bits_per_sample(uint32_t bits) {
+    if (flacenc_hip_set_max_bits_per_sample(h_, bits) != FLACENC_HIP_OK)
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+  }
   uint32_t sum_order_flags(size_t lpc_order) const {
     const uint32_t os = (order_search_ ? FLACENC_HIP_FLAG_ORDER_SEARCH : 0u) | (window_search_ ? FLACENC_HIP_FLAG_WINDOW_SEARCH : 0u) |
                         (order_guess_ ? FLACENC_HIP_FLAG_ORDER_GUESS : 0u) |

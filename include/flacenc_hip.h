@@ -439,6 +439,18 @@ int flacenc_hip_set_order_guesses(flacenc_hip_handle* h, uint32_t k);
  * value kept); a fresh handle holds 5.  Read when a call is enqueued: it applies to the calls made after it, and has no
  * effect without the flag. */
 int flacenc_hip_set_precision_floor(flacenc_hip_handle* h, uint32_t floor);
+/* The deepest FLAC stream the decode calls take: 24 (a fresh handle) or 32 bits per sample (else
+ * FLACENC_HIP_ERR_BAD_ARGUMENT, the value kept).  At 32, flacenc_hip_decode_frames / _verify_frames / _index_frames /
+ * _decode_pcm / _decode_streams / _decode_streams_md5 / _decode_ranges / _decode_ranges_planar / _recover_streams and
+ * their _async and device forms accept bits_per_sample 4..=32 (bytes_per_sample >= ceil(bits / 8) as before), a frame
+ * header may say 32 bits (sample-size code 7, or code 0 on a 32-bit stream), and the 33-bit side channel of a 32-bit
+ * stereo frame is reconstructed in 64-bit arithmetic.  Every decoded value of a valid stream fits 32 bits; on an invalid
+ * stream that passes both CRCs a frame of more than 24 bits decodes to the low 32 bits of the two's-complement 64-bit
+ * computation.  A float32 element of flacenc_hip_decode_ranges_planar at more than 24 bits is float(v), rounded to
+ * nearest even, times 2^-(bits - 1): not exact, and it can equal 1.0.  At 24 every call behaves as it always has: more
+ * than 24 bits is FLACENC_HIP_ERR_UNSUPPORTED for the call and FLACENC_HIP_DECODE_UNSUPPORTED for a frame.  Read when a
+ * call is enqueued.  The encode calls take at most 24 bits whatever the setting. */
+int flacenc_hip_set_max_bits_per_sample(flacenc_hip_handle* h, uint32_t bits);
 /* The weights of one extra-window entry over a block of block_size (<= 32767) samples, on the host: no handle, no GPU.
  * The same validation as flacenc_hip_set_lpc_windows (FLACENC_HIP_ERR_BAD_CONFIG). */
 int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,

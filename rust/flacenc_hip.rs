@@ -299,6 +299,8 @@ extern "C" {
     pub fn flacenc_hip_set_order_guesses(h: *mut Handle, k: u32) -> c_int;
     /// `FLAG_PRECISION_SEARCH`'s lowest precision of a handle, `1..=15` (a fresh handle holds 5).
     pub fn flacenc_hip_set_precision_floor(h: *mut Handle, floor: u32) -> c_int;
+    /// The deepest FLAC stream the decode calls of a handle take, `24` (a fresh handle) or `32` bits per sample.
+    pub fn flacenc_hip_set_max_bits_per_sample(h: *mut Handle, bits: u32) -> c_int;
     /// One extra-window entry's weights over a block, on the host.
     pub fn flacenc_hip_lpc_window_weights(
         window_type: u32, alpha: f32, start: u32, end: u32, block_size: u32, out: *mut f32,
@@ -605,6 +607,15 @@ impl Gpu {
         match unsafe { flacenc_hip_set_precision_floor(self.0, floor) } {
             OK => Ok(()),
             _ => Err(EncodeError::Config(VerifyError::new("precision_floor", "must be in range 1..=15"))),
+        }
+    }
+
+    /// The deepest FLAC stream the decode calls take on this handle: 24 (a fresh handle, the reference's limit) or 32.
+    /// The encode calls take at most 24 bits whatever the setting.
+    pub fn set_max_bits_per_sample(&self, bits: u32) -> Result<(), EncodeError> {
+        match unsafe { flacenc_hip_set_max_bits_per_sample(self.0, bits) } {
+            OK => Ok(()),
+            _ => Err(EncodeError::Config(VerifyError::new("max_bits_per_sample", "must be 24 or 32"))),
         }
     }
 }

@@ -32,6 +32,7 @@ def crop_all(files, handle, start_seconds, seconds):
     for i, data in enumerate(files):
         info, points, first_frame = flac_metadata.read_blocks(data)
         ch, bps = info["channels"], info["bits_per_sample"]
+        decode_flac.allow_depth(handle, bps)
         width = (bps + 7) // 8
         first = int(round(start_seconds * info["sample_rate"]))
         n = int(round(seconds * info["sample_rate"]))
@@ -74,6 +75,7 @@ def crop_all_planar(files, handle, start_seconds, seconds):
     for i, data in enumerate(files):
         info, points, first_frame = flac_metadata.read_blocks(data)
         ch, bps = info["channels"], info["bits_per_sample"]
+        decode_flac.allow_depth(handle, bps)
         first = int(round(start_seconds * info["sample_rate"]))
         n = int(round(seconds * info["sample_rate"]))
         shape = shape or (ch, n)

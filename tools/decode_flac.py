@@ -3,7 +3,8 @@
 The host reads the metadata blocks (it takes the stream's parameters and MD5 from STREAMINFO and skips every other
 block); flacenc_hip_decode_pcm finds the frames, decodes them and returns the samples as packed interleaved
 little-endian PCM -- the byte string the STREAMINFO MD5 is defined over.  The host checks that MD5 (an all-zero digest
-means "not checked") and writes the WAV (8 / 16 / 24-bit PCM).
+means "not checked") and writes the WAV (8 / 16 / 24 / 32-bit PCM; a file of more than 24 bits per sample sets the
+handle's depth limit to 32).
 
     python tools/decode_flac.py in.flac out.wav
 
@@ -34,11 +35,20 @@ def read_metadata(data: bytes):
 STOP_NAMES = {_capi.DECODE_NO_ROOM: "the output has no room", _capi.DECODE_CHAIN: "no verified frame starts here"}
 
 
+def allow_depth(handle, bits_per_sample):
+    """A file of more than 24 bits per sample raises the handle's limit to 32 (flacenc_hip_set_max_bits_per_sample);
+    shallower files decode the same under either limit.  The limit is never lowered again: a caller's handle that
+    has met one deep file (decode_many.py and crop_flac.py pass theirs in) stays at 32 for every later call on it."""
+    if bits_per_sample > 24:
+        handle.set_max_bits_per_sample(32)
+
+
 def decode(data: bytes, handle):
     """-> (packed interleaved little-endian PCM, ceil(bits / 8) bytes per sample, as a uint8 array; STREAMINFO)."""
     info, start = read_metadata(data)
     frames = np.frombuffer(data, np.uint8)[start:]
     ch, bps = info["channels"], info["bits_per_sample"]
+    allow_depth(handle, bps)
     width = (bps + 7) // 8
     if info["total_samples"]:
         room = info["total_samples"] * ch * width
@@ -53,10 +63,10 @@ def decode(data: bytes, handle):
 
 
 def wav_payload(pcm, bps):
-    """The call's PCM bytes as the data of an 8 / 16 / 24-bit PCM WAV."""
+    """The call's PCM bytes as the data of an 8 / 16 / 24 / 32-bit PCM WAV."""
     width = (bps + 7) // 8
     if 8 * width == bps and width > 1:
-        return pcm.tobytes()   # 16 / 24 bits: the WAV payload as it stands
+        return pcm.tobytes()   # 16 / 24 / 32 bits: the WAV payload as it stands
     # a depth that does not fill its bytes sits in the high bits of the WAV sample; 8-bit WAV is offset binary
     wide = np.zeros((pcm.size // width, 4), np.uint8)
     wide[:, :width] = pcm.reshape(-1, width)

@@ -45,6 +45,7 @@ def decode_all(files, handle, device_md5=False):
     for i, data in enumerate(files):
         info, start = decode_flac.read_metadata(data)
         ch, bps = info["channels"], info["bits_per_sample"]
+        decode_flac.allow_depth(handle, bps)
         width = (bps + 7) // 8
         n = len(data) - start
         room = (info["total_samples"] or (n // 9 + 1) * info["max_block_size"]) * ch * width
@@ -82,6 +83,7 @@ def recover_all(files, handle):
     for i, data in enumerate(files):
         info, start = decode_flac.read_metadata(data)
         ch, bps = info["channels"], info["bits_per_sample"]
+        decode_flac.allow_depth(handle, bps)
         width = (bps + 7) // 8
         n = len(data) - start
         room = (info["total_samples"] or (n // 9 + 1) * info["max_block_size"]) * ch * width
