@@ -88,6 +88,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_set_order_guesses",
     "flacenc_hip_set_precision_floor",
     "flacenc_hip_set_max_bits_per_sample",
+    "flacenc_hip_set_max_encode_bits_per_sample",
     "flacenc_hip_lpc_window_weights",
     "flacenc_hip_qlpc_batch",
     "flacenc_hip_qlpc_batch_async",
@@ -119,6 +120,7 @@ EXPORTED_SYMBOLS = (
     "flacenc_hip_fill_le_bytes_async",
     "flacenc_hip_encode_pack_stereo_frames_async",
     "flacenc_hip_encode_pack_frames_async",
+    "flacenc_hip_encode_pack_frames_wide",
     "flacenc_hip_comm_unique_id",
     "flacenc_hip_comm_create",
     "flacenc_hip_comm_destroy",
@@ -368,6 +370,8 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
     L.flacenc_hip_set_precision_floor.restype = C.c_int
     L.flacenc_hip_set_max_bits_per_sample.argtypes = [vp, C.c_uint32]
     L.flacenc_hip_set_max_bits_per_sample.restype = C.c_int
+    L.flacenc_hip_set_max_encode_bits_per_sample.argtypes = [vp, C.c_uint32]
+    L.flacenc_hip_set_max_encode_bits_per_sample.restype = C.c_int
     L.flacenc_hip_lpc_window_weights.argtypes = [C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.flacenc_hip_lpc_window_weights.restype = C.c_int
     L.flacenc_hip_synchronize.argtypes = [vp]
@@ -461,6 +465,10 @@ def _load_path(LIB_PATH: str) -> C.CDLL:
                                                         C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                         C.c_uint32, vp, vp, C.c_size_t, vp, vp]
     L.flacenc_hip_encode_pack_frames_async.restype = C.c_int
+    L.flacenc_hip_encode_pack_frames_wide.argtypes = [vp, C.POINTER(FrameConfig), vp, C.c_size_t, C.c_uint32,
+                                                      C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                      C.c_uint32, vp, C.c_size_t, vp]
+    L.flacenc_hip_encode_pack_frames_wide.restype = C.c_int
     L.flacenc_hip_stereo_frame_bytes_bound.argtypes = [C.c_uint32, C.c_uint32]
     L.flacenc_hip_stereo_frame_bytes_bound.restype = C.c_size_t
     L.flacenc_hip_encode_frames.argtypes = [vp, C.POINTER(FrameConfig), i32p, C.c_size_t, C.c_uint32, C.c_uint32,
@@ -722,8 +730,15 @@ class Handle:
 
     def set_max_bits_per_sample(self, bits: int):
         """flacenc_hip_set_max_bits_per_sample: the deepest FLAC stream the decode calls take, 24 (a fresh handle) or
-        32; applies to the calls made after it.  The encode calls take at most 24 bits whatever the setting."""
+        32; applies to the calls made after it.  The encode calls do not read it: set_max_encode_bits_per_sample is
+        theirs."""
         self._check(self._lib.flacenc_hip_set_max_bits_per_sample(self._h, int(bits)))
+
+    def set_max_encode_bits_per_sample(self, bits: int):
+        """flacenc_hip_set_max_encode_bits_per_sample: the deepest PCM encode_pcm*, encode_streams and
+        encode_streams_planar (SAMPLE_I32) take, 24 (a fresh handle) or 32; applies to the calls made after it.  More
+        than 24 bits come in 4-byte samples and run the wide path (encode_pack_frames_wide_device)."""
+        self._check(self._lib.flacenc_hip_set_max_encode_bits_per_sample(self._h, int(bits)))
 
     def _hook(self, name):
         if not hasattr(self._lib, name):
@@ -1118,6 +1133,36 @@ class Handle:
             self._h, C.byref(cfg), frames_ptr, n_frames, channels, block_size, stride, bits_per_sample, sample_rate,
             first_frame_number, frame_number_step, results_ptr, out_ptr, out_stride, out_len_ptr, stream or None)
         self._check(rc)
+
+    def encode_pack_frames_wide_device(self, cfg: FrameConfig, frames_ptr: int, n_frames: int, channels: int,
+                                       block_size: int, stride: int, bits_per_sample: int, sample_rate: int,
+                                       first_frame_number: int, frame_number_step: int, out_ptr: int, out_stride: int,
+                                       out_len_ptr: int):
+        """flacenc_hip_encode_pack_frames_wide: rows of 8..32-bit samples -> FLAC frame bytes on the device, the wide
+        path (Constant, Verbatim, fixed predictors; 2 channels take the stereo decision); blocks on the handle's
+        stream."""
+        rc = self._lib.flacenc_hip_encode_pack_frames_wide(
+            self._h, C.byref(cfg), frames_ptr, n_frames, channels, block_size, stride, bits_per_sample, sample_rate,
+            first_frame_number, frame_number_step, out_ptr, out_stride, out_len_ptr)
+        self._check(rc)
+
+    def encode_frames_wide(self, frames, bits_per_sample: int, cfg: FrameConfig, sample_rate: int = 44100,
+                           first_frame_number: int = 0, frame_number_step: int = 1):
+        """The wide path on a host array int32 [n_frames, channels, block_size] (staged through device tensors) ->
+        the frames' bytes, one bytes object each."""
+        import torch
+        x = np.ascontiguousarray(frames, np.int32)
+        n_frames, channels, n = x.shape
+        bound = int(self._lib.flacenc_hip_stereo_frame_bytes_bound(n, bits_per_sample) if channels == 2 else
+                    self._lib.flacenc_hip_frame_bytes_bound(channels, n, bits_per_sample))
+        rows = self._device_copy(x)
+        out = torch.full((n_frames, bound), 0xA5, dtype=torch.uint8, device="cuda")
+        lens = torch.zeros(n_frames, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()  # the inputs are in place before the handle's stream reads them
+        self.encode_pack_frames_wide_device(cfg, rows.data_ptr(), n_frames, channels, n, n, bits_per_sample, sample_rate,
+                                            first_frame_number, frame_number_step, out.data_ptr(), bound, lens.data_ptr())
+        got, lengths = out.cpu().numpy(), lens.cpu().numpy()
+        return [got[f, : int(lengths[f])].tobytes() for f in range(n_frames)]
 
     def frame_bytes_bound(self, block_size: int, bits_per_sample: int) -> int:
         return int(self._lib.flacenc_hip_stereo_frame_bytes_bound(block_size, bits_per_sample))

@@ -33,7 +33,7 @@ std::vector<DeviceBuffer*> device_buffers(flacenc_hip_handle* h) {
   std::vector<DeviceBuffer*> all = {
       &h->d_samples, &h->d_residual, &h->d_params, &h->d_bps, &h->d_autocorr, &h->d_lpc, &h->d_tables, &h->d_keys, &h->d_sel,
       &h->d_results, &h->d_out, &h->d_outlen, &h->d_cparams, &h->d_cresid, &h->d_fparams, &h->d_fresid, &h->d_fkeys,
-      &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram, &h->d_esc, &h->d_dec,
+      &h->d_split, &h->d_presid, &h->d_sumabs, &h->d_minmax, &h->d_marked, &h->d_irlsw, &h->d_gram, &h->d_esc, &h->d_wide, &h->d_dec,
       &h->d_dec_io, &h->d_idx, &h->d_vbs_frames, &h->d_vbs_results, &h->d_vbs_pack, &h->d_vbs_meta, &h->d_vbs_io, &h->d_wk,
       &h->d_wlist, &h->d_wrows, &h->d_wbps, &h->d_order, &h->d_ppk_off, &h->d_ppk_io, &h->d_dpcm_idx, &h->d_md5, &h->d_encs};
   for (int i = 0; i < 2; ++i)
@@ -184,6 +184,16 @@ int flacenc_hip_set_max_bits_per_sample(flacenc_hip_handle* h, uint32_t bits) {
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
   h->max_bps = bits;
+  return FLACENC_HIP_OK;
+}
+
+int flacenc_hip_set_max_encode_bits_per_sample(flacenc_hip_handle* h, uint32_t bits) {
+  if (!h) return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  if (bits != 24 && bits != 32) {
+    h->last_error = "flacenc_hip_set_max_encode_bits_per_sample: bits must be 24 or 32";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
+  h->max_encode_bps = bits;
   return FLACENC_HIP_OK;
 }
 

@@ -21,6 +21,7 @@
 //   flac_recover_streams.cpp  a batch of damaged streams decoded through their errors (flacenc_hip_recover_streams)
 //   md5_streams.cpp      MD5 digests of a batch of spans (flacenc_hip_md5_spans): its kernel, launcher and the call
 //   encode_streams.cpp   a batch of PCM streams to frames (flacenc_hip_encode_streams): its kernels and the call
+//   wide_encode.cpp      rows of up to 32 bits to frames (flacenc_hip_encode_pack_frames_wide): its kernels and the call
 //   api_variable.cpp     the block-size search
 //   api_debug_hooks.cpp  flacenc_hip_debug.h; linked into libflacenc_hip_hooks.so only
 #ifndef FLACENC_HIP_API_INTERNAL_H_
@@ -42,6 +43,7 @@
 #include "frame_plan.h"
 #include "order_mode_core.h"
 #include "qlpc_kernel.h"
+#include "wide_encode_core.h"
 
 namespace streamenc {
 struct LaunchFrame;  // stream_encode_core.h
@@ -188,12 +190,15 @@ struct flacenc_hip_handle {
   flacenc_hip::DeviceBuffer d_wk, d_wlist, d_wrows, d_wbps;
   // order / window search: every window's R[], every candidate's predictor record and the choice (order_search.h)
   flacenc_hip::DeviceBuffer d_order;
+  flacenc_hip::DeviceBuffer d_wide;  // the wide encode path's records, one per (frame, role) (wide_encode.cpp)
   flacenc_hip::DeviceBuffer d_esc;  // the packers' list of frames with escaped partitions (FramePackArgs::escape_list)
   uint32_t order_guesses = 1;  // FLACENC_HIP_FLAG_ORDER_GUESS: K, the guesses per window (flacenc_hip_set_order_guesses)
   // FLACENC_HIP_FLAG_PRECISION_SEARCH: F, the lowest precision searched (flacenc_hip_set_precision_floor)
   uint32_t precision_floor = 5;
   // the deepest stream the decode calls take, 24 or 32 (flacenc_hip_set_max_bits_per_sample)
   uint32_t max_bps = 24;
+  // the deepest PCM the stream-level encode calls take, 24 or 32 (flacenc_hip_set_max_encode_bits_per_sample)
+  uint32_t max_encode_bps = 24;
   // streaming host path (flacenc_hip_encode_pcm_stereo): copy-in / copy-out streams, two slots of pinned
   // staging and device buffers, the events that order them
   uint32_t marked_parity = 0;  // which of d_marked's two counters the current pipeline counts into
@@ -401,6 +406,29 @@ hipError_t launch_planar_pack(const uint32_t* elems, const planarenc::Frame* tab
 hipError_t launch_segmax_scan(uint64_t* plan, const uint32_t* f_slot, const uint64_t* base, uint64_t* emax,
                               const uint32_t* counters, size_t max_frames, uint32_t* agg_h, uint64_t* agg_v,
                               hipStream_t stream);
+
+// ---- wide_encode.cpp ----
+// The wide encode path's launch record: rows in, frame bytes and lengths out (wide_encode_core.h holds the rule).
+struct WideEncodeArgs {
+  const int32_t* frames;  // n_frames * channels rows of block_size words, `stride` words apart
+  size_t stride;
+  uint32_t channels, block_size, bits_per_sample, sample_rate;
+  uint32_t n_frames, first_frame_number, frame_number_step;
+  wideenc::Config cfg;
+  wideenc::SubRecord* records;  // scratch: n_frames * roles_of(channels)
+  uint8_t* out;                 // 16-byte aligned slots of out_stride bytes
+  size_t out_stride;
+  uint32_t* out_len;
+};
+// wide_decide_kernel and wide_write_kernel on `stream`; all pointers are device memory.
+hipError_t launch_wide_encode(const WideEncodeArgs& a, hipStream_t stream);
+// the device step enqueued on `stream` (flacenc_hip_encode_pack_frames_wide is its blocking form on the handle's stream)
+int encode_pack_frames_wide(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg, const int32_t* frames,
+                            size_t n_frames, uint32_t channels, uint32_t block_size, size_t stride, uint32_t bits_per_sample,
+                            uint32_t sample_rate, uint32_t first_frame_number, uint32_t frame_number_step, uint8_t* out,
+                            size_t out_stride, uint32_t* out_len, hipStream_t stream);
+// does a class of `bits_per_sample` run the wide step in the stream-level calls
+inline bool is_wide(uint32_t bits_per_sample) { return bits_per_sample > 24; }
 
 // ---- api_pack.cpp ----
 void fill_crc_powers(uint32_t lds_words, uint32_t* crc_per, uint16_t crc_pow[32]);

@@ -136,6 +136,13 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
                     "not in 64..=32767";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
+  // more than 24 bits: the wide step, after flacenc_hip_set_max_encode_bits_per_sample(h, 32) and in 4-byte samples
+  // (without the opt-in the frame-level calls below refuse the depth as they always have)
+  const bool wide = is_wide(bits_per_sample) && bits_per_sample <= h->max_encode_bps;
+  if (wide && bytes_per_sample != 4) {
+    h->last_error = "encode_pcm: more than 24 bits per sample come in 4-byte samples";
+    return FLACENC_HIP_ERR_BAD_ARGUMENT;
+  }
   const bool stereo = channels == 2;
   const uint64_t n_full = total_samples / block_size;
   const uint32_t tail = static_cast<uint32_t>(total_samples % block_size);
@@ -167,6 +174,8 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
   if ((rc = ensure(h, h->d_samples, chunk * channels * dstride * 4)) != FLACENC_HIP_OK) return rc;
   if ((rc = ensure(h, h->d_results, chunk * (stereo ? sizeof(flacenc_hip_stereo_frame_result)
                                                      : channels * sizeof(flacenc_hip_channel_result)))) != FLACENC_HIP_OK)
+    return rc;
+  if (wide && (rc = ensure(h, h->d_wide, chunk * wideenc::roles_of(channels) * sizeof(wideenc::SubRecord))) != FLACENC_HIP_OK)
     return rc;
   for (int i = 0; i < 2; ++i) {
     if ((rc = ensure(h, h->d_pcm[i], chunk * frame_in_bytes + 16)) != FLACENC_HIP_OK) return rc;
@@ -264,7 +273,11 @@ int flacenc_hip_encode_pcm(flacenc_hip_handle* h, const flacenc_hip_frame_config
                                    : flacenc_hip_frame_bytes_bound(channels, c.n, bits_per_sample)) + 15) & ~static_cast<size_t>(15);
     uint32_t* dlen = static_cast<uint32_t*>(h->d_plen[s].ptr);
     const uint32_t number = first_frame_number + static_cast<uint32_t>(c.first_frame) * frame_number_step;
-    if (stereo) {
+    if (wide) {
+      rc = encode_pack_frames_wide(h, cfg, static_cast<const int32_t*>(h->d_samples.ptr), c.frames, channels,
+                                                     c.n, cstride, bits_per_sample, sample_rate, number, frame_number_step,
+                                                     static_cast<uint8_t*>(h->d_pack[s].ptr), cbound, dlen, h->stream);
+    } else if (stereo) {
       rc = flacenc_hip_encode_pack_stereo_frames_async(
           h, cfg, static_cast<const int32_t*>(h->d_samples.ptr), c.frames, c.n, cstride, bits_per_sample, sample_rate,
           number, frame_number_step, static_cast<flacenc_hip_stereo_frame_result*>(h->d_results.ptr),

@@ -304,18 +304,22 @@ int flacenc_hip::encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_
       return FLACENC_HIP_ERR_BAD_ARGUMENT;
     }
   }
-  int rc = streamenc::check_streams(table, planar ? 0 : n_streams, pcm_bytes, out_bytes, block_size);
+  const uint32_t max_bits = h->max_encode_bps;
+  int rc = streamenc::check_streams(table, planar ? 0 : n_streams, pcm_bytes, out_bytes, block_size, max_bits);
   for (size_t s = 0; planar && rc == FLACENC_HIP_OK && s < n_streams; ++s) {
     // the packed PCM exists nowhere: every other rule holds, the span is held against a buffer without end
     Desc x = table[s];
     x.offset = 0;
     if (x.total_samples >= (streamenc::MAX_FRAMES << 15)) rc = FLACENC_HIP_ERR_BAD_ARGUMENT;  // 2^31 frames at any block size
-    if (rc == FLACENC_HIP_OK) rc = streamenc::check_streams(&x, 1, UINT64_MAX, out_bytes, block_size);
+    // (a float32 element holds 24 bits: deeper streams come as int32 alone)
+    if (is_wide(x.bits_per_sample) && planar->sample_format != FLACENC_HIP_SAMPLE_I32) rc = FLACENC_HIP_ERR_BAD_ARGUMENT;
+    if (rc == FLACENC_HIP_OK) rc = streamenc::check_streams(&x, 1, UINT64_MAX, out_bytes, block_size, max_bits);
   }
   const uint64_t F64 = rc == FLACENC_HIP_OK ? streamenc::count_frames(table, n_streams, block_size) : 0;
   if (rc != FLACENC_HIP_OK || F64 >= streamenc::MAX_FRAMES || F64 > max_frames) {
     h->last_error = "encode_streams: block_size not in 64..=32767, channels not in 1..=8, bytes_per_sample not in 1..=4, "
-                    "bits_per_sample not in 8..=24, a span past pcm_bytes, a slot past out_bytes, 2^31 frames or more, or "
+                    "bits_per_sample not in 8..=24 (..=32 at 4 bytes after flacenc_hip_set_max_encode_bits_per_sample; int32 "
+                    "elements only), a span past pcm_bytes, a slot past out_bytes, 2^31 frames or more, or "
                     "max_frames below flacenc_hip_encode_streams_frames";
     return FLACENC_HIP_ERR_BAD_ARGUMENT;
   }
@@ -414,9 +418,14 @@ int flacenc_hip::encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_
   const size_t o_off = take((static_cast<size_t>(F) + 1) * 8), o_zeros = take((static_cast<size_t>(F) + 1) * 8);
   if ((rc = ensure(h, h->d_encs, need)) != FLACENC_HIP_OK) return rc;
   const size_t stride = padded_stride(block_size);
-  size_t max_run = 1, max_record = sizeof(flacenc_hip_stereo_frame_result);
+  size_t max_run = 1, max_record = sizeof(flacenc_hip_stereo_frame_result), max_wide = 0;
   for (const streamenc::Run& r : pl.runs) {
     const streamenc::Class& k = pl.classes[r.cls];
+    if (is_wide(k.bits_per_sample)) {  // the wide step's records, sized here so that no run allocates
+      const size_t recs = r.frames * wideenc::roles_of(k.channels) * sizeof(wideenc::SubRecord);
+      if (recs > max_wide) max_wide = recs;
+      continue;
+    }
     const size_t rec = r.frames * (k.channels == 2 ? sizeof(flacenc_hip_stereo_frame_result)
                                                    : k.channels * sizeof(flacenc_hip_channel_result));
     if (rec > max_record) max_record = rec;
@@ -424,6 +433,7 @@ int flacenc_hip::encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_
   }
   if ((rc = ensure(h, h->d_samples, static_cast<size_t>(pl.max_class_rows) * stride * 4 + 16)) != FLACENC_HIP_OK) return rc;
   if ((rc = ensure(h, h->d_results, max_record)) != FLACENC_HIP_OK) return rc;
+  if (max_wide && (rc = ensure(h, h->d_wide, max_wide)) != FLACENC_HIP_OK) return rc;
   if ((rc = ensure(h, h->d_pack[0], static_cast<size_t>(pl.pack_bytes) + 16)) != FLACENC_HIP_OK) return rc;
   const uint8_t* d_pcm = planar ? static_cast<const uint8_t*>(planar->samples) : pcm;
   if (planar) pcm_bytes = ext.end - ext.first;  // what a host call sends up
@@ -502,7 +512,11 @@ int flacenc_hip::encode_streams_common(flacenc_hip_handle* h, const flacenc_hip_
       const streamenc::Run& r = pl.runs[next_run];
       const int32_t* run_rows = rows + static_cast<size_t>(r.first - k.first) * k.channels * stride;
       uint8_t* run_pack = pack + k.pack_base + static_cast<size_t>(r.first - k.first) * k.pack_stride;
-      if (k.channels == 2) {
+      if (is_wide(k.bits_per_sample)) {  // the wide step in place of the frame-level calls
+        rc = encode_pack_frames_wide(h, cfg, run_rows, r.frames, k.channels, r.block, stride,
+                                                       k.bits_per_sample, k.sample_rate, 0, 0, run_pack, k.pack_stride,
+                                                       len0 + r.first, st);
+      } else if (k.channels == 2) {
         rc = flacenc_hip_encode_pack_stereo_frames_async(
             h, cfg, run_rows, r.frames, r.block, stride, k.bits_per_sample, k.sample_rate, 0, 0,
             static_cast<flacenc_hip_stereo_frame_result*>(h->d_results.ptr), run_pack, k.pack_stride, len0 + r.first, st);

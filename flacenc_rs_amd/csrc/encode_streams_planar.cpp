@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(256) planar_fill_kernel(const uint32_t* __rest
   const uint64_t items = static_cast<uint64_t>(n_frames) * groups;
   const bool narrow = items <= 0xFFFFFFFFull;
   const float scale = planarenc::scale_of(bits);
-  const int32_t hi = 1 << (bits - 1);
+  const int32_t hi = static_cast<int32_t>(1u << (bits - 1));  // (read for float32 elements alone: bits <= 24)
   for (uint64_t base = blockIdx.x * 256ull; base < items; base += static_cast<uint64_t>(gridDim.x) * 256ull) {
     const uint64_t it = base + threadIdx.x;
     uint32_t cnt = 0, stream = 0;
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(256) planar_pack_kernel(const uint32_t* __rest
     if (k0 >= hi) continue;
     const uint64_t end = st.total_samples * C * B;
     const float scale = planarenc::scale_of(bits);
-    const int32_t top = 1 << (bits - 1);
+    const int32_t top = static_cast<int32_t>(1u << (bits - 1));  // (read for float32 elements alone: bits <= 24)
     planarenc::PackedByte at = planarenc::packed_byte(k0, C, B);
     uint32_t word = 0, unused = 0;
     int32_t v = 0;
@@ -162,7 +162,7 @@ hipError_t launch_planar_fill(const uint32_t* elems, const Frame* table, uint32_
                               uint32_t sample_format, uint32_t bits, uint32_t row0, size_t stride, int32_t* rows,
                               unsigned long long* clipped, int form, hipStream_t stream) {
   if (n_frames == 0) return hipSuccess;
-  if (bits < 1 || bits > 24) return hipErrorInvalidValue;
+  if (bits < 1 || bits > (sample_format == FLACENC_HIP_SAMPLE_I32 ? 32u : 24u)) return hipErrorInvalidValue;
   const uint32_t groups = static_cast<uint32_t>(stride / 4);
   const uint64_t items = static_cast<uint64_t>(n_frames) * groups;
   const dim3 grid(static_cast<uint32_t>(std::min<uint64_t>((items + 255) / 256, 65536)));

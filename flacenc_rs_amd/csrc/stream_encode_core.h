@@ -124,14 +124,15 @@ inline uint64_t count_frames(const flacenc_hip_pcm_stream_desc* d, size_t n, uin
   return sum;
 }
 
-// The table against the call's buffers.  0 or FLACENC_HIP_ERR_BAD_ARGUMENT (overflow-free).
+// The table against the call's buffers.  0 or FLACENC_HIP_ERR_BAD_ARGUMENT (overflow-free).  `max_bits` is the handle's
+// limit (flacenc_hip_set_max_encode_bits_per_sample), 24 or 32; more than 24 bits come in 4-byte samples.
 inline int check_streams(const flacenc_hip_pcm_stream_desc* d, size_t n, uint64_t pcm_bytes, uint64_t out_bytes,
-                         uint32_t block_size) {
+                         uint32_t block_size, uint32_t max_bits = 24) {
   if (block_size < FLACENC_HIP_MIN_BLOCK_SIZE || block_size > FLACENC_HIP_MAX_BLOCK_SIZE) return FLACENC_HIP_ERR_BAD_ARGUMENT;
   for (size_t s = 0; s < n; ++s) {
     const flacenc_hip_pcm_stream_desc& x = d[s];
     if (x.channels < 1 || x.channels > 8 || x.bytes_per_sample < 1 || x.bytes_per_sample > 4 ||
-        x.bits_per_sample < 8 || x.bits_per_sample > 24)
+        x.bits_per_sample < 8 || x.bits_per_sample > max_bits || (x.bits_per_sample > 24 && x.bytes_per_sample != 4))
       return FLACENC_HIP_ERR_BAD_ARGUMENT;
     const uint64_t per = static_cast<uint64_t>(x.channels) * x.bytes_per_sample;
     if (x.total_samples > pcm_bytes / per || x.offset > pcm_bytes - x.total_samples * per) return FLACENC_HIP_ERR_BAD_ARGUMENT;

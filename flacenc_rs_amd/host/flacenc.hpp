@@ -563,9 +563,15 @@ class HipContext {
       throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
   }
   // the deepest FLAC stream the handle's decode calls take: 24 (a fresh handle, the reference's limit) or 32
-  // (flacenc_hip_set_max_bits_per_sample); the encode calls take at most 24 bits whatever the setting
+  // (flacenc_hip_set_max_bits_per_sample); the encode calls do not read it
   void set_max_bits_per_sample(uint32_t bits) {
     if (flacenc_hip_set_max_bits_per_sample(h_, bits) != FLACENC_HIP_OK)
+      throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
+  }
+  // the deepest PCM the handle's stream-level encode calls take: 24 (a fresh handle) or 32
+  // (flacenc_hip_set_max_encode_bits_per_sample); more than 24 bits come in 4-byte samples and run the wide path
+  void set_max_encode_bits_per_sample(uint32_t bits) {
+    if (flacenc_hip_set_max_encode_bits_per_sample(h_, bits) != FLACENC_HIP_OK)
       throw error::EncodeError(error::EncodeError::Device, flacenc_hip_last_error(h_));
   }
   uint32_t sum_order_flags(size_t lpc_order) const {

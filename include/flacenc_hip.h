@@ -449,8 +449,16 @@ int flacenc_hip_set_precision_floor(flacenc_hip_handle* h, uint32_t floor);
  * computation.  A float32 element of flacenc_hip_decode_ranges_planar at more than 24 bits is float(v), rounded to
  * nearest even, times 2^-(bits - 1): not exact, and it can equal 1.0.  At 24 every call behaves as it always has: more
  * than 24 bits is FLACENC_HIP_ERR_UNSUPPORTED for the call and FLACENC_HIP_DECODE_UNSUPPORTED for a frame.  Read when a
- * call is enqueued.  The encode calls take at most 24 bits whatever the setting. */
+ * call is enqueued.  The encode calls do not read it: flacenc_hip_set_max_encode_bits_per_sample is theirs. */
 int flacenc_hip_set_max_bits_per_sample(flacenc_hip_handle* h, uint32_t bits);
+/* The deepest PCM the stream-level encode calls take: 24 (a fresh handle) or 32 bits per sample (else
+ * FLACENC_HIP_ERR_BAD_ARGUMENT, the value kept); independent of flacenc_hip_set_max_bits_per_sample.  At 32,
+ * flacenc_hip_encode_pcm / _encode_pcm_stereo, flacenc_hip_encode_streams and flacenc_hip_encode_streams_planar
+ * (FLACENC_HIP_SAMPLE_I32 only) accept bits_per_sample 25..=32 at bytes_per_sample 4, and a stream or class of more
+ * than 24 bits runs the step of flacenc_hip_encode_pack_frames_wide (below) in place of the frame-level calls; streams of 24
+ * bits or fewer launch the kernels they always have.  At 24 every call answers as it always has.  Read when a call is
+ * enqueued.  The frame-level record calls, the candidate batches and flacenc_hip_encode_variable stay at 24 bits. */
+int flacenc_hip_set_max_encode_bits_per_sample(flacenc_hip_handle* h, uint32_t bits);
 /* The weights of one extra-window entry over a block of block_size (<= 32767) samples, on the host: no handle, no GPU.
  * The same validation as flacenc_hip_set_lpc_windows (FLACENC_HIP_ERR_BAD_CONFIG). */
 int flacenc_hip_lpc_window_weights(uint32_t type, float alpha, uint32_t start, uint32_t end, uint32_t block_size,
@@ -754,6 +762,33 @@ int flacenc_hip_encode_pack_frames_async(flacenc_hip_handle* h, const flacenc_hi
                                          uint32_t sample_rate, uint32_t first_frame_number,
                                          uint32_t frame_number_step, flacenc_hip_channel_result* results,
                                          uint8_t* out, size_t out_stride, uint32_t* out_len, void* stream);
+
+/* The wide encode path: encode_frame + Frame::write for frames of 8..=32 bits per sample on
+ * 64-bit integers, with the candidates of libFLAC's -0 .. -2.  Arguments as flacenc_hip_encode_pack_frames_async, without
+ * the records; 2 channels take the stereo decision (the side channel has bits_per_sample + 1 bits, 33 at 32), any other
+ * count is Independent.  out_stride >= flacenc_hip_stereo_frame_bytes_bound (2 channels) or flacenc_hip_frame_bytes_bound.
+ * Device pointers; the call runs on the handle's stream and returns when the frames are written (there is no `stream`
+ * argument and no _async form yet: the stream-level calls run the same step on their own streams).
+ * Needs no opt-in: the caller names the path.  Per subframe (exact integers, no floating point):
+ *   - Constant under use_constant; Verbatim for block_size < 64;
+ *   - with use_fixed the fixed predictors of order 0..=min(fixed_max_order, 4): an order is eligible only if every
+ *     residual lies in (-2^31, 2^31) (RFC 9639 section 9.2.7.3); per eligible order the exhaustive partitioned-Rice search
+ *     (src/rice.rs:246-298 on exact 64-bit sums, parameters 0..=qlpc.max_rice_parameter); the smallest
+ *     width * order + code_bits wins, ties to the lower order (OrderSel::BitCount, src/coding.rs:242-265); the subframe is
+ *     Fixed if that key and its exact count_bits are below Verbatim's bits, with 5-bit (RICE2) parameters exactly when
+ *     a parameter exceeds 14;
+ *   - with FLACENC_HIP_FLAG_WASTED_BITS the subframe is that of x >> k at width - k bits, k counted as above;
+ *   - try_stereo_coding (src/coding.rs:493-522) on the four exact bit counts.
+ * NOT read on this path: use_lpc, every other field of cfg->qlpc, every search flag, FLACENC_HIP_FLAG_RICE_ESCAPE,
+ * fixed_order_sel and fixed_partitions (ApproxEnt's f32 sums have no meaning at these magnitudes).  They are tolerated,
+ * not refused: a batch may mix depths under one config.  The header's sample-size code is 7 for 32 bits and 0 for
+ * 25..=31.  FLACENC_HIP_ERR_BAD_CONFIG for max_rice_parameter > 30 or fixed_max_order > 4. */
+int flacenc_hip_encode_pack_frames_wide(flacenc_hip_handle* h, const flacenc_hip_frame_config* cfg,
+                                        const int32_t* frames, size_t n_frames, uint32_t channels,
+                                        uint32_t block_size, size_t stride, uint32_t bits_per_sample,
+                                        uint32_t sample_rate, uint32_t first_frame_number,
+                                        uint32_t frame_number_step, uint8_t* out, size_t out_stride,
+                                        uint32_t* out_len);
 
 /* Frame::count_bits / 8 (src/component/bitrepr.rs:275-287) of every frame from the decision records
  * alone: exactly the out_len flacenc_hip_pack_stereo_frames will produce.  Device pointers.  These
@@ -1280,7 +1315,10 @@ int flacenc_hip_decode_ranges_planar(flacenc_hip_handle* h, const uint8_t* bytes
  * FLACENC_HIP_ERR_BAD_ARGUMENT, with nothing written: a null pointer, an unknown memory kind, n_streams above 2^24, a span
  * that reaches past pcm_bytes, a slot that reaches past out_bytes, max_frames below
  * flacenc_hip_encode_streams_frames(...), a stream -- or a call -- of 2^31 frames or more, block_size outside 64..32767,
- * channels outside 1..8, bytes_per_sample outside 1..4, bits_per_sample outside 8..24.
+ * channels outside 1..8, bytes_per_sample outside 1..4, bits_per_sample outside 8..24 -- after
+ * flacenc_hip_set_max_encode_bits_per_sample(h, 32) outside 8..32, and more than 24 bits at bytes_per_sample other than 4
+ * (flacenc_hip_encode_streams_planar: with FLACENC_HIP_SAMPLE_F32).  A class of more than 24 bits runs
+ * the step of flacenc_hip_encode_pack_frames_wide in place of the frame-level calls; every other class runs as it always has.
  * The plan: a class is (channels, bits_per_sample, bytes_per_sample, sample_rate).  The full blocks of all streams of a
  * class are one run, cut into frame-level calls of at most clamp(48 MiB / frame bytes, 768, 8192) frames; the last blocks
  * of a class are one further run PER DISTINCT LENGTH, since the analysis kernels take one block size per launch (a corpus
@@ -1299,7 +1337,7 @@ struct flacenc_hip_pcm_stream_desc {
   uint64_t out_offset;       /* its slot: bytes [out_offset, out_offset + out_capacity) of `out` */
   uint64_t out_capacity;
   uint32_t channels;         /* 1..8; 2 = the stereo decision, else Independent(channels), as flacenc_hip_encode_pcm */
-  uint32_t bits_per_sample;  /* 8..24 */
+  uint32_t bits_per_sample;  /* 8..24; ..32 after flacenc_hip_set_max_encode_bits_per_sample(h, 32) */
   uint32_t bytes_per_sample; /* 1..4 */
   uint32_t sample_rate;
 };

@@ -301,6 +301,8 @@ extern "C" {
     pub fn flacenc_hip_set_precision_floor(h: *mut Handle, floor: u32) -> c_int;
     /// The deepest FLAC stream the decode calls of a handle take, `24` (a fresh handle) or `32` bits per sample.
     pub fn flacenc_hip_set_max_bits_per_sample(h: *mut Handle, bits: u32) -> c_int;
+    /// The deepest PCM the stream-level encode calls of a handle take, `24` (a fresh handle) or `32` bits per sample.
+    pub fn flacenc_hip_set_max_encode_bits_per_sample(h: *mut Handle, bits: u32) -> c_int;
     /// One extra-window entry's weights over a block, on the host.
     pub fn flacenc_hip_lpc_window_weights(
         window_type: u32, alpha: f32, start: u32, end: u32, block_size: u32, out: *mut f32,
@@ -360,6 +362,14 @@ extern "C" {
         h: *mut Handle, cfg: *const FrameConfig, frames: *const i32, n_frames: usize, channels: u32, block_size: u32,
         stride: usize, bits_per_sample: u32, sample_rate: u32, first_frame_number: u32, frame_number_step: u32,
         results: *mut ChannelResult, out: *mut u8, out_stride: usize, out_len: *mut u32, stream: *mut c_void,
+    ) -> c_int;
+    /// The wide encode path: frames of 8..=32 bits per sample on 64-bit integers (Constant, Verbatim, fixed predictors,
+    /// the stereo decision for 2 channels); the arguments of `flacenc_hip_encode_pack_frames_async` without the records
+    /// and the stream: device pointers, blocking on the handle's stream.
+    pub fn flacenc_hip_encode_pack_frames_wide(
+        h: *mut Handle, cfg: *const FrameConfig, frames: *const i32, n_frames: usize, channels: u32, block_size: u32,
+        stride: usize, bits_per_sample: u32, sample_rate: u32, first_frame_number: u32, frame_number_step: u32,
+        out: *mut u8, out_stride: usize, out_len: *mut u32,
     ) -> c_int;
     pub fn flacenc_hip_stereo_frame_lengths_async(
         h: *mut Handle, results: *const StereoFrameResult, n_frames: usize, block_size: u32, bits_per_sample: u32,
@@ -611,11 +621,20 @@ impl Gpu {
     }
 
     /// The deepest FLAC stream the decode calls take on this handle: 24 (a fresh handle, the reference's limit) or 32.
-    /// The encode calls take at most 24 bits whatever the setting.
+    /// The encode calls do not read it: `set_max_encode_bits_per_sample` is theirs.
     pub fn set_max_bits_per_sample(&self, bits: u32) -> Result<(), EncodeError> {
         match unsafe { flacenc_hip_set_max_bits_per_sample(self.0, bits) } {
             OK => Ok(()),
             _ => Err(EncodeError::Config(VerifyError::new("max_bits_per_sample", "must be 24 or 32"))),
+        }
+    }
+
+    /// The deepest PCM `encode_pcm`, `encode_streams` and `encode_streams_planar` (int32 elements) take on this handle:
+    /// 24 (a fresh handle) or 32.  More than 24 bits come in 4-byte samples and run the wide path.
+    pub fn set_max_encode_bits_per_sample(&self, bits: u32) -> Result<(), EncodeError> {
+        match unsafe { flacenc_hip_set_max_encode_bits_per_sample(self.0, bits) } {
+            OK => Ok(()),
+            _ => Err(EncodeError::Config(VerifyError::new("max_encode_bits_per_sample", "must be 24 or 32"))),
         }
     }
 }

@@ -1,6 +1,6 @@
 """End-to-end demo: PCM -> .flac with every per-frame stage on the GPU.
 
-Reads a 16/24-bit stereo WAV (or synthesises one), cuts it into 4096-sample frames, runs
+Reads a 16/24/32-bit stereo WAV (or synthesises one), cuts it into 4096-sample frames, runs
 flacenc_hip_encode_stereo_frames (analysis + encode_frame's decisions) and
 flacenc_hip_pack_stereo_frames (Frame::write), and writes "fLaC" + STREAMINFO + the frames.
 What stays on the host is what the reference keeps serial too: the container's 42 bytes and the
@@ -9,8 +9,11 @@ frame-level entry points take any block size.
 
     python tools/encode_flac.py [in.wav] out.flac [--seconds 10] [--levels L] [--wasted-bits] [--order-search]
                                   [--window-search] [--order-guess [K]] [--precision-search [FLOOR]] [--rice-escape]
-                                  [--seektable SECONDS]
+                                  [--seektable SECONDS] [--bits N]
 
+More than 24 bits per sample -- a 32-bit WAV, or --bits N on the synthetic source -- go through flacenc_hip_encode_pcm on
+the wide path after flacenc_hip_set_max_encode_bits_per_sample(h, 32): fixed predictors on 64-bit integers, of the
+switches only --wasted-bits and --seektable apply, and STREAMINFO says the depth.
 With --levels L the stream is variable-blocking: flacenc_hip_encode_variable codes each superblock of 4096 samples as
 the tiling into blocks of 4096 .. 4096 / 2^(L-1) that is shortest, and STREAMINFO announces the smallest chosen block
 (the last frame aside) and 4096 as the block-size range.
@@ -104,6 +107,25 @@ def encode_pcm(pcm, bps, rate, handle, block_size=4096, use_fixed=True, lpc_orde
     return head + b"".join(packed), np.concatenate(records)
 
 
+def encode_pcm_deep(pcm, bps, rate, handle, block_size=4096, flags=0, seektable=None):
+    """pcm int32 [n_samples, channels] of 25..32 bits -> (.flac bytes, frame lengths): flacenc_hip_encode_pcm on the wide
+    path (Constant, Verbatim, fixed predictors by exact bit counts; a 33-bit side channel for two channels), which the
+    handle takes after flacenc_hip_set_max_encode_bits_per_sample(h, 32).  STREAMINFO says `bps`."""
+    handle.set_max_encode_bits_per_sample(32)
+    cfg = _capi.make_frame_config(_capi.make_config(flags=flags & _capi.FLAG_WASTED_BITS), use_fixed=True,
+                                  fixed_order_sel=_capi.ORDERSEL_BITCOUNT)
+    total, channels = pcm.shape
+    raw = np.ascontiguousarray(pcm).astype("<i4").view(np.uint8).reshape(-1)
+    data, lens = handle.encode_pcm(raw, channels, cfg, 4, bps, block_size, rate, frame_number_step=1)
+    sizes = [int(v) for v in lens]
+    head = b"fLaC" + stream_info_block(block_size, min(sizes), max(sizes), rate, channels, bps, total,
+                                       hashlib.md5(raw.tobytes()).digest(), last=seektable is None)
+    if seektable is not None:
+        blocks = [min(block_size, total - t) for t in range(0, total, block_size)]
+        head += seektable_for(sizes, blocks, rate, seektable)
+    return head + data.tobytes(), np.array(sizes)
+
+
 def encode_pcm_variable(pcm, bps, rate, handle, block_size=4096, levels=3, use_fixed=True, lpc_order=8, flags=0,
                         seektable=None):
     """pcm int32 [n_samples, channels] -> (.flac bytes, dict of encode_variable's outputs): the block-size search over
@@ -161,6 +183,9 @@ def main():
     ap.add_argument("--seektable", type=float, default=None, metavar="SECONDS",
                     help="write a SEEKTABLE block with one seek point per SECONDS (tools/crop_flac.py starts at them)")
     ap.add_argument("--lpc-order", type=int, default=8)
+    ap.add_argument("--bits", type=int, default=0, metavar="N",
+                    help="the synthetic source at N bits per sample (16-bit content shifted); more than 24 bits, like a "
+                         "32-bit WAV, takes the wide path (flacenc_hip_set_max_encode_bits_per_sample) and STREAMINFO says N")
     args = ap.parse_args()
     if args.order_guess and args.order_search:
         ap.error("--order-guess and --order-search exclude each other")
@@ -181,7 +206,7 @@ def main():
     n = 4096
     if len(args.paths) == 2:
         with wave.open(args.paths[0], "rb") as w:
-            assert w.getnchannels() == 2 and w.getsampwidth() in (2, 3)
+            assert w.getnchannels() == 2 and w.getsampwidth() in (2, 3, 4)
             bps, rate = 8 * w.getsampwidth(), w.getframerate()
             raw = np.frombuffer(w.readframes(w.getnframes()), np.uint8).reshape(-1, 2, w.getsampwidth())
         pad = np.zeros(raw.shape[:2] + (4 - raw.shape[2],), np.uint8)
@@ -192,6 +217,18 @@ def main():
         nf = (nsamp + n - 1) // n
         pcm = np.ascontiguousarray(_capi.sigen_frames(nf, 2, n, bps, rate / 440.0, 0.8, 0.2, seed=1)
                                    .transpose(0, 2, 1)).reshape(-1, 2)[:nsamp]
+    if args.bits:
+        assert len(args.paths) == 1 and 8 <= args.bits <= 32, "--bits N (8..32) goes with the synthetic source"
+        bps, pcm = args.bits, pcm << (args.bits - 16) if args.bits >= 16 else pcm >> (16 - args.bits)
+    if bps > 24:
+        if args.levels:
+            ap.error("--levels stops at 24 bits per sample")
+        data, sizes = encode_pcm_deep(pcm, bps, rate, handle, block_size=n, flags=flags, seektable=args.seektable)
+        with open(args.paths[-1], "wb") as f:
+            f.write(data)
+        print(f"{len(sizes)} frames, {len(data)} bytes, {len(data) / (pcm.shape[0] * 2 * 4):.4f} of the PCM size; "
+              f"{bps} bits per sample on the wide path")
+        return
     if args.levels:
         data, v = encode_pcm_variable(pcm, bps, rate, handle, block_size=n, levels=args.levels,
                                       lpc_order=args.lpc_order, flags=flags, seektable=args.seektable)

@@ -33,7 +33,7 @@ def read_wav(path):
     """-> (packed interleaved little-endian signed PCM as uint8, channels, bits, width, rate, samples per channel)."""
     with wave.open(path, "rb") as w:
         ch, width, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
-        if not (1 <= ch <= 8 and width in (1, 2, 3)):
+        if not (1 <= ch <= 8 and width in (1, 2, 3, 4)):
             raise SystemExit(f"{path}: {ch} channels of {8 * width} bits are not supported")
         raw = np.frombuffer(w.readframes(n), np.uint8)
     if width == 1:
@@ -56,6 +56,8 @@ def encode_many(handle, wavs, block_size=4096, lpc_order=8, flags=0):
         out_at += cap
     pcm = np.concatenate([w[0] for w in wavs]) if wavs else np.zeros(0, np.uint8)
     out = np.empty(max(1, out_at), np.uint8)
+    if any(w[2] > 24 for w in wavs):  # 32-bit WAVs: the wide path, opt-in per handle
+        handle.set_max_encode_bits_per_sample(32)
     lens, totals, call, _ = handle.encode_streams(pcm, table, cfg, block_size, out)
     digests = handle.md5_spans(pcm, table["offset"], [w[0].size for w in wavs])
     files = []
@@ -76,6 +78,8 @@ def encode_array(handle, x, lengths, bits, rate, block_size=4096, lpc_order=8, f
     from flacenc_rs_amd import crops
 
     cfg = _capi.make_frame_config(_capi.make_config(lpc_order=lpc_order, flags=flags), use_fixed=True)
+    if bits > 24:  # int32 elements alone; the wide path, opt-in per handle
+        handle.set_max_encode_bits_per_sample(32)
     B, C, T = x.shape
     n = np.full(B, T, np.int64) if lengths is None else np.asarray(lengths, np.int64).reshape(-1)
     r = crops.encode_crops(handle, torch.from_numpy(np.ascontiguousarray(x)), n, bits, rate, cfg, block_size)
@@ -95,7 +99,7 @@ def main():
     ap.add_argument("wavs", nargs="*")
     ap.add_argument("--npy", help="a [B, C, T] float32 or int32 array in place of WAV files")
     ap.add_argument("--lengths", help="with --npy: a .npy of B valid lengths")
-    ap.add_argument("--bits", type=int, help="with --npy: bits per sample, 8..24")
+    ap.add_argument("--bits", type=int, help="with --npy: bits per sample, 8..24, or 25..32 for int32 elements (the wide path)")
     ap.add_argument("--rate", type=int, help="with --npy: the sample rate")
     ap.add_argument("--out-dir", required=True)
     ap.add_argument("--block-size", type=int, default=4096)
